@@ -26,11 +26,15 @@ rerank over 7 alphas -> host formatting; at N > 1 the corpus is row-sharded and 
 
 Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel, the fp32 MFMA GEMM that serves every
 encoder linear: algorithmic flops per launch / average launch duration, both measured live over the timed
-region with hipEvent pairs recorded by the library on the launch stream (gdr_prof_*).  `cpu_baseline` is the
-oracle ("port" of the reference's CPU path) timed on this box's host cores on a bounded sample.  `stages` (N = 1,
-measured AFTER the headline timed region, never part of `value`) carries the other stages of the path: latency-mode
-similarity against the HBM roof, generate() at the C3 and infer.sh settings against their flop / weight-byte floors,
-the two-stage C3 rate and the bf16 precision mode.
+region with hipEvent pairs recorded by the library on the launch stream (gdr_prof_*).
+
+A plain run sets up, warms up, times --steps steps, writes the last step's outputs (--dump-outputs DIR) and prints the
+line.  Everything else is behind --full (then the `#stages` line and bench_stages.json come first): `cpu_baseline`, the
+oracle ("port" of the reference's CPU path) timed on this box's host cores on a bounded sample; `recall` / `parity`
+against the oracle; the same step in its other forms (other similarity form, padded encoder, exploratory split forms);
+for c3 / c5 the profiled replay behind `roofline`; and `stages` (N = 1, measured AFTER the headline timed region, never
+part of `value`), the other stages of the path: latency-mode similarity against the HBM roof, generate() at the C3 and
+infer.sh settings against their flop / weight-byte floors, the two-stage C3 / C5 rates and the bf16 precision mode.
 """
 import argparse
 import ctypes as C
@@ -111,6 +115,34 @@ def emit(result, detail=None):
     sys.stdout.flush()
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as path/<name>.npy, float32 if it is a float of 32 bits or fewer, float64 otherwise (ids are
+    exact in float64).  All arrays share their leading (query) axis; if together they exceed DUMP_LIMIT_BYTES, the same fixed,
+    seeded sample of queries is taken from each and its query numbers go to path/rows.npy."""
+    out = {}
+    for name, x in arrays.items():
+        if isinstance(x, torch.Tensor):
+            x = x.detach()
+            x = (x.float() if x.is_floating_point() and x.element_size() <= 4 else x.double()).cpu().numpy()
+        x = np.asarray(x)
+        out[name] = x.astype(np.float32 if x.dtype.kind == "f" and x.dtype.itemsize <= 4 else np.float64)
+    n = {x.shape[0] for x in out.values()}
+    assert len(n) == 1, f"dump_outputs: leading axes differ {n}"
+    n = n.pop()
+    total = sum(x.nbytes for x in out.values())
+    if total + 128 * len(out) > DUMP_LIMIT_BYTES:         # 128: an .npy header
+        per_row = total / n + 8                           # + its entry in rows.npy
+        rows = np.sort(np.random.default_rng(0).choice(n, int((DUMP_LIMIT_BYTES - 4096) // per_row), replace=False))
+        out = {name: x[rows] for name, x in out.items()}
+        out["rows"] = rows.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for name, x in out.items():
+        np.save(os.path.join(path, name + ".npy"), x)
+
+
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -158,6 +190,12 @@ def parse():
                     help="c2: the library brackets every dense launch of every N-th step of the timed region with a hipEvent pair (the "
                          "roofline's per-launch durations); 1 = every step.  Two event packets per launch are not free: around every "
                          "launch of every step they cost 2.4 %% of the step's throughput")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: CPU baseline, recall / parity against the oracle, the other "
+                         "forms of the step, the c3 / c5 profiled replay and the stages (the --no-* options below select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy "
+                         "(float32 / float64; ids as float64; at most 64 MB in all, else the same seeded sample of rows of each)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-recall", action="store_true")
     ap.add_argument("--no-parity", action="store_true", help="c3 / c5: skip the oracle check of the step's output")
@@ -170,6 +208,8 @@ def parse():
                     help="stages: also run the two-stage path at 128 / 256 / 1024 / 2048 queries per batch (where the decode chain stops "
                          "being launch-bound); off by default so that the default run stays near 40 s")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if a.batch is None:
         a.batch = 64 if a.workload == "c3" else 512
     if a.corpus is None:
@@ -585,7 +625,7 @@ def stages(dev, cfg, D, D_dev, a):
         import torch.distributed as dist5
         a5 = argparse.Namespace(**vars(a))
         a5.workload, a5.corpus, a5.batch, a5.beams, a5.dtype, a5.steps, a5.warmup, a5.depth = "c5", 1000000, 512, 30, "bf16", 3, 1, 2
-        a5.constrained, a5.parity_queries = False, None
+        a5.constrained, a5.parity_queries, a5.full, a5.dump_outputs = False, None, True, None
         a5.parity_only = not (a.no_cpu_baseline or a.no_parity)
         a5.no_parity = a.no_cpu_baseline or a.no_parity
         t5 = time.perf_counter()
@@ -781,7 +821,7 @@ def two_stage_main(a):
     rank, world, dev, dist = init_ranks(a)
     result, detail, violations = two_stage_measure(a, rank, world, dev, dist)
     if rank == 0:
-        emit(result, detail)
+        emit(result, detail if a.full else None)
         if violations:
             raise SystemExit(f"bench: {violations} queries of the step differ from the CPU oracle outside the parity rule")
     if dist.is_initialized():
@@ -848,22 +888,25 @@ def two_stage_measure(a, rank, world, dev, dist):
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-    # the dominant kernel class (every linear: encoder, decoder, adaptor, head) from a PROFILED replay of the same steps right
-    # after the timed region — ~1 100 launches per step, each bracketed by two hipEvents, would slow a launch-bound chain if
-    # they were recorded inside it
-    lib = _ffi.lib()
-    n_prof = min(a.steps, 3)
-    _ffi.check(lib.gdr_prof_enable(4000 * n_prof * max(1, a.depth)), "gdr_prof_enable")
-    run(n_prof)
-    torch.cuda.synchronize()
-    n_l, ms_l, w_l = (C.c_int64 * 8)(), (C.c_double * 8)(), (C.c_double * 8)()
-    lost = lib.gdr_prof_collect(n_l, ms_l, w_l)
-    if lost < 0:
-        _ffi.check(lost, "gdr_prof_collect")
+    if a.dump_outputs and rank == 0 and last is not None:      # this rank's queries: per-alpha rerank lists and beam scores
+        dump_outputs(a.dump_outputs, {"rerank_values": last["rerank_values"], "rerank_doc_ids": last["doc_id_tensor"],
+                                      "beam_scores": np.asarray(last["inf_result_batch_prob"], np.float64).reshape(B, R)})
     n_cand = int(sum(len(look[s_]) for s_ in last["clusters"][0])) if last is not None else 0
+    # --full: the dominant kernel class (every linear: encoder, decoder, adaptor, head) from a PROFILED replay of the same steps
+    # right after the timed region — ~1 100 launches per step, each bracketed by two hipEvents, would slow a launch-bound chain
+    # if they were recorded inside it
+    if a.full:
+        lib = _ffi.lib()
+        n_prof = min(a.steps, 3)
+        _ffi.check(lib.gdr_prof_enable(4000 * n_prof * max(1, a.depth)), "gdr_prof_enable")
+        run(n_prof)
+        torch.cuda.synchronize()
+        n_l, ms_l, w_l = (C.c_int64 * 8)(), (C.c_double * 8)(), (C.c_double * 8)()
+        lost = lib.gdr_prof_collect(n_l, ms_l, w_l)
+        if lost < 0:
+            _ffi.check(lost, "gdr_prof_collect")
     if rank == 0:
         peak = BF16_MFMA_PEAK_TFLOPS if bf16 else F32_MFMA_PEAK_TFLOPS
-        lin_tf = w_l[0] / (ms_l[0] * 1e-3) / 1e12 if ms_l[0] > 0 else 0.0
         tag = a.workload.upper() + ("/constrained" if a.constrained else "") + ("/sharded" if sharded is not None else "")
         result = {
             "metric": "queries/sec on NQ-320k (768-d)" if a.workload == "c3" else "queries/sec on a 1Mx768 corpus (TriviaQA-scale)",
@@ -875,16 +918,19 @@ def two_stage_measure(a, rank, world, dev, dist):
                        "batch_per_gpu": B, "global_batch": B * world, "beams": R, "seq_len": 40, "corpus_rows": a.corpus,
                        "dim": cfg.d_model, "k": R, "alphas": 7, "candidates_per_query": n_cand, "pipeline_depth": max(1, a.depth),
                        "docid_depth": id_depth, "corpus_setup_s": round(t_corpus, 2), "corpus_rows_on_host": int(D.shape[0])},
-            "roofline": {"bound": "mfma",
-                         "kernel": ("every linear of the step (encoder, decoder, adaptor, head): gdr::gemm_nt_bf16_*" if bf16 else
-                                    "every linear of the step: gdr::gemm_nt_f32_small_kernel (decode rows) + persistent / stream-K (encoder)"),
-                         "achieved": lin_tf, "peak": peak, "unit": "TFLOP/s", "frac": lin_tf / peak, "traffic": None,
-                         "launches_per_step": int(n_l[0]) / n_prof, "avg_launch_ms": ms_l[0] / max(1, int(n_l[0])),
-                         "linear_ms_per_step": ms_l[0] / n_prof, "events_lost": int(lost)},
-            "kernels": {"attention_ms_per_step": ms_l[3] / n_prof, "rerank_dot_ms_per_step": ms_l[6] / n_prof,
-                        "rerank_select_ms_per_step": ms_l[5] / n_prof, "splitk_reduce_ms_per_step": ms_l[7] / n_prof},
-            "cpu_baseline": None, "parity": None, "recall": None,
+            "roofline": None, "kernels": None, "cpu_baseline": None, "parity": None, "recall": None,
         }
+        if a.full:
+            lin_tf = w_l[0] / (ms_l[0] * 1e-3) / 1e12 if ms_l[0] > 0 else 0.0
+            result["roofline"] = {
+                "bound": "mfma",
+                "kernel": ("every linear of the step (encoder, decoder, adaptor, head): gdr::gemm_nt_bf16_*" if bf16 else
+                           "every linear of the step: gdr::gemm_nt_f32_small_kernel (decode rows) + persistent / stream-K (encoder)"),
+                "achieved": lin_tf, "peak": peak, "unit": "TFLOP/s", "frac": lin_tf / peak, "traffic": None,
+                "launches_per_step": int(n_l[0]) / n_prof, "avg_launch_ms": ms_l[0] / max(1, int(n_l[0])),
+                "linear_ms_per_step": ms_l[0] / n_prof, "events_lost": int(lost)}
+            result["kernels"] = {"attention_ms_per_step": ms_l[3] / n_prof, "rerank_dot_ms_per_step": ms_l[6] / n_prof,
+                                 "rerank_select_ms_per_step": ms_l[5] / n_prof, "splitk_reduce_ms_per_step": ms_l[7] / n_prof}
         detail = {"config_note": "a step = one batch per GPU through validation_step_i: ragged t5-base encoder -> docid beam decode "
                   f"(beam {R}, 9 steps, prefix table) -> device cluster lookup -> in-cluster rerank over 7 alphas "
                   f"(top-{R}) -> host formatting; {max(1, a.depth)} batches in flight; corpus resident in HBM"
@@ -893,10 +939,10 @@ def two_stage_measure(a, rank, world, dev, dist):
                   + (f"; corpus row-sharded {world} ways, stage 2 = one all-gather of queries + candidate blocks, per-shard "
                      "scoring, one all-to-all of the packed lists, merge" if sharded is not None else ""),
                   "roofline_source": f"profiled replay of {n_prof} step(s) after the timed region (hipEvent pairs on the launch streams; "
-                                     "summed durations of two overlapping chains can exceed the step's wall time)"}
+                                     "summed durations of two overlapping chains can exceed the step's wall time)"} if a.full else None
         violations = 0
         parity_only = getattr(a, "parity_only", False)        # stages(): the oracle check without the CPU timing leg
-        if world == 1 and not a.no_parity and (parity_only or not a.no_cpu_baseline):
+        if a.full and world == 1 and not a.no_parity and (parity_only or not a.no_cpu_baseline):
             tree = None
             if a.constrained:
                 from oracle import beam_ref, codec_ref
@@ -905,7 +951,7 @@ def two_stage_measure(a, rank, world, dev, dist):
                                                 nq1=a.parity_queries[0] if a.parity_queries else (2 if R > 10 else 4),
                                                 nq2=a.parity_queries[1] if a.parity_queries else 64)
             violations = result["parity"]["stage1_rows_violating"] + result["parity"]["stage2_rows_violating"]
-        if world == 1 and not a.no_cpu_baseline and not parity_only and not violations:
+        if a.full and world == 1 and not a.no_cpu_baseline and not parity_only and not violations:
             result["cpu_baseline"] = cpu_baseline_two_stage(sd, cfg, ids_all, mask_all, D, look, R, args.score_rate,
                                                             n=1 if R > 10 else 2, reps=1 if R > 10 else 3)
         return result, detail, violations
@@ -995,11 +1041,13 @@ def main():
     if overflowed:
         raise SystemExit(f"bench: {overflowed} queries overflowed their candidate lists — the step did not compute "
                          "the exact top-k (use exact_on_overflow=True for such data)")
+    if a.dump_outputs and rank == 0:                     # this rank's queries: top-k values and global doc ids
+        dump_outputs(a.dump_outputs, {"topk_values": out[0], "topk_ids": out[1]})
     # ---- the same step with the OTHER similarity form — all-fp32 when the headline runs the bf16 pre-filter (the default), the
     # pre-filter when it runs all-fp32 (--sim-prefilter off) — timed AFTER the headline region with the same protocol, reported
     # beside it, never as `value`.  Both forms return the top-k of the fp32 scores for every input (tests/test_gpu_prefilter.py).
     pre = None
-    if world == 1 and not bf16 and not a.no_stages:
+    if a.full and world == 1 and not bf16 and not a.no_stages:
         P = D_dev if use_pre else ops.PrefilteredCorpus(D_raw)
         index_p = ShardedIndex(D_raw if use_pre else P, lo, exact=False)
 
@@ -1021,7 +1069,7 @@ def main():
     # ---- the same step with the PADDED encoder (every one of the batch x 40 token rows through all 48 linears, as the reference
     # computes it): the reference-equivalent-work number beside the headline's exact work elimination; same protocol, own roofline
     padded = None
-    if world == 1 and not bf16 and ragged and not a.no_stages and not form_terms:
+    if a.full and world == 1 and not bf16 and ragged and not a.no_stages and not form_terms:
         def step_pad():
             _, pooled = enc.forward(ids, mask, want_hidden=False, ragged=False)
             return index.search(pooled, a.k, return_status=True)
@@ -1048,7 +1096,7 @@ def main():
     # split-bf16 form (gdr_t5_encoder_forward_ragged_split: fp32 operands carried as three bf16 planes, six bf16 MFMA products, fp32
     # accumulate — the fp32 linear's error against float64, not its bits).  Its top-k lists are held to the fp32 step's by the top-k rule.
     split = None
-    if world == 1 and not bf16 and ragged and not a.no_stages and not form_terms:
+    if a.full and world == 1 and not bf16 and ragged and not a.no_stages and not form_terms:
         _, p_f = enc.forward(ids, mask, want_hidden=False, ragged=True, live_rows_hint=live_rows)
         out_f = index.search(p_f, a.k, return_status=True)
         split = {}
@@ -1177,7 +1225,7 @@ def main():
         # rows held to the top-k parity rule.  Nothing outside this leg touches oracle/.
         result["cpu_baseline"] = None
         result["recall"] = None
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             if not a.no_recall:
                 from oracle import retrieval_ref
                 Q, gold = synth.make_queries(D, a.batch)
@@ -1204,7 +1252,7 @@ def main():
                     raise SystemExit(f"bench: {bad} rows differ from the CPU oracle outside tolerance-tie groups")
             result["cpu_baseline"] = cpu_baseline(sd, cfg, ids_all, mask_all, D, a.k)
         result["stages_summary"] = None
-        if world == 1 and not a.no_stages and not bf16 and not form_terms:
+        if a.full and world == 1 and not a.no_stages and not bf16 and not form_terms:
             del enc
             if pre is not None:
                 del P, index_p
@@ -1243,7 +1291,7 @@ def main():
                     detail["stages"]["c2_step_bf16_prefilter_note"] = "the headline step with " + note
                     result["with_bf16_prefilter"] = beside
                     result["stages_summary"]["c2_prefilter_qps"] = pre["queries_per_s"]
-        emit(result, detail)
+        emit(result, detail if a.full else None)
     if dist.is_initialized():
         dist.barrier()
         dist.destroy_process_group()

@@ -1,5 +1,6 @@
 """bench.py's output contract (the round driver parses this line): one JSON line on stdout with the agreed keys, the
-`roofline` and `cpu_baseline` objects, recall parity, on a reduced workload so that the test takes seconds."""
+`roofline` and `cpu_baseline` objects, recall parity (--full), on a reduced workload so that the test takes seconds; a plain run
+(no --full) prints the headline line alone and writes its outputs with --dump-outputs."""
 import json
 import os
 import subprocess
@@ -11,14 +12,17 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _run(*extra, with_detail=False):
+def _run(*extra, with_detail=False, full=True):
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "64",
-                          "--corpus", "30000", *extra], capture_output=True, text=True, timeout=900, cwd=ROOT)
+                          "--corpus", "30000", *(["--full"] if full else []), *extra], capture_output=True, text=True, timeout=900,
+                         cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     all_lines = out.stdout.splitlines()
     lines = [l for l in all_lines if l.startswith("{")]
     assert len(lines) == 1, "exactly one JSON line on stdout"
     assert all_lines[-1] == lines[0], "the JSON line is the LAST line of stdout"
+    if not full:
+        assert all_lines == lines, "a plain run prints the headline line alone"
     # the round driver keeps the last 8 KB of stdout: the headline must fit with room to spare (round 4's line was 20 KB and was lost)
     assert len(lines[0]) <= 4096, len(lines[0])
     j = json.loads(lines[0])
@@ -34,8 +38,8 @@ def _run(*extra, with_detail=False):
 
 
 def test_bench_line_contract_fp32():
-    """The DEFAULT stage list (exactly what `python bench.py` runs, on a reduced corpus): the line's shape and length are those of
-    the full-size run — the stage keys do not depend on --corpus."""
+    """The DEFAULT stage list (exactly what `python bench.py --full` runs, on a reduced corpus): the line's shape and length are
+    those of the full-size run — the stage keys do not depend on --corpus."""
     j, det = _run(with_detail=True)
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                 "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline", "recall", "stages_summary"):
@@ -239,9 +243,41 @@ def test_bench_under_torchrun_one_rank_rccl():
         out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
                               "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
                               "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "64", "--corpus", "30000",
-                              "--no-cpu-baseline", "--no-stages", *extra], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                              "--full", "--no-cpu-baseline", "--no-stages", *extra], capture_output=True, text=True, timeout=600,
+                             cwd=ROOT)
         assert out.returncode == 0, out.stderr[-2000:]
         lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
         assert len(lines) == 1
         j = json.loads(lines[0])
         assert j["n_gpus"] == 1 and j["value"] > 0 and j["cpu_baseline"] is None
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_the_last_step(tmp_path):
+    """Without --full: --steps sets the timed steps, the line carries the headline (c2's roofline is measured inside the timed region)
+    and nothing of the --full legs, and --dump-outputs writes what the timed path returned in its last step — the same arrays from
+    run to run on the same arguments."""
+    import numpy as np
+    dumps = []
+    for r in range(2):
+        d = tmp_path / f"c2_{r}"
+        j = _run("--steps", "3", "--dump-outputs", str(d), full=False)
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline"):
+            assert key in j, key
+        assert j["steps"] == 3 and j["warmup"] == 1 and j["dtype"] == "f32" and j["higher_is_better"] is True
+        assert abs(j["value"] - 64 / (j["ms_per_step"] * 1e-3)) / j["value"] < 1e-3
+        assert j["roofline"]["timed_steps"] == 1 and j["roofline"]["launches"] == 48          # step 0 of 3 carries the events
+        assert j["cpu_baseline"] is None and j["recall"] is None and j["stages_summary"] is None and "all_fp32" not in j
+        v, i = np.load(d / "topk_values.npy"), np.load(d / "topk_ids.npy")
+        assert sorted(os.listdir(d)) == ["topk_ids.npy", "topk_values.npy"]
+        assert v.dtype == np.float32 and i.dtype == np.float64 and v.shape == i.shape == (64, 100)
+        assert np.all(np.diff(v, axis=1) <= 0) and np.all(i == np.round(i)) and i.min() >= 0 and i.max() < 30000
+        assert all(len(set(row)) == 100 for row in i.tolist())
+        dumps.append((v, i))
+    assert np.array_equal(dumps[0][1], dumps[1][1]) and np.allclose(dumps[0][0], dumps[1][0], rtol=0, atol=1e-6)
+    d = tmp_path / "c3"
+    k = _run("--workload", "c3", "--batch", "8", "--dump-outputs", str(d), full=False)
+    assert k["steps"] == 2 and k["roofline"] is None and k["parity"] is None and k["cpu_baseline"] is None and k["value"] > 0
+    assert abs(k["value"] - 8 / (k["ms_per_step"] * 1e-3)) / k["value"] < 1e-3
+    rv, ri, bs = np.load(d / "rerank_values.npy"), np.load(d / "rerank_doc_ids.npy"), np.load(d / "beam_scores.npy")
+    assert rv.dtype == np.float32 and rv.shape == ri.shape == (8, 7, 10) and ri.dtype == np.float64 and bs.shape == (8, 10)
+    assert np.all(ri == np.round(ri)) and ri.max() < 30000 and np.all(np.isfinite(bs))

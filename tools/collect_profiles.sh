@@ -22,9 +22,9 @@ python3 $ROOT/tools/trace_steps.py $(ls $OUT/stats_generate/*/*kernel_trace.csv 
 timeout -s KILL 600 rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES --output-format csv -d "$OUT/pmc_mfma_generate" -- python3 $ROOT/tools/prof_generate.py > "$OUT/pmc_mfma_generate.log" 2>&1
 timeout -s KILL 600 rocprofv3 --kernel-trace --pmc GRBM_GUI_ACTIVE SQ_WAVES --output-format csv -d "$OUT/pmc_clk_generate" -- python3 $ROOT/tools/prof_generate.py > "$OUT/pmc_clk_generate.log" 2>&1
 cd "$ROOT"
-python3 bench.py > "$OUT/bench_n1.json" 2> "$OUT/bench_n1.err"
-python3 bench.py --encoder padded --no-stages > "$OUT/bench_n1_padded.json" 2> "$OUT/bench_n1_padded.err"
-python3 bench.py --dtype bf16 --no-cpu-baseline > "$OUT/bench_bf16.json" 2> "$OUT/bench_bf16.err"
+python3 bench.py --full > "$OUT/bench_n1.json" 2> "$OUT/bench_n1.err"
+python3 bench.py --full --encoder padded --no-stages > "$OUT/bench_n1_padded.json" 2> "$OUT/bench_n1_padded.err"
+python3 bench.py --full --dtype bf16 --no-cpu-baseline > "$OUT/bench_bf16.json" 2> "$OUT/bench_bf16.err"
 # keep what travels back small: the per-dispatch traces are large
 find "$OUT" -name "*kernel_trace.csv" -size +8M -delete
 find "$OUT" -name "*.db" -delete

@@ -6,7 +6,7 @@ OUT=$ROOT/gpurun_out/$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 timeout -s KILL 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/bench" -- python3 $ROOT/bench.py --steps 7 --warmup 2 --no-cpu-baseline --no-recall --no-stages > "$OUT/bench.log" 2>&1
-timeout -s KILL 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/c5_depth1" -- python3 $ROOT/bench.py --workload c5 --depth 1 --steps 3 --warmup 1 --no-cpu-baseline > "$OUT/c5_depth1.log" 2>&1
+timeout -s KILL 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/c5_depth1" -- python3 $ROOT/bench.py --full --workload c5 --depth 1 --steps 3 --warmup 1 --no-cpu-baseline > "$OUT/c5_depth1.log" 2>&1
 timeout -s KILL 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/gen_64x10" -- python3 $ROOT/tools/prof_generate.py > "$OUT/gen_64x10.log" 2>&1
 cd "$ROOT"
 find "$OUT" -name "*kernel_trace.csv" -delete

@@ -6,8 +6,8 @@ ROOT=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p "$OUT"
 cd "$ROOT"
-python3 bench.py --workload c5 > "$OUT/bench_c5.json" 2> "$OUT/bench_c5.err"
-python3 bench.py --workload c3 > "$OUT/bench_c3.json" 2> "$OUT/bench_c3.err"
+python3 bench.py --full --workload c5 > "$OUT/bench_c5.json" 2> "$OUT/bench_c5.err"
+python3 bench.py --full --workload c3 > "$OUT/bench_c3.json" 2> "$OUT/bench_c3.err"
 cd /tmp && export TMPDIR=/tmp
 for b in 32 1; do
   rm -rf /tmp/sp
