@@ -179,6 +179,10 @@ __global__ __launch_bounds__(256) void bert_embed_packed_kernel(const float* __r
   }
 }
 
+// fp16 x 2 form: whether the wi GEMM's epilogue writes wo2's plane rows itself — the 256-row tile kernel only, asked with the launcher's own
+// predicate (virtual K = 3 d); otherwise wi stores fp32 in `ff` and a split launch makes the planes
+static bool bert_plane_epilogue(const GdrBertWeights& w, int64_t M) { return linear_bf16_tile_form(M, w.d_ff, w.d_model, 0, 3, 2) >= 192; }
+
 struct BertRagWs {
   size_t seq_len, seq_off, row_src, rows_total, ctx_cls, x_cls, t_cls, ff_cls, x16, pl_ff, total;
 };
@@ -195,9 +199,9 @@ static BertRagWs bert_rag_ws(const GdrBertWeights& w, int B, int L) {
   r.t_cls = o, o += align_up((size_t)B * d * 4, 256);
   r.ff_cls = o, o += align_up((size_t)B * w.d_ff * 4, 256);
   r.x16 = o, o += align_up(M * 2 * d * 2, 256);  // bf16 mode: the bf16 image of the block input x; fp16 x 2 form: its plane rows [M, 2 d]
-  // fp16 x 2 form: the plane rows of the GeLU output [M, 2 d_ff] — from 8 192 rows on the wi GEMM's epilogue writes them and the fp32 `ff`
-  // buffer (the same size) is free to hold them; below that both exist
-  r.pl_ff = o, o += align_up((M < 8192 ? M : 0) * 2 * (size_t)w.d_ff * 2, 256);
+  // fp16 x 2 form: the plane rows of the GeLU output [M, 2 d_ff] — where the wi GEMM's epilogue writes them the fp32 `ff` buffer (the
+  // same size) is free to hold them; where a split launch reads `ff` to make them both exist
+  r.pl_ff = o, o += align_up((bert_plane_epilogue(w, (int64_t)M) ? 0 : M) * 2 * (size_t)w.d_ff * 2, 256);
   r.total = o;
   return r;
 }
@@ -261,7 +265,8 @@ static int bert_ragged_impl(const GdrBertWeights* w, const int64_t* ids, const i
   hipLaunchKernelGGL(bert_embed_packed_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, stream, w->word_emb, w->pos_emb, w->type_emb,
                      ids, token_type_ids, row_src, rows_dev, L, d / 4, w->vocab_size, w->type_vocab, t);
   GDR_CHECK_LAUNCH("bert_embed_packed_kernel");
-  void* pl_ff = M < 8192 ? static_cast<void*>(base + rw.pl_ff) : static_cast<void*>(ff);
+  const bool plane_epi = bert_plane_epilogue(*w, M);
+  void* pl_ff = plane_epi ? static_cast<void*>(ff) : static_cast<void*>(base + rw.pl_ff);
   const int ld_d = 2 * d, ld_ff = 2 * dff;  // fp16 x 2 plane rows
   if ((rc = launch_layernorm_dev(t, w->emb_ln_w, w->emb_ln_b, x, rows_dev, M, d, w->eps, nullptr, stream, (bf16 || f16s) ? x16 : nullptr,
                                  f16s ? ld_d : 0)))
@@ -320,7 +325,6 @@ static int bert_ragged_impl(const GdrBertWeights* w, const int64_t* ids, const i
     const bool last = i + 1 == w->num_layers;
     if (f16s) {
       // x (fp32) and its plane rows x16 come from the LayerNorm in front; attention is the fp32 path's
-      const bool big = M >= 8192;  // the plane epilogue lives in the 256-row tile kernel
       if ((rc = gsplit(x16, ly.wqkv, qkv, 3 * d, M, rows_dev, 3 * d, d, 0, ly.bqkv, nullptr, 0))) return rc;
       if ((rc = launch_attention(at, stream))) return rc;
       if (pooled_only && last) {
@@ -337,7 +341,7 @@ static int bert_ragged_impl(const GdrBertWeights* w, const int64_t* ids, const i
       if ((rc = launch_split_f32_bf16x3(ctx, d, x16, ld_d, M, d, rows_dev, stream, 1))) return rc;  // x16 is free: x's planes fed qkv already
       if ((rc = gsplit(x16, ly.wo, t, d, M, rows_dev, d, d, 0, ly.bo, x, 0))) return rc;
       if ((rc = launch_layernorm_dev(t, ly.ln1_w, ly.ln1_b, x, rows_dev, M, d, w->eps, nullptr, stream, x16, ld_d))) return rc;
-      if (big) {
+      if (plane_epi) {
         if ((rc = gsplit(x16, ly.wi, pl_ff, ld_ff, M, rows_dev, dff, d, 2, ly.bi, nullptr, 1))) return rc;  // GeLU, plane rows out
       } else {
         if ((rc = gsplit(x16, ly.wi, ff, dff, M, rows_dev, dff, d, 2, ly.bi, nullptr, 0))) return rc;

@@ -491,8 +491,11 @@ static int ragged_split_impl(const GdrT5EncoderWeights* w, const int64_t* ids, c
     if (int rc_ = launch_split_f32_bf16x3(A, K, P, split_row_elems(K, f16), rows, K, md, stream, f16)) return rc_;
     return gemm(P, W, C, ldc, rows, md, N, K, act, residual, 0);
   };
-  // the wi GEMM's plane epilogue lives in the 256-row tile kernel, which serves >= 8 192 rows
+  // from 8 192 rows the norms write the operand planes themselves; the wi GEMM's plane epilogue lives in the 256-row tile kernel only,
+  // which the launcher picks by the VIRTUAL contraction length (6 K0 / 3 K0 >= 2 048: not at d_model = 512 with 3 terms or fp16 x 2) —
+  // asked here with the launcher's own predicate; where it says no, wi stores fp32 and a split launch makes wo_ff's planes
   const bool fuse = fuse_on && M >= 8192;
+  const bool fuse_wi = fuse && linear_bf16_tile_form(M, dff, d, 0, f16 ? 3 : 2, terms) >= 192;
   const int ld_d = split_row_elems(d, f16), ld_ff = split_row_elems(dff, f16);
   if ((rc = launch_embed_packed(w->embed, ids, row_src, rows_dev, M, d, dm.vocab_size, h, stream))) return rc;
   AttnArgs at{};
@@ -528,10 +531,14 @@ static int ragged_split_impl(const GdrT5EncoderWeights* w, const int64_t* ids, c
       return launch_rmsnorm(h_cls, w->final_ln, out_pooled, B, d, dm.eps, nullptr, 1, stream);
     }
     if ((rc = linear(ctx, ly.wo, h, d, M, rows_dev, d, inner, 0, h))) return rc;
-    if (fuse) {  // norm -> planes; wi's ReLU epilogue writes the planes of wo_ff's operand
+    if (fuse_wi) {  // norm -> planes; wi's ReLU epilogue writes the planes of wo_ff's operand
       if ((rc = launch_rmsnorm_planes(h, ly.ln_ff, nullptr, planes, ld_d, rows_dev, M, d, dm.eps, stream, f16))) return rc;
       if ((rc = gemm(planes, ly.wi, planes_ff, ld_ff, M, rows_dev, dff, d, 1, nullptr, 1))) return rc;
       if ((rc = gemm(planes_ff, ly.wo_ff, h, d, M, rows_dev, d, dff, 0, h, 0))) return rc;
+    } else if (fuse) {  // norm -> planes; wi stores fp32 (no plane epilogue at this virtual K), then the split launch for wo_ff
+      if ((rc = launch_rmsnorm_planes(h, ly.ln_ff, nullptr, planes, ld_d, rows_dev, M, d, dm.eps, stream, f16))) return rc;
+      if ((rc = gemm(planes, ly.wi, ff, dff, M, rows_dev, dff, d, 1, nullptr, 0))) return rc;
+      if ((rc = linear(ff, ly.wo_ff, h, d, M, rows_dev, d, dff, 0, h))) return rc;
     } else {
       if ((rc = launch_rmsnorm_dev(h, ly.ln_ff, nx, rows_dev, M, d, dm.eps, stream))) return rc;
       if ((rc = linear(nx, ly.wi, ff, dff, M, rows_dev, dff, d, 1, nullptr))) return rc;

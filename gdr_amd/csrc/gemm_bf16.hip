@@ -63,15 +63,14 @@ __device__ __forceinline__ int plane_of(int p, bool is_w) {
   if (SPLIT == 1) return ((is_w ? 0x102010 : 0x120100) >> (4 * p)) & 3;
   return ((is_w ? 0x001 : 0x010) >> (4 * p)) & 3;
 }
-// Byte offsets of virtual K-tile kt (64 elements) inside a row of A resp. W.  kt is wave-uniform: scalar arithmetic; inv = ceil(2^16 / (k0 / 64)).
+// Byte offsets of virtual K-tile kt (64 elements) inside a row of A resp. W: block p = kt / nk0, K-tile k0 = kt % nk0 of that block
+// (nk0 = split_k0 / 64), kept by the K loop as a running pair — exact for every K0, and wave-uniform: scalar arithmetic.
 template <int SPLIT>
-__device__ __forceinline__ void ktile_offsets(int kt, int split_k0, int inv, int& off_a, int& off_w) {
+__device__ __forceinline__ void ktile_offsets(int kt, int p, int k0, int split_k0, int& off_a, int& off_w) {
   if (SPLIT == 0) {
     off_a = off_w = kt * 128;
     return;
   }
-  const int nk0 = split_k0 >> 6;
-  const int p = (kt * inv) >> 16, k0 = kt - p * nk0;  // exact for kt < 6 * nk0 <= 6 * 1024
   off_a = (plane_of<SPLIT>(p, false) * split_k0 + k0 * 64) * 2;
   off_w = (plane_of<SPLIT>(p, true) * split_k0 + k0 * 64) * 2;
 }
@@ -224,10 +223,11 @@ __global__ __launch_bounds__(256, 3) void gemm_nt_bf16_glds_kernel(const Bf16Gem
     for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4b){0.f, 0.f, 0.f, 0.f};
 
   const int nk = g.K >> 6;
-  const int split_inv = SPLIT ? (65536 + (g.split_k0 >> 6) - 1) / (g.split_k0 >> 6) : 0;
-  for (int kt = 0; kt < nk; ++kt) {
+  const int split_nk0 = SPLIT ? g.split_k0 >> 6 : 0;
+  for (int kt = 0, sp = 0, sk0 = 0; kt < nk; ++kt) {
     int koff, koff_w;
-    ktile_offsets<SPLIT>(kt, g.split_k0, split_inv, koff, koff_w);
+    ktile_offsets<SPLIT>(kt, sp, sk0, g.split_k0, koff, koff_w);
+    if (SPLIT && ++sk0 == split_nk0) sk0 = 0, ++sp;
     if (SPLIT == 2 && kt == 2 * (g.split_k0 >> 6)) {  // the two cross blocks are in: scale them by 2^-11 before the hi.hi block
 #pragma unroll
       for (int i = 0; i < MI; ++i)
@@ -736,9 +736,12 @@ static int pick_tile256(int64_t M, int N, int K, int has_residual, int out_bf16)
 #endif
 }
 
-// The form launch_linear_bf16_glds gives an aligned launch (gdr_linear_bf16_tile_form): must mirror the branches below.
-int linear_bf16_tile_form(int64_t M, int N, int K, int has_residual, int out_bf16) {
+// The form launch_linear_bf16_glds gives an aligned launch (gdr_linear_bf16_tile_form): must mirror the branches below.  K is the real
+// contraction length; split (as in the launcher) makes it the virtual one.  The plane-row output (out_bf16 >= 2) exists in the 256-row
+// tiles only: callers that want it test this for >= 192 and otherwise store fp32 and split in a launch of its own.
+int linear_bf16_tile_form(int64_t M, int N, int K, int has_residual, int out_bf16, int split) {
   if (K % 64 != 0) return 0;
+  if (split) K *= split == 2 ? 3 : split;
   if (K % 128 == 0 && N % 4 == 0) {
     const int sel = pick_tile256(M, N, K, has_residual, out_bf16);
     if (sel) return sel == 1 ? 256 : 192;
@@ -800,6 +803,7 @@ int launch_linear_bf16_glds(const void* A, int64_t lda, const void* W, int64_t l
       return 0;
     }
   }
+  if (out_bf16 >= 2) return 1;  // plane rows out: the 128 / 64-row epilogues write one plain bf16 image, never the planes
   // fewer than 2 tiles of 128 rows per CU: 64-row tiles (same k order per output element: bit-identical results)
   // (tools/exp_bf16_linear.py, profiles/r04_bf16_tile_height_sweep.txt: 1 920 rows qkv 21.6 -> 18.2 us, o 18.9 -> 15.2, wi 22.8 ->
   // 19.9, wo 57.4 -> 43.6; 4 096 rows o 23.2 -> 17.5, wo 58.5 -> 46.2; from ~2 tiles per CU on the 128-row form is as fast or faster)

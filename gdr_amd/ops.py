@@ -455,7 +455,9 @@ class T5EncoderHandle:
 
     def __init__(self, cfg, sd, device, prefix="encoder.", dtype=torch.float32, split=False):
         """split=True (r06, exploratory; dtype float32): every linear weight is stored as three bf16 planes (split_bf16x3) and forward()
-        runs gdr_t5_encoder_forward_ragged_split — fp32 operands carried through bf16 MFMAs with fp32-level error, not fp32 bits."""
+        runs gdr_t5_encoder_forward_ragged_split — fp32 operands carried through bf16 MFMAs with fp32-level error, not fp32 bits.
+        split=2 (fp16 x 2 planes): an operand |x| in [2^-14, 65504] is carried to 2^-21 relative, a smaller one to an absolute 3e-11,
+        and one >= 65520 overflows fp16 and makes its output row non-finite (never a finite wrong value)."""
         if dtype not in (torch.float32, torch.bfloat16):
             raise ValueError("T5EncoderHandle: dtype must be float32 or bfloat16")
         if split and dtype != torch.float32:
@@ -561,7 +563,9 @@ class BertEncoderHandle:
 
     def __init__(self, bcfg, sd, device, prefix="ctx_encoder.bert_model.", dtype=torch.float32, split=False):
         """split=True (r06, exploratory; dtype float32): the linear weights are stored as fp16 x 2 plane rows (split_f16x2) and forward()
-        runs gdr_bert_encoder_forward_ragged_split — fp32-level embeddings through the fp16 MFMA path."""
+        runs gdr_bert_encoder_forward_ragged_split — fp32-level embeddings through the fp16 MFMA path.  An operand |x| in
+        [2^-14, 65504] is carried to 2^-21 relative, a smaller one to an absolute 3e-11, and one >= 65520 overflows fp16 and makes its
+        output row non-finite (never a finite wrong value)."""
         if dtype not in (torch.float32, torch.bfloat16):
             raise ValueError("BertEncoderHandle: dtype must be float32 or bfloat16")
         if split and dtype != torch.float32:

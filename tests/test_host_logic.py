@@ -184,6 +184,21 @@ def test_reference_model_variants_the_kernels_do_not_implement_fail_loudly(flag,
     assert unsupported_variant(gmain.parsers_parser(["--mode", "eval"])) is None
 
 
+@pytest.mark.parametrize("size,widths", [
+    ("small", dict(d_model=512, num_heads=8, d_ff=2048, num_layers=6, num_decoder_layers=3, d_kv=64)),
+    ("base", dict(d_model=768, num_heads=12, d_ff=3072, num_layers=12, num_decoder_layers=6, d_kv=64)),
+    ("large", dict(d_model=1024, num_heads=16, d_ff=4096, num_layers=24, num_decoder_layers=12, d_kv=64))])
+def test_model_info_sizes_reach_the_config(size, widths):
+    """`--model_info` through parsers_parser + GDRConfig.from_args gives the t5-small / base / large widths that
+    tests/test_gpu_model_sizes.py builds its models from (main.py _SIZES): those tests cannot drift off the CLI's shapes."""
+    from gdr_amd.main import parsers_parser
+    from gdr_amd.config import GDRConfig
+    cfg = GDRConfig.from_args(parsers_parser(["--model_info", size]))
+    for k, v in widths.items():
+        assert getattr(cfg, k) == v, (size, k, getattr(cfg, k), v)
+    assert cfg.d_model % 64 == 0 and cfg.num_heads * cfg.d_kv == cfg.d_model
+
+
 def test_synthetic_corpus_shard_is_bit_identical_to_the_slice_of_the_whole():
     """r06: an N-GPU rank materialises only its own rows of the synthetic corpus (synth.make_corpus(rows=), bench.py / main.py): the
     shard must be the slice of the whole corpus BIT FOR BIT — every chunk geometry (shard inside one chunk, spanning chunks, starting /
