@@ -95,6 +95,28 @@ class ClusterIndex:
         members = np.concatenate([np.asarray(id_mapping[n], dtype=np.int32) for n in names]) if names else np.zeros(0, np.int32)
         return ClusterIndex(names, offsets, members)
 
+    def with_csr(self, offsets, members):
+        """The same clusters (names unchanged) over another member CSR, e.g. the merged one of an insertion."""
+        if len(offsets) != len(self.names) + 1:
+            raise ValueError(f"{len(offsets) - 1} segments for {len(self.names)} clusters")
+        return ClusterIndex(self.names, offsets, members)
+
+    def sorted_members(self):
+        """members with every cluster's segment in ascending doc-id order (the order in which the reference's TreeBuilder
+        attaches documents, main_models.py:137-151: the rows of title_content.tsv)."""
+        seg = np.repeat(np.arange(len(self.names), dtype=np.int64), np.diff(self.offsets))
+        return np.ascontiguousarray(self.members[np.lexsort((self.members, seg))], dtype=np.int32)
+
+    def unassigned(self, lo, hi):
+        """Doc ids in [lo, hi) that are members of no cluster, ascending."""
+        return np.setdiff1d(np.arange(lo, hi, dtype=np.int64), self.members.astype(np.int64)).astype(np.int32)
+
+    def save_npz(self, path):
+        """Writes the clusters.npz layout of tools/convert_artifacts.py (cluster_names, cluster_offsets, cluster_members) to
+        exactly `path`."""
+        with open(path, "wb") as f:
+            np.savez(f, cluster_names=np.array(self.names), cluster_offsets=self.offsets, cluster_members=self.members)
+
     def __getitem__(self, name):
         c = self.lookup.get(name)
         if c is None:

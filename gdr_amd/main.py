@@ -85,6 +85,10 @@ _FLAGS = [
     ("prefix_table", int, 1),                # 1: build the device prefix table over the corpus' docid trie at load
     ("constrain_tree", int, 0),              # 1: apply the trie constraint of generation_utils_previous.py:714-729 (the
                                              #    shipped generate() ignores decode_tree even with --tree 1)
+    ("expand_index", int, 0),                # 1: insert the rows >= --docnum of --doc_embed_npy that belong to no cluster into the
+                                             #    cluster with the nearest centroid before the eval loop (the reference's
+                                             #    tree_embedding_insert, main_models.py:877-889; opt-in: --expand is ignored)
+    ("save_index", str, ""),                 # write the index the run uses (clusters.npz layout) — the analogue of indexmap_insert.pkl
 ]
 _SIZES = {"base": (12, 6, 3072, 768, 12, 64), "large": (24, 12, 4096, 1024, 16, 64), "small": (6, 3, 2048, 512, 8, 64)}
 
@@ -197,6 +201,19 @@ def inference(args):
     dev = torch.device(args.device)
     two_stage_wanted = bool(args.is_train_encoder)
     data = _load_inputs(args, cfg, shard=(world, rank) if two_stage_wanted else None)
+    if args.expand_index:
+        if world > 1:
+            raise SystemExit("--expand_index 1 runs on one GPU (sharded insertion is not supported)")
+        if not args.data_npz or data["doc_embed"] is None:
+            raise SystemExit("--expand_index 1 needs --data_npz and --doc_embed_npy")
+        from .modeling import expand_cluster_index
+        data["doc_embed_dev"] = torch.from_numpy(np.ascontiguousarray(data["doc_embed"], dtype=np.float32)).to(dev)
+        rows = data["index"].unassigned(args.docnum, data["doc_embed"].shape[0])
+        data["index"], _cl = expand_cluster_index(data["doc_embed_dev"], data["index"], rows)
+        print(f"[gdr_amd] --expand_index: {rows.size} documents inserted into {len(data['index'].names)} clusters")
+    if args.save_index and rank == 0:                    # one writer when several ranks run the same command
+        os.makedirs(os.path.dirname(args.save_index) or ".", exist_ok=True)
+        data["index"].save_npz(args.save_index)
     if args.constrain_tree and args.kary != args.output_vocab_size:
         raise SystemExit(f"--constrain_tree 1 needs --kary ({args.kary}) == --output_vocab_size "
                          f"({args.output_vocab_size}): the trie is indexed by the head's digit columns")
@@ -221,8 +238,10 @@ def inference(args):
         sharded_index = ShardedIndex(shard, lo_r)
         retr = GDRRetriever(model, None, data["index"], args, sharded=sharded_index)
     elif two_stage:
-        retr = GDRRetriever(model, torch.from_numpy(np.ascontiguousarray(data["doc_embed"], dtype=np.float32)).to(dev),
-                            data["index"], args)
+        D_dev = data.get("doc_embed_dev")
+        if D_dev is None:
+            D_dev = torch.from_numpy(np.ascontiguousarray(data["doc_embed"], dtype=np.float32)).to(dev)
+        retr = GDRRetriever(model, D_dev, data["index"], args)
     n = data["source_ids"].shape[0] if args.n_test < 0 else min(args.n_test, data["source_ids"].shape[0])
     texts = data.get("texts") or ["q%d" % i for i in range(data["source_ids"].shape[0])]
     inf_result_cache, outputs = [], []
@@ -351,6 +370,8 @@ def main(argv=None):
         why = unsupported_variant(args)                      # before any rank is started: a variant the kernels lack
         if why:
             raise SystemExit("gdr_amd: " + why)
+        if args.expand_index and args.n_gpu > 1:
+            raise SystemExit("gdr_amd: --expand_index 1 runs on one GPU: it cannot be combined with --n_gpu > 1")
         if args.n_gpu > 1 and not launch.under_launcher():
             # one command, N GPUs: this process (which has not touched a GPU) starts the N ranks as children and relays
             # their output; rank 0 writes the TSVs and prints the metrics

@@ -303,6 +303,28 @@ class LazyRows:
         return repr(self._get())
 
 
+def expand_cluster_index(doc_embed, index, rows, centroids=None):
+    """Inserts the documents `rows` (ascending doc ids, rows of doc_embed fp32[N,d] on the GPU that belong to no cluster) into
+    the cluster with the nearest centroid — the reference's tree_embedding_insert (main_models.py:268-295, run at :877-889
+    over every row >= --docnum).  centroids: an ops.FrozenCentroids (default: computed from `index` as it stands).
+    Returns (the expanded codec.ClusterIndex, names unchanged; the cluster index of every inserted row, int32 numpy)."""
+    import numpy as np
+    if doc_embed.dtype != torch.float32:
+        raise _ffi.GdrError("corpus expansion needs the fp32 corpus (the bf16 precision mode is not supported)")
+    fc = centroids if centroids is not None else ops.FrozenCentroids(doc_embed, index)
+    dev = doc_embed.device
+    rows = np.asarray(rows, dtype=np.int64)
+    if rows.size and (np.any(np.diff(rows) <= 0) or rows[0] < 0 or rows[-1] >= doc_embed.shape[0]):
+        raise _ffi.GdrError("expand_cluster_index: rows must be ascending doc ids of the corpus")
+    ids = torch.from_numpy(rows.astype(np.int32)).to(dev)
+    tgt = fc.assign(doc_embed.index_select(0, ids.long()) if rows.size else doc_embed[:0], compact=True)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)   # noqa: E731
+    offs, mem, _mx = ops.cluster_insert(up(index.offsets), up(index.members), ids, tgt, fc.cmap)
+    csr = torch.cat([offs, mem]).cpu().numpy()                                      # one read-back of the merged CSR
+    C_ = len(index.names)
+    return index.with_csr(csr[:C_ + 1], csr[C_ + 1:]), fc.cmap[tgt.long()].cpu().numpy()
+
+
 class GDRRetriever:
     """Two-stage GDR retrieval = `T5FineTuner.validation_step_i` (main_models.py:1337-1642):
     beam-decode cluster ids -> id_mapping lookup -> tanh(q·d) over the candidates -> + alpha*softmax(beam scores)
@@ -331,6 +353,99 @@ class GDRRetriever:
         # device_candidates: decoded rows -> clusters -> candidate CSR on the GPU (gdr_cluster_candidates); False keeps the
         # host form (decode_token strings + ClusterIndex.candidates) — same lists, one D2H / H2D round trip more per step
         self.device_candidates = bool(device_candidates)
+
+    @torch.no_grad()
+    def add_documents(self, embeds=None, tokens=None):
+        """Adds n documents to the corpus without retraining the generative model (the GDR paper's scalability claim; the
+        reference's tree_embedding_insert, main_models.py:268-295): each joins the cluster whose centroid has the largest fp32
+        dot product with it (ties: the lower cluster index).  embeds: fp32 [n, d]; or tokens=(input_ids int64[n, Lp],
+        attention_mask) — pre-tokenised passages that the retriever's doc tower (doc_tower=) embeds.  With the re-encode path
+        configured (doc_tokens=), tokens= is required and appended to doc_tokens.
+        The rows are appended to doc_embed (backing buffer grown geometrically) and become doc ids N .. N+n-1.  The centroids
+        are frozen on the first call from the index as built and never updated, as in the reference: adding in k calls gives
+        the index that one call gives.  The merged CSR replaces both the device index and the host ClusterIndex (one read-back),
+        so the device_candidates=False / --kary 0 paths see the same lists.  Returns (doc ids int64[n], cluster indices int32[n]
+        into cluster_index.names).
+        Must not run while validation_steps() has steps in flight: their candidate lists and doc_embed would change under them.
+        Raises GdrError for a sharded retriever, a bf16 doc_embed (the C5 precision mode) and a dimension mismatch."""
+        import numpy as np
+        if self.sharded is not None:
+            raise _ffi.GdrError("add_documents: a sharded retriever cannot take documents (sharded insertion is not supported)")
+        if self.doc_embed is None or self.doc_embed.dtype != torch.float32:
+            raise _ffi.GdrError("add_documents needs the fp32 doc_embed (the bf16 precision mode is not supported)")
+        dev = self.doc_embed.device
+        N, d = self.doc_embed.shape
+        if self.doc_tokens is not None and tokens is None:
+            raise _ffi.GdrError("add_documents: the re-encode path is configured (doc_tokens=): pass tokens= as well")
+        if tokens is not None:
+            tok, msk = (t.to(dev) for t in tokens)
+            if tok.dim() != 2 or msk.shape != tok.shape:
+                raise _ffi.GdrError(f"add_documents: tokens {tuple(tok.shape)} / mask {tuple(msk.shape)} must be [n, Lp]")
+        if embeds is None:
+            if tokens is None:
+                raise _ffi.GdrError("add_documents: pass embeds= or tokens=")
+            if getattr(self.encoder, "bert", None) is None:
+                raise _ffi.GdrError("add_documents(tokens=...) needs the doc tower (doc_tower=)")
+            embeds = self.encoder(passage={"input_ids": tok, "attention_mask": msk})
+        embeds = torch.as_tensor(embeds)
+        if embeds.dtype != torch.float32 or embeds.dim() != 2 or embeds.shape[1] != d:
+            raise _ffi.GdrError(f"add_documents: embeds must be fp32 [n, {d}], got {embeds.dtype} {tuple(embeds.shape)}")
+        n = embeds.shape[0]
+        if tokens is not None and tok.shape[0] != n:
+            raise _ffi.GdrError(f"add_documents: {n} embeddings but {tok.shape[0]} token rows")
+        if N + n >= 2 ** 31:
+            raise _ffi.GdrError("add_documents: doc ids must fit int32")
+        embeds = embeds.to(dev).contiguous()
+        if getattr(self, "_centroids", None) is None:
+            self._centroids = ops.FrozenCentroids(self.doc_embed, self.index)          # frozen: the index as built
+        fc = self._centroids
+        tgt = fc.assign(embeds, compact=True)
+        # doc_embed: append into a geometrically grown buffer (a 64-doc add does not copy the corpus)
+        buf = getattr(self, "_doc_buf", None)
+        if buf is None or buf.shape[0] < N + n or buf.data_ptr() != self.doc_embed.data_ptr():
+            buf = torch.empty((max(N + n, N + N // 2 + 64), d), dtype=torch.float32, device=dev)
+            buf[:N].copy_(self.doc_embed)
+            self._doc_buf = buf
+        buf[N:N + n].copy_(embeds)
+        self.doc_embed = buf[:N + n]
+        if self.doc_tokens is not None:
+            self._append_tokens(tok, msk)
+        ids = torch.arange(N, N + n, dtype=torch.int32, device=dev)
+        dci = self._device_index()
+        C_ = len(self.index.names)
+        if dci is not None:
+            dci.insert(ids, tgt, target_map=fc.cmap, streams=getattr(self, "_streams", ()))
+            offs, mem = dci.offsets, dci.members[:dci.n_members]
+        else:
+            up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)   # noqa: E731
+            offs, mem, _mx = ops.cluster_insert(up(self.index.offsets), up(self.index.members), ids, tgt, fc.cmap)
+        csr = torch.cat([offs, mem]).cpu().numpy()                                  # one read-back of the merged CSR
+        self.index = self.index.with_csr(csr[:C_ + 1], csr[C_ + 1:])
+        return np.arange(N, N + n, dtype=np.int64), fc.cmap[tgt.long()].cpu().numpy()
+
+    def _append_tokens(self, tok, msk):
+        """doc_tokens += (tok, msk) in backing buffers grown like doc_embed's: rows geometrically, and once wider when a passage is
+        longer than every earlier one (PAD 0, mask 0) — an add after the first copies only its own rows."""
+        old_t, old_m = self.doc_tokens
+        N, L0 = old_t.shape
+        n, L1 = tok.shape
+        bt, bm = getattr(self, "_tok_buf", (None, None))
+        if (bt is None or bt.shape[0] < N + n or bt.shape[1] < L1 or bt.data_ptr() != old_t.data_ptr()
+                or bm.data_ptr() != old_m.data_ptr() or bt.shape[1] != L0):
+            grow = bt is None or bt.shape[0] < N + n or bt.data_ptr() != old_t.data_ptr()
+            cap = max(N + n, N + N // 2 + 64) if grow else bt.shape[0]
+            L = max(L0, L1)
+            bt = torch.zeros((cap, L), dtype=old_t.dtype, device=old_t.device)
+            bm = torch.zeros((cap, L), dtype=old_m.dtype, device=old_m.device)
+            bt[:N, :L0].copy_(old_t)
+            bm[:N, :L0].copy_(old_m)
+            self._tok_buf = (bt, bm)
+        W = bt.shape[1]
+        bt[N:N + n, :L1].copy_(tok)
+        bm[N:N + n, :L1].copy_(msk)
+        bt[N:N + n, L1:W].zero_()
+        bm[N:N + n, L1:W].zero_()
+        self.doc_tokens = (bt[:N + n], bm[:N + n])
 
     def _reencode(self, cand_ids, chunk=1024):
         """Embeds the candidate docs with the doc tower (main_models.py:1445-1455).  cand_ids int32 [total] on device."""
@@ -400,7 +515,8 @@ class GDRRetriever:
             a = self.args
             self._dci = None
             if getattr(a, "kary", 30) and self.device_candidates:
-                self._dci = ops.DeviceClusterIndex(self.index, self.model.device, getattr(a, "output_vocab_size", a.kary),
+                dev = self.model.device if self.model is not None else self.doc_embed.device
+                self._dci = ops.DeviceClusterIndex(self.index, dev, getattr(a, "output_vocab_size", a.kary),
                                                    position=getattr(a, "position", 1), kary=a.kary)
         return self._dci
 

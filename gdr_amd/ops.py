@@ -199,7 +199,8 @@ def sim_topk(Q, D, k, idx_offset=0, workspace=None, return_status=False, exact_o
         if bad.numel():
             for lo in range(0, bad.numel(), 64):                     # bounded workspace: 64 queries * N * 8 B
                 rows = bad[lo:lo + 64]
-                v2, i2, _ = _sim_topk_raw(Q[rows].contiguous(), D, k, idx_offset, None, _ffi.SIM_EXHAUSTIVE)
+                v2, i2, _ = _sim_topk_raw(Q[rows].contiguous(), D, k, idx_offset, None,
+                                          _ffi.SIM_EXHAUSTIVE | (flags & _ffi.SIM_NO_STREAM))   # the core the caller chose
                 vals[rows], idx[rows] = v2, i2
             status = torch.zeros_like(status)
     return (vals, idx, status) if return_status else (vals, idx)
@@ -421,8 +422,28 @@ class DeviceClusterIndex:
         self.offsets, self.members = dev(index.offsets.astype(np.int32)), dev(index.members.astype(np.int32) if index.members.size
                                                                              else np.zeros(1, np.int32))
         self.max_cluster = int(np.diff(index.offsets).max()) if n else 0
-        self.struct = _ffi.GdrClusterIndex(n, key_len, T, self.slots.data_ptr(), self.keys.data_ptr(), self.lens.data_ptr(),
-                                           self.offsets.data_ptr(), self.members.data_ptr())
+        self.n_members = int(index.members.size)
+        self.key_len, self.table_size = key_len, T
+        self._make_struct()
+
+    def _make_struct(self):
+        self.struct = _ffi.GdrClusterIndex(self.offsets.numel() - 1, self.key_len, self.table_size, self.slots.data_ptr(),
+                                           self.keys.data_ptr(), self.lens.data_ptr(), self.offsets.data_ptr(),
+                                           self.members.data_ptr())
+
+    def insert(self, new_ids, new_cluster, target_map=None, streams=()):
+        """Merges documents into the member CSR on the device (cluster_insert): every cluster keeps its members in order,
+        followed by the ids it received in ascending order.  new_ids int32[n] ascending, new_cluster int32[n] cluster indices
+        (or indices into target_map int32, the compact -> cluster map of FrozenCentroids).  Swaps in the merged CSR, updates
+        max_cluster (one read-back) and rebuilds `struct` (it holds raw pointers).  The old arrays are kept alive on every
+        stream in `streams` (record_stream): a step enqueued there before this call may still read them."""
+        offs, mem, mx = cluster_insert(self.offsets, self.members[:self.n_members], new_ids, new_cluster, target_map)
+        for t in (self.offsets, self.members):
+            for st in streams:
+                t.record_stream(st)
+        self.offsets, self.members = offs, (mem if mem.numel() else torch.zeros(1, dtype=torch.int32, device=mem.device))
+        self.n_members, self.max_cluster = int(mem.numel()), mx
+        self._make_struct()
 
     def candidates(self, out_ids, B, R):
         """out_ids int64[B*R, max_length] (device, untrimmed) -> (cluster_of int32[B*R], cand_offsets int32[B,R+1],
@@ -437,6 +458,126 @@ class DeviceClusterIndex:
         check(lib().gdr_cluster_candidates(C.byref(self.struct), ptr(out_ids), B, R, out_ids.shape[1], ptr(cl), ptr(offs),
                                            ptr(ids), stride, stream_ptr()), "gdr_cluster_candidates")
         return cl, offs, ids, stride
+
+
+def cluster_centroids(D, index):
+    """(centroids fp32[C,d], counts int32[C]) of the clusters of `index` (codec.ClusterIndex) over D fp32[N,d] —
+    gdr_cluster_centroids.  Each centroid is the mean of its members' rows, bit-identical to the reference's
+    tree_embedding_calculate (main_models.py:154-179): the members are put in ascending order here, once, on the host (index
+    preparation), and the device adds them in that order.  An empty cluster has count 0 and a zero row."""
+    import numpy as np
+    _need_cuda(D)
+    D = _f32c(D)
+    N, d = D.shape
+    C_ = len(index.names)
+    if C_ == 0:
+        raise _ffi.GdrError("cluster_centroids: the index has no clusters")
+    mem = index.sorted_members()
+    if mem.size and (int(mem.min()) < 0 or int(mem.max()) >= N):
+        raise _ffi.GdrError(f"cluster_centroids: member ids outside [0, {N})")
+    offs = torch.from_numpy(np.ascontiguousarray(index.offsets, dtype=np.int32)).to(D.device)
+    mem_d = torch.from_numpy(mem if mem.size else np.zeros(1, np.int32)).to(D.device)
+    cent = torch.empty((C_, d), dtype=torch.float32, device=D.device)
+    counts = torch.empty((C_,), dtype=torch.int32, device=D.device)
+    check(lib().gdr_cluster_centroids(ptr(D), N, d, ptr(offs), ptr(mem_d), int(mem.size), C_, ptr(cent), ptr(counts),
+                                      stream_ptr()), "gdr_cluster_centroids")
+    return cent, counts
+
+
+ASSIGN_CHUNK = 4096                # rows per gdr_sim_topk call of the assignment: ~0.5 GB of workspace at 16k centroids
+
+
+def _nearest_compact(X, compact, chunk=ASSIGN_CHUNK, workspace=None):
+    """(compact index int32[n], its fp32 score [n]).  Always the tiled GEMM core (SIM_NO_STREAM): at B <= 32 gdr_sim_topk would
+    otherwise take the stream kernel, which sums K in another order — a row's score, and so its cluster near a tie, would
+    depend on how many rows were in the call.  The GEMM core has no split-K: every row's bits are the same for any B, so
+    adding documents in k calls assigns them as one call does."""
+    n = X.shape[0]
+    out = torch.empty((n,), dtype=torch.int32, device=X.device)
+    val = torch.empty((n,), dtype=torch.float32, device=X.device)
+    ws = workspace or Workspace(X.device)
+    for lo in range(0, n, chunk):
+        v, i = sim_topk(X[lo:lo + chunk], compact, 1, workspace=ws, flags=_ffi.SIM_NO_STREAM)   # exact_on_overflow stays on
+        out[lo:lo + chunk], val[lo:lo + chunk] = i[:, 0], v[:, 0]
+    return out, val
+
+
+def nearest_cluster(X, centroids, counts, chunk=ASSIGN_CHUNK):
+    """int32[n]: for every row of X fp32[n,d] the cluster whose centroid has the largest fp32 dot product with it, among the
+    clusters with counts > 0 (the reference's argmax over the set of clusters that hold documents, main_models.py:268-295).
+    Ties: the higher score, then the lower cluster index — gdr_sim_topk with k = 1 over the compacted non-empty centroids,
+    in chunks of `chunk` rows (bounded workspace)."""
+    fc = FrozenCentroids.from_tensors(centroids, counts)
+    return fc.assign(X, chunk=chunk)
+
+
+class FrozenCentroids:
+    """The centroids of an index, computed once (the reference never updates them: insertions do not move a centroid), with
+    the compacted matrix of the non-empty ones and its compact -> cluster map."""
+
+    def __init__(self, D=None, index=None):
+        if D is not None:
+            self._set(*cluster_centroids(D, index))
+
+    @staticmethod
+    def from_tensors(centroids, counts):
+        fc = FrozenCentroids()
+        fc._set(_f32c(centroids), counts)
+        return fc
+
+    def _set(self, centroids, counts):
+        _need_cuda(centroids, counts)
+        self.centroids, self.counts = centroids, counts.to(torch.int32)
+        nz = torch.nonzero(self.counts > 0).flatten()
+        if nz.numel() == 0:
+            raise _ffi.GdrError("no cluster has a member: there is no centroid to assign to")
+        self.cmap = nz.to(torch.int32)
+        self.compact = centroids.index_select(0, nz).contiguous()
+
+    def assign(self, X, compact=False, chunk=ASSIGN_CHUNK, return_scores=False):
+        """Nearest non-empty cluster of every row of X: cluster indices int32[n], or (compact=True) indices into `cmap`;
+        with return_scores=True also the winning fp32 scores [n].  A row's result does not depend on the other rows of the call."""
+        _need_cuda(X)
+        X = _f32c(X)
+        if X.dim() != 2 or X.shape[1] != self.compact.shape[1]:
+            raise _ffi.GdrError(f"assign: rows {tuple(X.shape)} vs centroids of dim {self.compact.shape[1]}")
+        if X.shape[0] == 0:
+            ci, val = (torch.empty((0,), dtype=torch.int32, device=X.device),
+                       torch.empty((0,), dtype=torch.float32, device=X.device))
+        else:
+            ci, val = _nearest_compact(X, self.compact, chunk=chunk)
+        ci = ci if compact else self.cmap[ci.long()]
+        return (ci, val) if return_scores else ci
+
+
+def cluster_insert(offsets, members, new_ids, new_cluster, target_map=None, workspace=None):
+    """gdr_cluster_insert: the member CSR (offsets int32[C+1], members int32[n_old]) + new_ids int32[n] (ascending) with
+    their clusters new_cluster int32[n] (or indices into target_map) -> (offsets int32[C+1], members int32[n_old+n], largest
+    cluster).  Every cluster keeps its members in order, followed by the ids it received in ascending order.  One read-back:
+    the largest cluster size."""
+    _need_cuda(offsets, members, new_ids, new_cluster, target_map)
+    C_ = offsets.numel() - 1
+    n_old, n = members.numel(), new_ids.numel()
+    if new_cluster.numel() != n:
+        raise _ffi.GdrError(f"cluster_insert: {n} ids but {new_cluster.numel()} targets")
+    for t in (offsets, members, new_ids, new_cluster) + ((target_map,) if target_map is not None else ()):
+        if t.dtype != torch.int32:
+            raise _ffi.GdrError(f"cluster_insert: expected int32, got {t.dtype}")
+    offsets, members, new_ids, new_cluster = (t.contiguous() for t in (offsets, members, new_ids, new_cluster))
+    dev = offsets.device
+    out_off = torch.empty((C_ + 1,), dtype=torch.int32, device=dev)
+    out_mem = torch.empty((max(n_old + n, 1),), dtype=torch.int32, device=dev)
+    out_max = torch.empty((1,), dtype=torch.int32, device=dev)
+    need = lib().gdr_cluster_insert_workspace_bytes(C_)
+    ws = (workspace or Workspace(dev)).get(need)
+    n_map = target_map.numel() if target_map is not None else 0
+    check(lib().gdr_cluster_insert(ptr(offsets), ptr(members) if n_old else None, C_, n_old, ptr(new_ids) if n else None,
+                                   ptr(new_cluster) if n else None, n, ptr(target_map) if n_map else None, n_map, ptr(out_off),
+                                   ptr(out_mem), ptr(out_max), ptr(ws), ws.numel(), stream_ptr()), "gdr_cluster_insert")
+    mx = int(out_max.item())
+    if mx < 0:
+        raise _ffi.GdrError("cluster_insert: a target is out of range or the old offsets are inconsistent")
+    return out_off, out_mem[:n_old + n], mx
 
 
 def relative_bucket_table(bidirectional, num_buckets, max_distance, qlen, klen):

@@ -326,6 +326,35 @@ uint64_t gdr_cluster_key_hash(const int32_t* tokens_host, int len);   /* host ro
 int gdr_cluster_candidates(const GdrClusterIndex* ci, const int64_t* out_ids, int B, int R, int max_length,
                            int32_t* cluster_of, int32_t* cand_offsets, int32_t* cand_ids, int cand_stride, void* stream);
 
+/* Corpus expansion — replaces tree_embedding_calculate + tree_embedding_insert (main_models.py:154-179, 268-295, called at
+ * :877-889): new documents join the cluster with the nearest centroid without retraining the generative model.
+ *
+ * Centroids: centroids fp32[n_clusters, d], counts int32[n_clusters] from D fp32[N, d] and the member CSR
+ *   (offsets int32[n_clusters+1] into members int32[n_members]).  With every cluster's members ASCENDING (the order in which
+ *   the reference's TreeBuilder attaches them) the centroid is bit-identical to the reference's
+ *   sum([emb[i] for i in members]) / len(members): sequential fp32 adds starting from 0, then one correctly rounded fp32
+ *   division.  An empty cluster gets count 0 and a zero row.  Member ids outside [0, N) contribute nothing (validate them on
+ *   the host).  d % 4 == 0, d <= 4096; D and out_centroids 16-byte aligned; N, n_members < 2^31.
+ *
+ * Assignment is gdr_sim_topk with k = 1 over the compacted matrix of the non-empty centroids (ties: higher score, then the
+ *   lower cluster index).
+ *
+ * Insert: the member CSR (offsets, members: n_old ids) plus n_new documents new_ids int32[n_new] (ASCENDING) with their
+ *   targets new_target int32[n_new] -> out_offsets int32[n_clusters+1], out_members int32[n_old+n_new]: every cluster keeps
+ *   its members in their order, followed by the documents it received in ascending id order.  target_map int32[n_map]
+ *   (may be NULL, n_map = 0) maps a target to its cluster index (the compact index of the assignment -> cluster).
+ *   out_max (device int32[1]) = the largest cluster after the insertion, or -1 if a target was out of range or the old
+ *   offsets were inconsistent (offsets[0] != 0, offsets[n_clusters] != n_old, a negative segment): the output is then
+ *   invalid.  Deterministic (the result does not depend on atomic order); O(n_old + n_new) while no cluster receives more than
+ *   4,096 documents, plus one ordered pass over the n_new inputs for each cluster that does; n_old + n_new < 2^31.
+ *   workspace: gdr_cluster_insert_workspace_bytes(n_clusters) bytes. */
+int gdr_cluster_centroids(const float* D, int64_t N, int d, const int32_t* offsets, const int32_t* members, int64_t n_members,
+                          int n_clusters, float* out_centroids, int32_t* out_counts, void* stream);
+size_t gdr_cluster_insert_workspace_bytes(int n_clusters);
+int gdr_cluster_insert(const int32_t* offsets, const int32_t* members, int n_clusters, int64_t n_old, const int32_t* new_ids,
+                       const int32_t* new_target, int n_new, const int32_t* target_map, int n_map, int32_t* out_offsets,
+                       int32_t* out_members, int32_t* out_max, void* workspace, size_t workspace_bytes, void* stream);
+
 /* The exchange row of the SHARDED in-cluster rerank (gdr_amd/dist.py ShardedIndex.rerank_own; the arithmetic being sharded
  * is main_models.py:1434-1462,1574-1637, the per-GPU layout follows Data_process/NQ_dataset/bert/bert_NQ.sh:5-12): per query
  * ONE int32 row  wire[b] = { q fp32[d] | beam_scores fp32[R] | cand_offsets int32[R+1] | cand_ids int32[cand_stride] },
