@@ -134,6 +134,14 @@ SIGNATURES = {
     "gdr_cluster_centroids": (_i, [_vp, _i64, _i, _vp, _vp, _i64, _i, _vp, _vp, _vp]),
     "gdr_cluster_insert_workspace_bytes": (_sz, [_i]),
     "gdr_cluster_insert": (_i, [_vp, _vp, _i, _i64, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "gdr_kmeans_assign_tile": (_i, []),
+    "gdr_kmeans_partition_tile": (_i, []),
+    "gdr_kmeans_assign_workspace_bytes": (_sz, [_i, _i]),
+    "gdr_kmeans_assign": (_i, [_vp, _i64, _i, _vp, _i64, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "gdr_kmeans_partition_workspace_bytes": (_sz, [_i, _i]),
+    "gdr_kmeans_partition": (_i, [_vp, _vp, _i64, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "gdr_kmeans_centroids_workspace_bytes": (_sz, [_i64, _i]),
+    "gdr_kmeans_centroids": (_i, [_vp, _i64, _i, _vp, _vp, _i64, _i, _vp, _vp, _vp, _sz, _vp]),
     "gdr_t5_relative_bucket_table": (_i, [_i, _i, _i, _i, _i, C.POINTER(C.c_int32)]),
     "gdr_bert_encoder_workspace_bytes": (_sz, [C.POINTER(GdrBertWeights), _i, _i]),
     "gdr_bert_encoder_forward": (_i, [C.POINTER(GdrBertWeights), _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),

@@ -580,6 +580,141 @@ def cluster_insert(offsets, members, new_ids, new_cluster, target_map=None, work
     return out_off, out_mem[:n_old + n], mx
 
 
+KMEANS_MAX_K = 64
+KMEANS_MAX_D = 4096
+
+
+def cluster_centroids_csr(D, offsets, members, n_members=None):
+    """gdr_cluster_centroids over a member CSR that already lives on the device (offsets int32[C+1], members int32[>= n_members],
+    every segment ascending) -> (centroids fp32[C,d], counts int32[C]).  The k-means update step; no validation read-back."""
+    _need_cuda(D, offsets, members)
+    D = _f32c(D)
+    if offsets.dtype != torch.int32 or members.dtype != torch.int32:
+        raise _ffi.GdrError("cluster_centroids_csr: expected int32 offsets / members")
+    N, d = D.shape
+    C_ = offsets.numel() - 1
+    n = members.numel() if n_members is None else int(n_members)
+    cent = torch.empty((C_, d), dtype=torch.float32, device=D.device)
+    counts = torch.empty((C_,), dtype=torch.int32, device=D.device)
+    check(lib().gdr_cluster_centroids(ptr(D), N, d, ptr(offsets.contiguous()), ptr(members.contiguous()), n, C_, ptr(cent),
+                                      ptr(counts), stream_ptr()), "gdr_cluster_centroids")
+    return cent, counts
+
+
+def kmeans_worklist(node_offsets, tile):
+    """work int32[n_work, 2] = (node, first row position) of every `tile`-row tile of every node of the CSR node_offsets
+    int32[S+1] (device), nodes and tiles ascending — the list gdr_kmeans_assign / gdr_kmeans_partition walk.  Built in torch;
+    one read-back (the number of tiles)."""
+    off = node_offsets.to(torch.int64)
+    sizes = off[1:] - off[:-1]
+    nt = (sizes + (tile - 1)) // tile
+    total = int(nt.sum().item())
+    S = sizes.numel()
+    node = torch.repeat_interleave(torch.arange(S, device=off.device), nt, output_size=total)
+    first = torch.cumsum(nt, 0) - nt
+    q = torch.arange(total, device=off.device) - first[node]
+    return torch.stack([node, off[node] + q * tile], 1).to(torch.int32).contiguous()
+
+
+def _kmeans_check(what, D, rows, node_offsets, k):
+    _need_cuda(D, rows, node_offsets)
+    if D is not None:
+        if D.dtype != torch.float32:
+            raise _ffi.GdrError(f"{what}: the corpus must be float32, got {D.dtype} (a bf16 corpus is not supported)")
+        if D.dim() != 2 or D.shape[1] % 4 or not 4 <= D.shape[1] <= KMEANS_MAX_D:
+            raise _ffi.GdrError(f"{what}: d={D.shape[-1]} (needs d % 4 == 0, 4 <= d <= {KMEANS_MAX_D})")
+        if D.shape[0] >= 1 << 31:
+            raise _ffi.GdrError(f"{what}: N={D.shape[0]} does not fit int32 doc ids")
+    if not 2 <= int(k) <= KMEANS_MAX_K:
+        raise _ffi.GdrError(f"{what}: k={k} (needs 2 <= k <= {KMEANS_MAX_K})")
+    for t in (rows, node_offsets):
+        if t.dtype != torch.int32:
+            raise _ffi.GdrError(f"{what}: expected int32, got {t.dtype}")
+    if rows.numel() == 0 or node_offsets.numel() < 2:
+        raise _ffi.GdrError(f"{what}: empty level")
+
+
+def kmeans_assign(D, rows, node_offsets, centroids, k, work=None, prev_labels=None, workspace=None):
+    """gdr_kmeans_assign: one Lloyd E-step over the nodes of a level.  D fp32[N,d]; rows int32[n] (doc ids, ascending inside a
+    node), node_offsets int32[S+1]; centroids fp32[S*k, d]; work = kmeans_worklist(node_offsets, gdr_kmeans_assign_tile()) (built
+    here when absent) -> (labels int32[n], score fp32[n] = x.c - |c|^2/2 of the label, changed int32[S] = labels per node that
+    differ from prev_labels, status int32[1]: non-zero when a work item was malformed).  No read-back."""
+    _kmeans_check("kmeans_assign", D, rows, node_offsets, k)
+    _need_cuda(centroids, work, prev_labels)
+    D, centroids = _f32c(D), _f32c(centroids)
+    rows, node_offsets = rows.contiguous(), node_offsets.contiguous()
+    n, S = rows.numel(), node_offsets.numel() - 1
+    if tuple(centroids.shape) != (S * k, D.shape[1]):
+        raise _ffi.GdrError(f"kmeans_assign: centroids {tuple(centroids.shape)}, expected {(S * k, D.shape[1])}")
+    if prev_labels is not None and (prev_labels.dtype != torch.int32 or prev_labels.numel() != n):
+        raise _ffi.GdrError("kmeans_assign: prev_labels must be int32[n]")
+    if work is None:
+        work = kmeans_worklist(node_offsets, lib().gdr_kmeans_assign_tile())
+    if work.dtype != torch.int32 or work.dim() != 2 or work.shape[1] != 2 or work.shape[0] == 0:
+        raise _ffi.GdrError("kmeans_assign: work must be int32[n_work, 2]")
+    dev = D.device
+    labels = torch.empty((n,), dtype=torch.int32, device=dev)
+    score = torch.empty((n,), dtype=torch.float32, device=dev)
+    changed = torch.empty((S,), dtype=torch.int32, device=dev)
+    status = torch.empty((1,), dtype=torch.int32, device=dev)
+    need = lib().gdr_kmeans_assign_workspace_bytes(S, k)
+    ws = (workspace or Workspace(dev)).get(need)
+    check(lib().gdr_kmeans_assign(ptr(D), D.shape[0], D.shape[1], ptr(rows), n, ptr(node_offsets), S, ptr(centroids), k,
+                                  ptr(work.contiguous()), work.shape[0], ptr(prev_labels.contiguous()) if prev_labels is not None else None,
+                                  ptr(labels), ptr(score), ptr(changed), ptr(status), ptr(ws), ws.numel(), stream_ptr()),
+          "gdr_kmeans_assign")
+    return labels, score, changed, status
+
+
+def kmeans_partition(rows, labels, node_offsets, k, work=None, workspace=None):
+    """gdr_kmeans_partition: stable segmented counting sort of every node's rows by label -> (rows' int32[n], child_offsets
+    int32[S*k+1], status int32[1]: bit 1 a label outside [0, k), bit 2 a malformed work item).  Child j of node s is
+    rows'[child_offsets[s*k+j] : child_offsets[s*k+j+1]], ascending.  No read-back (beyond building the work list when absent)."""
+    _kmeans_check("kmeans_partition", None, rows, node_offsets, k)
+    _need_cuda(labels, work)
+    n, S = rows.numel(), node_offsets.numel() - 1
+    if labels.dtype != torch.int32 or labels.numel() != n:
+        raise _ffi.GdrError("kmeans_partition: labels must be int32[n]")
+    rows, labels, node_offsets = rows.contiguous(), labels.contiguous(), node_offsets.contiguous()
+    if work is None:
+        work = kmeans_worklist(node_offsets, lib().gdr_kmeans_partition_tile())
+    if work.dtype != torch.int32 or work.dim() != 2 or work.shape[1] != 2 or work.shape[0] == 0:
+        raise _ffi.GdrError("kmeans_partition: work must be int32[n_work, 2]")
+    dev = rows.device
+    out_rows = torch.empty((n,), dtype=torch.int32, device=dev)
+    child = torch.empty((S * k + 1,), dtype=torch.int32, device=dev)
+    status = torch.empty((1,), dtype=torch.int32, device=dev)
+    need = lib().gdr_kmeans_partition_workspace_bytes(work.shape[0], k)
+    ws = (workspace or Workspace(dev)).get(need)
+    check(lib().gdr_kmeans_partition(ptr(rows), ptr(labels), n, ptr(node_offsets), S, k, ptr(work.contiguous()), work.shape[0],
+                                     ptr(out_rows), ptr(child), ptr(status), ptr(ws), ws.numel(), stream_ptr()),
+          "gdr_kmeans_partition")
+    return out_rows, child, status
+
+
+def kmeans_centroids(D, child_offsets, rows, workspace=None):
+    """gdr_kmeans_centroids: the k-means update step over the child CSR of kmeans_partition -> (centroids fp32[C,d], counts
+    int32[C]); member means as a fixed-shape two-stage sum (chunks of 256 members in order, then the chunk sums in order, one
+    division): deterministic, and gdr_cluster_centroids' bits for a child of <= 256 members.  An empty child: count 0, zero row."""
+    _need_cuda(D, child_offsets, rows)
+    if D.dtype != torch.float32:
+        raise _ffi.GdrError(f"kmeans_centroids: the corpus must be float32, got {D.dtype} (a bf16 corpus is not supported)")
+    D = _f32c(D)
+    if child_offsets.dtype != torch.int32 or rows.dtype != torch.int32:
+        raise _ffi.GdrError("kmeans_centroids: expected int32 child_offsets / rows")
+    N, d = D.shape
+    C_, n = child_offsets.numel() - 1, rows.numel()
+    if C_ < 1 or n < 1:
+        raise _ffi.GdrError("kmeans_centroids: empty level")
+    cent = torch.empty((C_, d), dtype=torch.float32, device=D.device)
+    counts = torch.empty((C_,), dtype=torch.int32, device=D.device)
+    need = lib().gdr_kmeans_centroids_workspace_bytes(n, d)
+    ws = (workspace or Workspace(D.device)).get(need)
+    check(lib().gdr_kmeans_centroids(ptr(D), N, d, ptr(child_offsets.contiguous()), ptr(rows.contiguous()), n, C_, ptr(cent),
+                                     ptr(counts), ptr(ws), ws.numel(), stream_ptr()), "gdr_kmeans_centroids")
+    return cent, counts
+
+
 def relative_bucket_table(bidirectional, num_buckets, max_distance, qlen, klen):
     """Host table int32[qlen,klen] from the same routine the attention kernels use (no GPU needed)."""
     buf = (C.c_int32 * (qlen * klen))()

@@ -380,6 +380,50 @@ int gdr_device_fault_pending(void);
 void gdr_device_fault_clear(void);
 void gdr_device_fault_inject_for_tests(void);
 
+/* Hierarchical k-means docid construction: one Lloyd round over every open node of a tree level — the device form
+ * of the reference's Data_process/NQ_dataset/kmeans/kmeans.py.  The state of a level is a CSR over nodes: rows int32[n_rows] (doc
+ * ids, ASCENDING inside every node), node_offsets int32[n_nodes+1] (node_offsets[0] = 0, node_offsets[n_nodes] = n_rows), and a
+ * centroid table fp32[n_nodes*k, d].  Both calls take a work list work int32[n_work, 2] = (node, first row position): every
+ * tile of gdr_kmeans_assign_tile() / gdr_kmeans_partition_tile() rows of every node to process, nodes ascending and the tiles of
+ * a node ascending and contiguous.  An item that names no node, or a position outside its node (for the partition: one that is
+ * not a multiple of the tile past the node's start) touches nothing and sets bit 2 of out_status (device int32[1]).
+ *
+ * Assign: for every listed row position p: out_labels[p] = argmax_j (x . c_j - 0.5 |c_j|^2) over the k centroids of p's node,
+ *   ties to the lower j, out_score[p] = that maximum (fp32; |x - c|^2 = |x|^2 - 2 score), out_changed[node] = how many labels of
+ *   the node differ from prev_labels (NULL: all of them).  Exact fp32 products (v_mfma_f32_32x32x2_f32); a row's dot product is ONE
+ *   fma chain in a fixed column order, so its bits do not depend on the tile, the other nodes of the call or the launch.  A row id
+ *   outside [0, N) reads as a zero row.  d % 4 == 0, d <= 4096, 2 <= k <= 64, N and n_rows < 2^31; D, centroids 16-byte aligned.
+ *   workspace: gdr_kmeans_assign_workspace_bytes(n_nodes, k).
+ *
+ * Partition: stable segmented counting sort of each listed node's rows by label -> out_rows int32[n_rows] and
+ *   out_child_offsets int32[n_nodes*k+1]: child j of node s holds out_rows[out_child_offsets[s*k+j] : out_child_offsets[s*k+j+1]],
+ *   ascending again (stable + ascending input) — the member order gdr_cluster_centroids wants (the update step is that call over
+ *   this CSR) and the next level's state.  No ticket atomics: label counts per tile by ballot, one exclusive scan, ordered
+ *   placement.  Every node must be non-empty and listed (a node that is not keeps -1 in its child offsets).  A label outside
+ *   [0, k) sets bit 1 of out_status and its row is dropped.  workspace: gdr_kmeans_partition_workspace_bytes(n_work, k).
+ *
+ * Update: gdr_kmeans_centroids — member means over the child CSR as a FIXED-SHAPE two-stage sum: a child's members are cut into
+ *   chunks of 256 counted from the child's own start, each chunk is summed member after member in fp32, the chunk sums are added
+ *   in chunk order, then one correctly rounded division.  Deterministic, a function of the child's member list alone, and for a
+ *   child of <= 256 members bit-identical to gdr_cluster_centroids (which stays the update of record for the expansion: one
+ *   sequential chain per cluster; here a 10,000-member child would make every Lloyd round wait for that chain).  An empty child
+ *   gets count 0 and a zero row.  workspace: gdr_kmeans_centroids_workspace_bytes(n_rows, d), 16-byte aligned. */
+int gdr_kmeans_assign_tile(void);
+int gdr_kmeans_partition_tile(void);
+size_t gdr_kmeans_assign_workspace_bytes(int n_nodes, int k);
+int gdr_kmeans_assign(const float* D, int64_t N, int d, const int32_t* rows, int64_t n_rows, const int32_t* node_offsets,
+                      int n_nodes, const float* centroids, int k, const int32_t* work, int n_work, const int32_t* prev_labels,
+                      int32_t* out_labels, float* out_score, int32_t* out_changed, int32_t* out_status, void* workspace,
+                      size_t workspace_bytes, void* stream);
+size_t gdr_kmeans_partition_workspace_bytes(int n_work, int k);
+int gdr_kmeans_partition(const int32_t* rows, const int32_t* labels, int64_t n_rows, const int32_t* node_offsets, int n_nodes,
+                         int k, const int32_t* work, int n_work, int32_t* out_rows, int32_t* out_child_offsets,
+                         int32_t* out_status, void* workspace, size_t workspace_bytes, void* stream);
+size_t gdr_kmeans_centroids_workspace_bytes(int64_t n_rows, int d);
+int gdr_kmeans_centroids(const float* D, int64_t N, int d, const int32_t* child_offsets, const int32_t* rows, int64_t n_rows,
+                         int n_children, float* out_centroids, int32_t* out_counts, void* workspace, size_t workspace_bytes,
+                         void* stream);
+
 /* T5 relative-position buckets (transformers/modeling_t5.py:242-288) for relative_position =
  * key_pos - query_pos, written to a HOST int32[qlen*klen] table; the attention kernels use the same
  * host routine, so tests pin it bit-exact against the reference. */
