@@ -75,7 +75,7 @@ extern "C" int gdr_bert_encoder_forward(const GdrBertWeights* w, const int64_t* 
   using namespace gdr;
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   GDR_CHECK_ARG(w && ids && workspace && (out_hidden || out_pooled), "bert: null pointer");
-  GDR_CHECK_ARG(B > 0 && L > 0 && L <= 128 && L <= w->max_pos, "bert: B=%d L=%d (L must be <= min(128, max_pos))", B, L);
+  GDR_CHECK_ARG(B > 0 && L > 0 && L <= 512 && L <= w->max_pos, "bert: B=%d L=%d (L must be <= min(512, max_pos = %d))", B, L, w->max_pos);
   const int d = w->d_model, H = w->num_heads;
   GDR_CHECK_ARG(d % 4 == 0 && H > 0 && d % H == 0 && (d / H) % 4 == 0 && w->d_ff % 4 == 0, "bert: unsupported dims");
   GDR_CHECK_ARG(w->word_emb && w->pos_emb && w->type_emb && w->emb_ln_w && w->emb_ln_b && w->layers, "bert: null weight");
@@ -214,7 +214,7 @@ static int bert_ragged_impl(const GdrBertWeights* w, const int64_t* ids, const i
   const bool bf16 = prec == 1, f16s = prec == 2;
   if (B == 0) return GDR_OK;
   GDR_CHECK_ARG(w && ids && mask && workspace && (out_hidden || out_pooled), "bert_ragged: null pointer");
-  GDR_CHECK_ARG(B > 0 && L > 0 && L <= 128 && L <= w->max_pos, "bert_ragged: B=%d L=%d (L must be <= min(128, max_pos))", B, L);
+  GDR_CHECK_ARG(B > 0 && L > 0 && L <= 512 && L <= w->max_pos, "bert_ragged: B=%d L=%d (L must be <= min(512, max_pos = %d))", B, L, w->max_pos);
   const int d = w->d_model, H = w->num_heads;
   GDR_CHECK_ARG(d % 4 == 0 && H > 0 && d % H == 0 && (d / H) % 4 == 0 && w->d_ff % 4 == 0, "bert_ragged: unsupported dims");
   GDR_CHECK_ARG(w->word_emb && w->pos_emb && w->type_emb && w->emb_ln_w && w->emb_ln_b && w->layers, "bert_ragged: null weight");

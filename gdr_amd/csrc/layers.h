@@ -52,6 +52,9 @@ struct AttnArgs {
   const int32_t* live;
 };
 int launch_attention(const AttnArgs& a, hipStream_t stream);
+// attention_long.hip: d_kv = 64 full self-attention over 128 < Lk <= 512 keys (key-block walk, online softmax), fp32 or bf16 q / k / v,
+// padded or packed layout.  Reached through launch_attention only, which checks the form and opens the ProfScope.
+int launch_attention_long(const AttnArgs& a, hipStream_t stream);
 
 int launch_embed(const float* table, const int64_t* ids, int64_t rows, int d, int vocab, float* out,
                  hipStream_t stream);

@@ -542,7 +542,9 @@ int launch_layernorm_dev(const float* x, const float* w, const float* b, float* 
 // ------------------------------------------------------------------------------------------ attention
 // One workgroup per (batch, head): K and V rows of that head are staged once in LDS (row stride dk+4 floats:
 // ≡ 4 mod 64 banks for dk = 64, so the per-lane ds_read_b128 of "my key's row" is conflict-free); each of
-// the 4 waves then walks query rows: lane j scores keys j and j+64, softmax by wave shuffles, PV with lane = d.
+// the 4 waves then walks query rows: lane j scores keys j, j+64, ... (KT strips of 64 keys: 2 serves Lk <= 128, every call of the T5
+// paths; 8 serves the doc tower's other head widths up to 512 keys), softmax by wave shuffles, PV with lane = d.
+template <int KT>
 __global__ __launch_bounds__(256) void attention_kernel(const AttnArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   if (a.live && *a.live == 0) return;  // uniform: every query of the generate call is done
@@ -616,12 +618,12 @@ __global__ __launch_bounds__(256) void attention_kernel(const AttnArgs a) {
       for (int d = lane; d < dk; d += 64) qs[d] = qr[d] * a.scale;
     }
     __builtin_amdgcn_wave_barrier();
-    float sc[2];
+    float sc[KT];
     float mx = -INFINITY;
     if (active) {
       const int i_abs = a.q_pos0 + (a.q_same_pos ? 0 : i);
 #pragma unroll
-      for (int t = 0; t < 2; ++t) {
+      for (int t = 0; t < KT; ++t) {
         const int j = lane + 64 * t;
         float s = -INFINITY;
         if (j < Lk) {
@@ -662,7 +664,7 @@ __global__ __launch_bounds__(256) void attention_kernel(const AttnArgs a) {
       mx = wave_max(mx);
       float sum = 0.f;
 #pragma unroll
-      for (int t = 0; t < 2; ++t) {
+      for (int t = 0; t < KT; ++t) {
         const int j = lane + 64 * t;
         if (j < Lk) {
           const float p = expf(sc[t] - mx);
@@ -1603,7 +1605,12 @@ __global__ __launch_bounds__(256) void attention_decode_heads4_kernel(const Attn
 // (kv_rows -> K / V), the shared rows already meet in L2, and the staging adds barriers and a third dependent phase.
 int launch_attention(const AttnArgs& a, hipStream_t stream) {
   GDR_CHECK_ARG(a.dk % 4 == 0 && a.dk >= 4 && a.dk <= 256, "attention: dk=%d unsupported", a.dk);
-  GDR_CHECK_ARG(a.Lk >= 1 && a.Lk <= 128, "attention: Lk=%d must be in [1,128]", a.Lk);
+  GDR_CHECK_ARG(a.Lk >= 1 && a.Lk <= 512, "attention: Lk=%d must be in [1,512]", a.Lk);
+  // more than 128 keys: full self-attention without position bias (the doc tower) only — every other form keeps its whole K / V strip
+  // in LDS or in registers sized for 128 keys
+  GDR_CHECK_ARG(a.Lk <= 128 || (a.Lq == a.Lk && a.q_pos0 == 0 && !a.kv_rows && a.kv_group == 1 && !a.q_same_pos && !a.rel_bias &&
+                                !a.causal && !a.q_part && !a.b_count_dev),
+                "attention: Lk=%d > 128 serves full self-attention without position bias or causal mask only (Lq=%d)", a.Lk, a.Lq);
   GDR_CHECK_ARG(a.ldq % 4 == 0 && a.ldk % 4 == 0 && a.ldv % 4 == 0, "attention: row strides must be multiples of 4");
   GDR_CHECK_ARG(!a.rel_bias || (a.num_buckets >= 2 && a.num_buckets <= 256), "attention: bad num_buckets");
   GDR_CHECK_ARG(a.kv_group >= 1, "attention: kv_group must be >= 1");
@@ -1659,6 +1666,7 @@ int launch_attention(const AttnArgs& a, hipStream_t stream) {
                 "attention: the packed (ragged) form and bf16 q/k/v serve full self-attention with d_kv = 64 only");
   GDR_CHECK_ARG(!a.qkv_bf16 || (a.ldq % 8 == 0 && a.ldk % 8 == 0 && a.ldv % 8 == 0), "attention: bf16 q/k/v need row strides %% 8 == 0");
   if (a.Lq == a.Lk && a.q_pos0 == 0 && !a.kv_rows && a.kv_group == 1 && !a.q_same_pos && a.dk == 64 && a.ldo % 4 == 0) {
+    if (a.Lk > 128) return launch_attention_long(a, stream);  // K / V no longer fit in LDS: key-block walk (attention_long.hip)
     if (a.qkv_bf16 && a.scale == 1.0f) {  // bf16 operands as they stand: the bf16-MFMA form
       switch ((a.Lk + 15) / 16) {
         case 1: return launch_attention_mfma_bf16<1>(a, stream);
@@ -1705,9 +1713,16 @@ int launch_attention(const AttnArgs& a, hipStream_t stream) {
   }
   const int qrows = rows_per <= 32 ? ((rows_per + 3) & ~3) : 4;  // as the kernel lays its query strip out
   const size_t lds = sizeof(float) * ((size_t)2 * a.Lk * dks + (size_t)qrows * a.dk + 4 * Lkp + 256);
-  GDR_CHECK_ARG(lds <= 160 * 1024, "attention: Lk=%d dk=%d needs %zu B of LDS", a.Lk, a.dk, lds);
-  if (int rc__ = ensure_dyn_lds(reinterpret_cast<const void*>(attention_kernel), 160 * 1024, "attention")) return rc__;
-  hipLaunchKernelGGL(attention_kernel, dim3((unsigned)(a.B * a.H), (unsigned)chunks), dim3(256), lds, stream, a);
+  GDR_CHECK_ARG(lds <= 160 * 1024,
+                "attention: d_kv=%d at L=%d needs %zu B of LDS for K and V (limit 163840; only d_kv = 64 has a key-block form for L > 128)",
+                a.dk, a.Lk, lds);
+  if (a.Lk > 128) {
+    if (int rc__ = ensure_dyn_lds(reinterpret_cast<const void*>(attention_kernel<8>), 160 * 1024, "attention")) return rc__;
+    hipLaunchKernelGGL(attention_kernel<8>, dim3((unsigned)(a.B * a.H), (unsigned)chunks), dim3(256), lds, stream, a);
+  } else {
+    if (int rc__ = ensure_dyn_lds(reinterpret_cast<const void*>(attention_kernel<2>), 160 * 1024, "attention")) return rc__;
+    hipLaunchKernelGGL(attention_kernel<2>, dim3((unsigned)(a.B * a.H), (unsigned)chunks), dim3(256), lds, stream, a);
+  }
   GDR_CHECK_LAUNCH("attention_kernel");
   return GDR_OK;
 }

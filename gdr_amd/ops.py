@@ -831,8 +831,14 @@ class T5EncoderHandle:
         return (out if want_hidden else None), pooled
 
 
+BERT_MAX_LEN = 512             # the doc tower's entry points take L <= min(BERT_MAX_LEN, max_pos) (csrc/bert.hip)
+ATTN_LONG_QUERY_BLOCK = 128    # above 128 tokens (csrc/attention_long.hip): query rows per workgroup ...
+ATTN_LONG_KEY_BLOCK = 64       # ... and keys per staged K / V block; stated here for the tests that walk the block edges
+
+
 class BertEncoderHandle:
     """Device-resident doc-tower weights (DPRContextEncoder / BertModel keys) + pointer table.
+    Passages of up to BERT_MAX_LEN = 512 tokens (the reference's corpus embedder runs at MAX_LEN=512), bounded by max_pos.
     dtype=torch.bfloat16 selects the bf16 precision mode (config C5's corpus is bf16): the linear weights are rounded to bf16 on the
     device, the attention's 1/sqrt(dh) is folded into the q rows of wqkv / bqkv (exact: a power of two at dh = 64), and forward()
     runs gdr_bert_encoder_forward_ragged_bf16 — the packed form is the only bf16 form."""

@@ -433,7 +433,11 @@ int gdr_t5_relative_bucket_table(int bidirectional, int num_buckets, int max_dis
 /* ------------------------------------------------------------------------------------------------
  * Doc tower — replaces `EncoderModel.forward(passage=...)` (main_models.py:79-89) = DPRContextEncoder
  * (transformers/modeling_dpr.py:146-191) over BertModel (transformers/modeling_bert.py); pooled = hidden[:,0].
- * Producer of the corpus matrix D (Data_process/NQ_dataset/bert/bert.py:69-71).  L <= 128 (encoder_max_len).
+ * Producer of the corpus matrix D (Data_process/NQ_dataset/bert/bert.py:69-71).  L <= min(512, max_pos) in all four entry points
+ * (the reference's corpus embedder runs at MAX_LEN=512, bert_NQ.sh:5).  Up to 128 tokens the one-pass attention kernels serve every
+ * head width; above, head width 64 takes the key-block kernels (online softmax; same results in the padded and the ragged form, bit
+ * for bit) and another head width the generic kernel while K and V of one head fit in 160 KB of LDS (d_kv = 16 at L = 512 does,
+ * d_kv = 128 does not: GDR_EINVAL naming d_kv and L).
  * ---------------------------------------------------------------------------------------------- */
 typedef struct {
   const float *wqkv, *bqkv;      /* [3d,d],[3d]  attention.self.{query,key,value} row-concat   */

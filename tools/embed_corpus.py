@@ -2,7 +2,7 @@
 """Offline corpus embedding with the doc tower — the role of Data_process/NQ_dataset/bert/bert.py:28-83 and its
 launcher bert_NQ.sh:5-12 (one process per GPU, `--partition_num/--idx`, no collectives).
 
-Input: pre-tokenised passages `tokens.npz` (input_ids int64[N,L<=128], attention_mask) — the tokenizer is out of scope
+Input: pre-tokenised passages `tokens.npz` (input_ids int64[N,L<=512], attention_mask) — the tokenizer is out of scope
 (SURVEY §2.3).  Output: `<out>/doc_embed.<idx>.npy` fp32[rows,768]; concatenate the shards in idx order to obtain the
 corpus matrix D that gdr_sim_topk / gdr_rerank_topk read.
 
