@@ -126,6 +126,7 @@ int launch_linear_f32_small(const float* A, int64_t lda, const float* W, int64_t
                             const NormEpilogue* ne = nullptr,  // with ne: returns 2 if the fused form does not apply
                             SlabRef* slabs = nullptr,          // with slabs (no epilogue allowed): the reduction is left to the caller
                             const int32_t* live = nullptr);    // StreamK::live
+int linear_f32_small_splits(int64_t M, int N, int K, bool has_ws, size_t ws_bytes);  // K slabs of the launcher above; 0: shape not served
 int launch_linear_bf16_headdot(const void* A, int64_t lda, const void* W, int64_t ldw, int64_t M, const int64_t* m_dev, int N, int K,
                                const float* h, int64_t ldh, const int32_t* rows_map, const float* E, int dot_d, float scale,
                                float* partial, hipStream_t stream);

@@ -791,6 +791,17 @@ static bool streamk_wanted(int64_t tiles, int nk) {
   const int64_t rem = tiles % 512;
   return rem != 0 && (512 - rem) * nk > (int64_t)thr * 512;
 }
+// K slabs of the 128x128 split-K form (tiles < 192: the grid cannot fill the chip): about 384 workgroups per launch, at
+// least two K-steps per slab, and no more slabs than the workspace holds.  < 2: not split.  launch_linear_f32_ws and
+// gdr_linear_f32_form both ask here.
+static int linear_f32_splitk_slabs(int64_t tiles, int nk, size_t ws_bytes) {
+  constexpr int target = 384;  // desired number of workgroups per split launch
+  const size_t tile_bytes = (size_t)BM * BN * sizeof(float);
+  int S = (int)((target + tiles - 1) / tiles);
+  if (S > nk / 2) S = nk / 2;
+  if ((size_t)S * tiles * tile_bytes > ws_bytes) S = (int)(ws_bytes / (tiles * tile_bytes));
+  return S;
+}
 template <bool UNITS>  // UNITS: the work items are split-K (tile, chunk) units (StreamKArgs.S > 1), else whole tiles
 __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_nt_f32_streamk_kernel(const GemmArgs g, const int total_tiles_host,
                                                                               const StreamKArgs sk) {
@@ -1324,10 +1335,7 @@ int launch_linear_f32_ws(const float* A, int64_t lda, const float* W, int64_t ld
   if (splitk_ws && K % BK == 0 && tiles < 0x7fffffff / 64) {
     if (tiles < 192 && nk >= 4) {
       // (a) the grid cannot fill the chip (decode: M = batch*beams rows): split every tile along K
-      constexpr int target = 384;  // desired number of workgroups per split launch
-      int S = (int)((target + tiles - 1) / tiles);
-      if (S > nk / 2) S = nk / 2;
-      if ((size_t)S * tiles * tile_bytes > splitk_ws_bytes) S = (int)(splitk_ws_bytes / (tiles * tile_bytes));
+      const int S = linear_f32_splitk_slabs(tiles, nk, splitk_ws_bytes);
       if (S >= 2) {
         // A packed batch (device-side row count, live rows known to the host as a hint) whose LIVE (tile, chunk) units number
         // between one and two per CU: one workgroup per unit leaves every CU waiting for those that got two (a 64-query
@@ -1555,6 +1563,32 @@ extern "C" int gdr_linear_f32_splitk(const float* A, int64_t lda, const float* W
   }
   return launch_linear_f32_ws(A, lda, W, ldw, C, ldc, M, N, K, epilogue, bias, residual, ldr, static_cast<float*>(workspace),
                               workspace_bytes, st);
+}
+
+// Which kernel form gdr_linear_f32 (workspace_bytes == 0) / gdr_linear_f32_splitk give a dense launch: the decisions of
+// gdr_linear_f32_splitk and launch_linear_f32_ws above, in their order, without the launches.  Must mirror the order of
+// those branches; every threshold and slab count (streamk_mid_wanted, streamk_wanted, linear_f32_small_splits,
+// linear_f32_splitk_slabs) is the launchers' own routine.  A workspace is "given" when workspace_bytes > 0: a non-NULL
+// workspace of 0 bytes launches like NULL (no slab fits, no stream-K scratch fits).
+extern "C" int gdr_linear_f32_form(int64_t M, int N, int K, size_t workspace_bytes) {
+  using namespace gdr;
+  if (M <= 0 || N <= 0 || K <= 0 || K % 4 != 0) return 0;
+  const bool has_ws = workspace_bytes > 0;
+  const int64_t tiles = ((M + BM - 1) / BM) * (int64_t)((N + BN - 1) / BN);
+  const int nk = K / BK;
+  const bool kfull = K % BK == 0;
+  const bool sk = has_ws && workspace_bytes >= STREAMK_BYTES && kfull &&
+                  (streamk_mid_wanted(tiles) || (tiles > 512 && streamk_wanted(tiles, nk))) && streamk_fits(M, K, N, K);
+  if (tiles < 192 && M <= 1536 && nk >= 4 && kfull) {
+    const int S = linear_f32_small_splits(M, N, K, has_ws, workspace_bytes);
+    if (S) return S > 1 ? GDR_F32_FORM_SMALL_SPLITK : GDR_F32_FORM_SMALL;
+  }
+  if (has_ws && kfull && tiles < 0x7fffffff / 64 && tiles < 192 && nk >= 4) {
+    if (linear_f32_splitk_slabs(tiles, nk, workspace_bytes) >= 2) return GDR_F32_FORM_SPLITK;  // (the stream-K form over split-K units needs a device-side row count: encoder-internal)
+  }
+  if (sk && streamk_mid_wanted(tiles)) return GDR_F32_FORM_STREAMK_256;
+  if (tiles > 512 && tiles < 0x7fffffff && kfull) return sk && streamk_wanted(tiles, nk) ? GDR_F32_FORM_STREAMK_TAIL : GDR_F32_FORM_PERSISTENT;
+  return GDR_F32_FORM_TILES;
 }
 
 extern "C" int gdr_linear_bf16(const void* A, int64_t lda, const void* W, int64_t ldw, float* C, int64_t ldc, int64_t M,

@@ -295,26 +295,36 @@ __global__ __launch_bounds__(256) void splitk_reduce_norm_row_kernel(const float
   if (on) *reinterpret_cast<float4*>(yr + 4 * tid) = v;
 }
 
-// Returns 1 when the shape is left to the 128x128 core, 0 after launching, < 0 on error.
-int launch_linear_f32_small(const float* A, int64_t lda, const float* W, int64_t ldw, float* C, int64_t ldc, int64_t M, int N,
-                            int K, int has_bias, int has_residual, int act, const float* bias, const float* residual,
-                            int64_t ldr, float* ws, size_t ws_bytes, hipStream_t stream, const int64_t* m_dev,
-                            const NormEpilogue* ne, SlabRef* slabs, const int32_t* live) {
+// The number of K slabs (>= 1) launch_linear_f32_small takes for a shape and a scratch size, 0 if it does not serve the shape.
+// One routine for the launcher and for gdr_linear_f32_form, so that the two cannot drift apart.
+int linear_f32_small_splits(int64_t M, int N, int K, bool has_ws, size_t ws_bytes) {
   constexpr int target = 512;  // workgroups wanted per launch (measured flat between 256 and 512, worse outside)
-  if (K % SBK != 0) return 1;
-  const int64_t tiles_m = (M + SB - 1) / SB;
-  const int tiles_n = (N + SB - 1) / SB;
-  const int64_t tiles = tiles_m * tiles_n;
-  if (tiles > 4096) return 1;
+  if (K % SBK != 0) return 0;
+  const int64_t tiles = ((M + SB - 1) / SB) * (int64_t)((N + SB - 1) / SB);
+  if (tiles > 4096) return 0;
   const int nk = K / SBK;
   int S = (int)((target + tiles / 2) / tiles);  // nearest
   if (S > nk / 4) S = nk / 4;
   if (S < 1) S = 1;
   const size_t slab = (size_t)SB * SB * sizeof(float);
-  if (S > 1 && (!ws || (size_t)S * tiles * slab > ws_bytes)) S = ws ? (int)(ws_bytes / (tiles * slab)) : 1;
+  if (S > 1 && (!has_ws || (size_t)S * tiles * slab > ws_bytes)) S = has_ws ? (int)(ws_bytes / (tiles * slab)) : 1;
   if (S < 1) S = 1;
   const int chunk_steps = (nk + S - 1) / S;
-  S = (nk + chunk_steps - 1) / chunk_steps;
+  return (nk + chunk_steps - 1) / chunk_steps;
+}
+
+// Returns 1 when the shape is left to the 128x128 core, 0 after launching, < 0 on error.
+int launch_linear_f32_small(const float* A, int64_t lda, const float* W, int64_t ldw, float* C, int64_t ldc, int64_t M, int N,
+                            int K, int has_bias, int has_residual, int act, const float* bias, const float* residual,
+                            int64_t ldr, float* ws, size_t ws_bytes, hipStream_t stream, const int64_t* m_dev,
+                            const NormEpilogue* ne, SlabRef* slabs, const int32_t* live) {
+  const int S = linear_f32_small_splits(M, N, K, ws != nullptr, ws_bytes);
+  if (S == 0) return 1;
+  const int64_t tiles_m = (M + SB - 1) / SB;
+  const int tiles_n = (N + SB - 1) / SB;
+  const int64_t tiles = tiles_m * tiles_n;
+  const int nk = K / SBK;
+  const int chunk_steps = (nk + S - 1) / S;  // S slabs of chunk_steps K-steps cover nk exactly (linear_f32_small_splits)
   SmallGemmArgs g{};
   g.A = A, g.W = W, g.bias = bias, g.residual = residual;
   g.lda = lda, g.ldw = ldw, g.ldc = ldc, g.ldr = ldr, g.M = M, g.N = N, g.K = K, g.tiles_n = tiles_n;

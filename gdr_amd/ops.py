@@ -1121,11 +1121,13 @@ class PrefixTable:
     `trie` is a codec.Trie in any order; `.device_trie` is its breadth-first DeviceTrie — pass THAT one as the constraint
     trie when both are used (gdr_t5_generate checks that they share their arrays)."""
 
-    def __init__(self, dec, trie, device, max_levels=None, max_bytes=None):
+    def __init__(self, dec, trie, device, max_levels=None, max_bytes=None, kv=None, W=None, workspace=None):
         """max_levels: cap on the trie depth stored.  max_bytes: HBM budget of the table (default: half of what is free on
         the device now) — the table costs n_table * (adaptor_layers*3*d + (V+1)*d) * 4 bytes (~130 KB per node at t5-base),
         so the deepest levels are dropped until it fits (rows whose prefix is deeper simply take the computed path);
-        a table that does not even hold the root level raises."""
+        a table that does not even hold the root level raises.
+        kv, W (optional): caller-provided table storage, fp32 [adaptor_layers, n_table, 3d] and [n_table, V+1, d]; workspace
+        (optional): an object whose get(nbytes) returns the build's scratch (ops.Workspace).  Defaults: allocated here."""
         import numpy as np
         bfs, level_off, parent, tok = trie.breadth_first()
         cfg = dec.cfg
@@ -1153,12 +1155,15 @@ class PrefixTable:
         node_anc = torch.from_numpy(np.concatenate(anc_blocks).astype(np.int32)).to(device)
         node_tok = torch.from_numpy(tok[:n_table].copy()).to(device)
         d, V1, na = cfg.d_model, cfg.output_vocab_size + 1, cfg.adaptor_layer_num
-        self.kv = torch.empty((na, n_table, 3 * d), dtype=torch.float32, device=device)
-        self.W = torch.empty((n_table, V1, d), dtype=torch.float32, device=device)
+        for name, t, shape in (("kv", kv, (na, n_table, 3 * d)), ("W", W, (n_table, V1, d))):
+            if t is not None and (tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous()):
+                raise _ffi.GdrError(f"PrefixTable: {name} must be a contiguous float32 tensor of shape {shape}")
+        self.kv = kv if kv is not None else torch.empty((na, n_table, 3 * d), dtype=torch.float32, device=device)
+        self.W = W if W is not None else torch.empty((n_table, V1, d), dtype=torch.float32, device=device)
         lo_host = (C.c_int32 * (n_levels + 1))(*[int(x) for x in level_off[:n_levels + 1]])
         max_n = int(max(level_off[s + 1] - level_off[s] for s in range(n_levels)))
         need = lib().gdr_t5_prefix_table_workspace_bytes(C.byref(dec.struct), max_n)
-        ws = torch.empty(need, dtype=torch.uint8, device=device)
+        ws = workspace.get(need) if workspace is not None else torch.empty(need, dtype=torch.uint8, device=device)
         build = lib().gdr_t5_prefix_table_build_bf16 if dec.dtype == torch.bfloat16 else lib().gdr_t5_prefix_table_build
         check(build(C.byref(dec.struct), n_levels, lo_host, ptr(node_tok), ptr(node_anc), ptr(self.kv), ptr(self.W), ptr(ws),
                     ws.numel(), stream_ptr()), "gdr_t5_prefix_table_build")

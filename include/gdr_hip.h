@@ -89,6 +89,17 @@ int gdr_linear_f32_splitk(const float* A, int64_t lda, const float* W, int64_t l
                           int64_t M, int N, int K, int epilogue, const float* bias, const float* residual,
                           int64_t ldr, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Which kernel form a DENSE launch (lda = ldw = K) of gdr_linear_f32 (workspace_bytes = 0) or gdr_linear_f32_splitk gets (host-only, no
+ * GPU work; for tests and profiles, like gdr_linear_bf16_tile_form below); 0 = a shape the linear refuses. */
+#define GDR_F32_FORM_TILES 1         /* one 128x128 tile per workgroup                                          */
+#define GDR_F32_FORM_PERSISTENT 2    /* more than 512 tiles: 512 workgroups walk the tiles                      */
+#define GDR_F32_FORM_SMALL 3         /* 64x64 tiles (few rows), whole K                                         */
+#define GDR_F32_FORM_SMALL_SPLITK 4  /* 64x64 tiles, K slabs in the workspace + fixed-order reduction           */
+#define GDR_F32_FORM_SPLITK 5        /* 128x128 tiles, K slabs in the workspace + fixed-order reduction         */
+#define GDR_F32_FORM_STREAMK_256 6   /* 256 < tiles <= 512: stream-K on 256 workgroups                          */
+#define GDR_F32_FORM_STREAMK_TAIL 7  /* more than 512 tiles: whole-tile rounds, then the stream-K tail          */
+int gdr_linear_f32_form(int64_t M, int N, int K, size_t workspace_bytes);
+
 /* bf16 operands (A [M,K], W [N,K] bf16, round-to-nearest-even of the fp32 tensors), fp32 accumulate, epilogue and output:
  * the linear of the opt-in bf16 precision mode (BASELINE config C5; the reference itself runs precision=32).  K, lda,
  * ldw multiples of 8.  K % 64 == 0 takes the LDS-DMA kernel (gemm_bf16.hip), other K the generic core. */
@@ -215,7 +226,10 @@ int gdr_t5_encoder_forward_bf16(const GdrT5EncoderWeights* w, const int64_t* ids
  * replaces `compute_similarity` (dense.py:53-54, encoder.py:128-129: q @ p.T) followed by
  * `Tensor.topk(k, largest=True, sorted=True)` (as at main_models.py:1625).
  *   Q fp32[B,d], D fp32[N,d] (the resident corpus shard) -> out_val fp32[B,k] descending,
- *   out_idx int32[B,k] = row in D + idx_offset.  Ties: higher score first, then lower id.
+ *   out_idx int32[B,k] = row in D + idx_offset.  Ties: higher score first, then lower id.  Scores are ordered by the IEEE
+ *   total order of their fp32 bit patterns (the kernels' sort keys), which differs from comparison by value in ONE place:
+ *   +0.0 ranks above -0.0 whatever the ids.  The same holds for gdr_sim_topk_bf16 / _prefilter, gdr_topk_merge,
+ *   gdr_topk_merge_packed and gdr_rerank_topk*; a NaN score is not ordered (inputs are finite).
  *   status (device int32[B], may be NULL): status[q] = 1 if query q's candidate list overflowed — only possible on
  *   degenerate data (tens of thousands of docs tied at / above the sampled threshold, e.g. duplicated embeddings);
  *   its result is then the top-k of a subset.  Re-running those queries with GDR_SIM_EXHAUSTIVE (every score kept,
@@ -256,7 +270,8 @@ int gdr_row_norm2_max(const float* D, int64_t N, int d, float* out_dev, void* st
 int gdr_cast_f32_bf16(const float* in, void* out_bf16, int64_t n, void* stream);
 
 /* Merge of per-shard top-k lists after the RCCL all-gather (no reference analogue):
- * vals/idx [G,B,k] (shard-major) -> [B,k]; same tie rule, so every rank computes identical output. */
+ * vals/idx [G,B,k] (shard-major) -> [B,k]; same tie rule (higher score in total order — +0.0 above -0.0 —, then lower id), so
+ * every rank computes identical output. */
 int gdr_topk_merge(const float* vals, const int32_t* idx, int G, int B, int k, float* out_val, int32_t* out_idx,
                    void* stream);
 /* The wire form of a per-shard result, so that the exchange is ONE collective: per query row k+1 entries of
