@@ -33,7 +33,7 @@ class GdrT5EncLayer(C.Structure):
 
 class GdrT5EncoderWeights(C.Structure):
     _fields_ = [("dims", GdrT5Dims), ("embed", C.c_void_p), ("rel_bias", C.c_void_p), ("final_ln", C.c_void_p),
-                ("layers", C.POINTER(GdrT5EncLayer))]
+                ("layers", C.POINTER(GdrT5EncLayer)), ("qkv0_table", C.c_void_p)]   # trailing, optional: NULL = compute
 
 
 class GdrBertLayer(C.Structure):

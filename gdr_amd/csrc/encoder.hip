@@ -20,6 +20,7 @@ namespace gdr {
 constexpr size_t ENC_SPLITK_BYTES = (size_t)112 << 20;  // <= 384 tail tiles x 4 splits x 64 KiB + slack; the same region
                                                         // serves as the stream-K hand-off scratch (a launch uses one or the other)
 static_assert(STREAMK_BYTES <= ENC_SPLITK_BYTES, "stream-K scratch must fit the split-K region");
+constexpr bool ENC_LAST_Q_CLS_DEFAULT = true;  // GDR_ENC_LAST_Q_CLS when unset (DESIGN 4 "Token table": the A/B that decided it)
 
 // the stream-K scratch inside the split-K region of an encoder workspace; flags zeroed once per call
 static int enc_streamk(char* splitk_region, StreamK* sk, hipStream_t stream) {
@@ -353,7 +354,18 @@ static int ragged_impl(const GdrT5EncoderWeights* w, const int64_t* ids, const i
     return launch_linear_f32_dev(A, lda, W, K, C, ldc, M, rows_dev, N, K, epi, nullptr, residual, ldc, live_rows_hint, stream,
                                  &sk);
   };
-  if ((rc = launch_embed_packed(w->embed, ids, row_src, rows_dev, M, d, dm.vocab_size, h, stream))) return rc;
+  // Token table (un-split forms only): block 0's q/k/v depend on the token id alone — no position embedding, a per-row norm,
+  // independent GEMM rows — so the caller may hand them in as a [vocab, 3*inner] table made with the same norm and the same
+  // un-split linear (same k order: the bits of the launch it replaces).  One gather by ids[row_src[row]], with the embedding's
+  // clamp, fills h and qkv; block 0's norm and qkv linear are not launched.  Rows of qkv past the live count stay unwritten
+  // and unread (attention clamps to a sequence's last row).
+  const float* qkv0 = big ? w->qkv0_table : nullptr;
+  GDR_CHECK_ARG(!qkv0 || (((uintptr_t)qkv0) & 15) == 0, "t5_encoder_ragged: qkv0_table must be 16-byte aligned");
+  if (qkv0)
+    rc = launch_embed_packed2(w->embed, qkv0, ids, row_src, rows_dev, M, d, 3 * inner, dm.vocab_size, h, qkv, stream);
+  else
+    rc = launch_embed_packed(w->embed, ids, row_src, rows_dev, M, d, dm.vocab_size, h, stream);
+  if (rc) return rc;
 
   AttnArgs at{};
   at.q = qkv, at.k = qkv + inner, at.v = qkv + 2 * inner, at.out = ctx;
@@ -368,11 +380,29 @@ static int ragged_impl(const GdrT5EncoderWeights* w, const int64_t* ids, const i
   at.seq_off = seq_off, at.seq_len = seq_len;
 
   const bool pooled_only = out_hidden == nullptr && big;
+  static const bool last_q_cls_on = [] {
+    const char* e = getenv("GDR_ENC_LAST_Q_CLS");  // exact A/B knob: 0 = the last block's q for every live row (one qkv launch)
+    return e ? atoi(e) != 0 : ENC_LAST_Q_CLS_DEFAULT;
+  }();
   for (int i = 0; i < dm.num_layers; ++i) {
     const GdrT5EncLayer& ly = w->layers[i];
     GDR_CHECK_ARG(ly.ln_attn && ly.wqkv && ly.wo && ly.ln_ff && ly.wi && ly.wo_ff, "t5_encoder_ragged: layer %d null weight", i);
-    if ((rc = launch_rmsnorm_dev(h, ly.ln_attn, nx, rows_dev, M, d, dm.eps, stream))) return rc;
-    if ((rc = linear(nx, d, ly.wqkv, qkv, 3 * inner, 3 * inner, d, GDR_EPI_NONE, nullptr))) return rc;
+    if (i == 0 && qkv0) {
+      // q, k, v came with the embedding gather
+    } else if (pooled_only && i == dm.num_layers - 1 && last_q_cls_on) {
+      // only the CLS queries' context is read below: k and v over every live row, q for the B CLS rows alone.  The other q rows
+      // keep what an earlier block left (or what the workspace held): each attention lane computes one query, and only ctx rows
+      // seq_off[b] are gathered afterwards.  Un-split kernel for the B rows, as in the tail below: the full launch's bits.
+      if ((rc = launch_rmsnorm_dev(h, ly.ln_attn, nx, rows_dev, M, d, dm.eps, stream))) return rc;
+      if ((rc = linear(nx, d, ly.wqkv + (size_t)inner * d, qkv + inner, 3 * inner, 2 * inner, d, GDR_EPI_NONE, nullptr))) return rc;
+      if ((rc = launch_gather_rows(nx, seq_off, B, d, nx_cls, stream))) return rc;
+      if ((rc = launch_linear_f32(nx_cls, d, ly.wqkv, d, ctx_cls, inner, B, inner, d, GDR_EPI_NONE, nullptr, nullptr, 0, stream)))
+        return rc;
+      if ((rc = launch_scatter_rows_strided(ctx_cls, seq_off, B, inner, qkv, 3 * inner, stream))) return rc;
+    } else {
+      if ((rc = launch_rmsnorm_dev(h, ly.ln_attn, nx, rows_dev, M, d, dm.eps, stream))) return rc;
+      if ((rc = linear(nx, d, ly.wqkv, qkv, 3 * inner, 3 * inner, d, GDR_EPI_NONE, nullptr))) return rc;
+    }
     if ((rc = launch_attention(at, stream))) return rc;
     if (pooled_only && i == dm.num_layers - 1) {
       // only h[:,0] leaves this call: the rest of the block on the B CLS rows (packed row seq_off[b]); unsplit kernels,

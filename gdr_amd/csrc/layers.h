@@ -68,8 +68,14 @@ int launch_pack_plan(const int64_t* mask, int B, int L, int32_t* seq_len, int32_
 // out[r] = table[ids[row_src[r]]] for r < *rows_dev (grid sized for max_rows)
 int launch_embed_packed(const float* table, const int64_t* ids, const int32_t* row_src, const int64_t* rows_dev,
                         int64_t max_rows, int d, int vocab, float* out, hipStream_t stream);
+// the same gather from two tables by one token id: out2[r] = table2[ids[row_src[r]]] (rows of e floats) beside out[r]
+int launch_embed_packed2(const float* table, const float* table2, const int64_t* ids, const int32_t* row_src,
+                         const int64_t* rows_dev, int64_t max_rows, int d, int e, int vocab, float* out, float* out2,
+                         hipStream_t stream);
 // dst[i] = src[idx[i]] (rows of d floats), i < n
 int launch_gather_rows(const float* src, const int32_t* idx, int n, int d, float* dst, hipStream_t stream);
+// dst[idx[i]] = src[i] (dense rows of d floats into rows of dst that are ldd floats apart), i < n
+int launch_scatter_rows_strided(const float* src, const int32_t* idx, int n, int d, float* dst, int64_t ldd, hipStream_t stream);
 // dst[row_src[r]] = src[r] for r < *rows_dev: packed rows back into the [B*L, d] layout (dst pre-zeroed by the caller)
 int launch_scatter_rows(const float* src, const int32_t* row_src, const int64_t* rows_dev, int64_t max_rows, int d,
                         float* dst, hipStream_t stream);

@@ -151,17 +151,47 @@ int launch_embed_packed(const float* table, const int64_t* ids, const int32_t* r
   return GDR_OK;
 }
 
-// SCATTER = false: dst[i] = src[map[i]];  SCATTER = true: dst[map[i]] = src[i]   (rows of d4 float4), i < n or *n_dev
+// Two gathers by the same token id in one launch: out[row] = table[id] (d4 float4) and out2[row] = table2[id] (e4 float4) — the
+// embedding row and block 0's q/k/v row of the token table (encoder.hip).  Same id, same clamp as embed_packed_kernel.
+__global__ __launch_bounds__(256) void embed_packed2_kernel(const float* __restrict__ table, const float* __restrict__ table2,
+                                                            const int64_t* __restrict__ ids, const int32_t* __restrict__ row_src,
+                                                            const int64_t* __restrict__ rows_dev, int d4, int e4, int vocab,
+                                                            float* __restrict__ out, float* __restrict__ out2) {
+  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= *rows_dev) return;
+  int64_t id = ids[row_src[row]];
+  id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
+  const float4* src2 = reinterpret_cast<const float4*>(table2) + id * e4;
+  float4* dst2 = reinterpret_cast<float4*>(out2) + row * e4;
+  for (int c = threadIdx.x & 63; c < e4; c += 64) dst2[c] = src2[c];
+  const float4* src = reinterpret_cast<const float4*>(table) + id * d4;
+  float4* dst = reinterpret_cast<float4*>(out) + row * d4;
+  for (int c = threadIdx.x & 63; c < d4; c += 64) dst[c] = src[c];
+}
+
+int launch_embed_packed2(const float* table, const float* table2, const int64_t* ids, const int32_t* row_src,
+                         const int64_t* rows_dev, int64_t max_rows, int d, int e, int vocab, float* out, float* out2,
+                         hipStream_t stream) {
+  GDR_CHECK_ARG(d % 4 == 0 && e % 4 == 0, "embed: d %% 4 != 0");
+  if (max_rows == 0) return GDR_OK;
+  hipLaunchKernelGGL(embed_packed2_kernel, dim3((unsigned)((max_rows + 3) / 4)), dim3(256), 0, stream, table, table2, ids,
+                     row_src, rows_dev, d / 4, e / 4, vocab, out, out2);
+  GDR_CHECK_LAUNCH("embed_packed2_kernel");
+  return GDR_OK;
+}
+
+// SCATTER = false: dst[i] = src[map[i]];  SCATTER = true: dst[map[i]] = src[i]   (rows of d4 float4), i < n or *n_dev;
+// dst rows are dst_ld4 float4 apart (= d4: dense)
 template <bool SCATTER>
 __global__ __launch_bounds__(256) void move_rows_kernel(const float* __restrict__ src, const int32_t* __restrict__ map,
                                                         int64_t n, const int64_t* __restrict__ n_dev, int d4,
-                                                        float* __restrict__ dst) {
+                                                        float* __restrict__ dst, int64_t dst_ld4) {
   const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (n_dev) n = *n_dev;
   if (i >= n) return;
   const int64_t m = map[i];
   const float4* s = reinterpret_cast<const float4*>(src) + (SCATTER ? i : m) * d4;
-  float4* o = reinterpret_cast<float4*>(dst) + (SCATTER ? m : i) * d4;
+  float4* o = reinterpret_cast<float4*>(dst) + (SCATTER ? m : i) * dst_ld4;
   for (int c = threadIdx.x & 63; c < d4; c += 64) o[c] = s[c];
 }
 
@@ -169,8 +199,18 @@ int launch_gather_rows(const float* src, const int32_t* idx, int n, int d, float
   GDR_CHECK_ARG(d % 4 == 0, "gather_rows: d %% 4 != 0");
   if (n == 0) return GDR_OK;
   hipLaunchKernelGGL(move_rows_kernel<false>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, stream, src, idx, (int64_t)n,
-                     (const int64_t*)nullptr, d / 4, dst);
+                     (const int64_t*)nullptr, d / 4, dst, (int64_t)(d / 4));
   GDR_CHECK_LAUNCH("gather_rows");
+  return GDR_OK;
+}
+
+// dst[idx[i]] = src[i] for i < n: rows of d floats out of a dense src into rows of dst that are ldd floats apart
+int launch_scatter_rows_strided(const float* src, const int32_t* idx, int n, int d, float* dst, int64_t ldd, hipStream_t stream) {
+  GDR_CHECK_ARG(d % 4 == 0 && ldd % 4 == 0 && ldd >= d && ((uintptr_t)dst & 15) == 0, "scatter_rows: bad row width / stride / alignment");
+  if (n == 0) return GDR_OK;
+  hipLaunchKernelGGL(move_rows_kernel<true>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, stream, src, idx, (int64_t)n,
+                     (const int64_t*)nullptr, d / 4, dst, ldd / 4);
+  GDR_CHECK_LAUNCH("scatter_rows_strided");
   return GDR_OK;
 }
 
@@ -179,7 +219,7 @@ int launch_scatter_rows(const float* src, const int32_t* row_src, const int64_t*
   GDR_CHECK_ARG(d % 4 == 0, "scatter_rows: d %% 4 != 0");
   if (max_rows == 0) return GDR_OK;
   hipLaunchKernelGGL(move_rows_kernel<true>, dim3((unsigned)((max_rows + 3) / 4)), dim3(256), 0, stream, src, row_src,
-                     max_rows, rows_dev, d / 4, dst);
+                     max_rows, rows_dev, d / 4, dst, (int64_t)(d / 4));
   GDR_CHECK_LAUNCH("scatter_rows");
   return GDR_OK;
 }

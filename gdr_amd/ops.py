@@ -2,6 +2,7 @@
 purely as device buffers; all arithmetic happens in libgdr_hip.so."""
 import ctypes as C
 import math
+import os
 
 import torch
 
@@ -729,8 +730,12 @@ class T5EncoderHandle:
     dtype=torch.bfloat16 selects the C5 precision mode: the linear weights are rounded to bf16 on the device
     (gdr_cast_f32_bf16) and forward() calls gdr_t5_encoder_forward_bf16; everything else stays fp32."""
 
-    def __init__(self, cfg, sd, device, prefix="encoder.", dtype=torch.float32, split=False):
-        """split=True (r06, exploratory; dtype float32): every linear weight is stored as three bf16 planes (split_bf16x3) and forward()
+    def __init__(self, cfg, sd, device, prefix="encoder.", dtype=torch.float32, split=False, token_table=None):
+        """token_table (float32 without split, d_kv = 64): block 0's q/k/v of every token id, [vocab, 3*inner] fp32 made once here
+        (T5 adds no position embedding, so they depend on the id alone); the ragged forward gathers them instead of running block 0's
+        norm and qkv linear (include/gdr_hip.h).  Default on; token_table=False or GDR_ENC_TOKEN_TABLE=0 leaves it out (the exact
+        A/B switch).  It is a snapshot of the weights: after an in-place update call refresh_token_table().
+        split=True (r06, exploratory; dtype float32): every linear weight is stored as three bf16 planes (split_bf16x3) and forward()
         runs gdr_t5_encoder_forward_ragged_split — fp32 operands carried through bf16 MFMAs with fp32-level error, not fp32 bits.
         split=2 (fp16 x 2 planes): an operand |x| in [2^-14, 65504] is carried to 2^-21 relative, a smaller one to an absolute 3e-11,
         and one >= 65520 overflows fp16 and makes its output row non-finite (never a finite wrong value)."""
@@ -770,7 +775,10 @@ class T5EncoderHandle:
             wqkv = lin(torch.cat([sd[p + "0.SelfAttention.q.weight"], sd[p + "0.SelfAttention.k.weight"],
                                   sd[p + "0.SelfAttention.v.weight"]], dim=0))
             L = self._layers[i]
-            L.ln_attn = dev(sd[p + "0.layer_norm.weight"]).data_ptr()
+            ln_attn = dev(sd[p + "0.layer_norm.weight"])
+            if i == 0:
+                self._ln0, self._wqkv0 = ln_attn, wqkv       # what the token table is made from
+            L.ln_attn = ln_attn.data_ptr()
             L.wqkv = wqkv.data_ptr()
             L.wo = lin(sd[p + "0.SelfAttention.o.weight"]).data_ptr()
             L.ln_ff = dev(sd[p + "1.layer_norm.weight"]).data_ptr()
@@ -783,6 +791,32 @@ class T5EncoderHandle:
         self.struct = _ffi.GdrT5EncoderWeights(self.dims, self.embed.data_ptr(), self.rel_bias.data_ptr(),
                                                self.final_ln.data_ptr(), self._layers)
         self.ws = Workspace(device)
+        if token_table is None:
+            token_table = os.environ.get("GDR_ENC_TOKEN_TABLE", "1") != "0"
+        inner = cfg.num_heads * cfg.d_kv
+        # only the packed un-split form reads the table (csrc/encoder.hip ragged_packs): other precisions and widths never would
+        packs = cfg.d_kv == 64 and cfg.d_model % 32 == 0 and cfg.d_ff % 32 == 0 and inner % 32 == 0
+        self.token_table = None
+        if token_table and dtype == torch.float32 and not split and packs:
+            self.token_table = torch.empty((cfg.vocab_size, 3 * inner), dtype=torch.float32, device=device)
+            self.refresh_token_table()
+            self.struct.qkv0_table = self.token_table.data_ptr()
+
+    @property
+    def token_table_bytes(self):
+        """Device memory the token table adds (0 without one): vocab * 3 * inner * 4."""
+        return 0 if self.token_table is None else self.token_table.numel() * 4
+
+    def refresh_token_table(self, chunk=4096):
+        """Re-derive the token table from the current embedding, block 0's norm weight and wqkv (after an in-place weight update,
+        like PrefilteredCorpus.refresh()).  table[id] = t5_layer_norm(embed[id]) @ wqkv0.T with the operators the encoder itself
+        launches, so a row holds the bits the in-encoder launch gives; built in row chunks (temporary: chunk * d_model floats)."""
+        if self.token_table is None:
+            return self
+        for s in range(0, self.cfg.vocab_size, chunk):
+            e = min(s + chunk, self.cfg.vocab_size)
+            linear(t5_layer_norm(self.embed[s:e], self._ln0, self.cfg.layer_norm_epsilon), self._wqkv0, out=self.token_table[s:e])
+        return self
 
     def forward(self, input_ids, attention_mask=None, want_pooled=True, want_hidden=True, ragged=False,
                 live_rows_hint=-1):

@@ -161,6 +161,9 @@ typedef struct {
   const float* rel_bias;    /* [buckets, H]   encoder.block.0...relative_attention_bias.weight       */
   const float* final_ln;    /* [d]            encoder.final_layer_norm.weight                        */
   const GdrT5EncLayer* layers;  /* host array of num_layers entries (device pointers inside)        */
+  const float* qkv0_table;  /* optional [vocab_size, 3*inner] fp32, NULL = compute: row id holds block 0's q/k/v of token id,
+                             * rmsnorm(embed[id], layers[0].ln_attn) x layers[0].wqkv^T as gdr_t5_layer_norm + gdr_linear_f32
+                             * give it.  Read by gdr_t5_encoder_forward_ragged alone (see there); a snapshot of the weights. */
 } GdrT5EncoderWeights;
 
 size_t gdr_t5_encoder_workspace_bytes(const GdrT5Dims* dims, int B, int L);
@@ -187,7 +190,16 @@ int gdr_t5_encoder_forward(const GdrT5EncoderWeights* w, const int64_t* ids, con
  *     speed, never a bit of the result.
  * Batches of fewer than 256 token rows, or d_kv != 64, run the padded form internally (same outputs); below 4 096 token
  * rows the packed form runs on the split-K / stream-K kernel forms the padded forward picks for the same B*L (kept rows
- * still bit-identical) and the pooled-only shortcut of the last block is not taken. */
+ * still bit-identical) and the pooled-only shortcut of the last block is not taken.
+ * From 192 tiles of 128 x 128 over B*L x d_model (the form with the pooled-only shortcut) two more pieces of work that the
+ * result does not need are left out, both exact:
+ *   - w->qkv0_table != NULL: block 0's q/k/v are a function of the token id alone (T5 adds no position embedding, the norm is
+ *     per row, GEMM rows are independent), so they are gathered from the table by the id that also picks the embedding row —
+ *     one launch for both — instead of a norm and a [rows, 3*inner, d_model] linear per call.  Smaller batches, the padded
+ *     form, the bf16 mode and the split form never read the field.
+ *   - pooled-only, last block (GDR_ENC_LAST_Q_CLS, see README): k and v over every live row, q for the B CLS rows alone
+ *     (gather, un-split linear, scatter into the q columns); the other q rows are stale and feed attention lanes whose
+ *     output nothing reads. */
 size_t gdr_t5_encoder_ragged_workspace_bytes(const GdrT5Dims* dims, int B, int L);
 int gdr_t5_encoder_forward_ragged(const GdrT5EncoderWeights* w, const int64_t* ids, const int64_t* mask, int B, int L,
                                   float* out_hidden, float* out_pooled, int64_t live_rows_hint, void* workspace,
