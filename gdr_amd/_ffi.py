@@ -15,6 +15,10 @@ RERANK_POSITIONS = 1
 SIM_EXHAUSTIVE = 1
 SIM_NO_STREAM = 2
 EPI_NONE, EPI_RESIDUAL, EPI_RELU, EPI_BIAS, EPI_BIAS_RELU, EPI_BIAS_RESIDUAL, EPI_BIAS_GELU = range(7)
+# gdr_linear_f32_form (include/gdr_hip.h GDR_F32_FORM_*): the kernel form of a dense fp32 linear; 0 = a shape the linear refuses
+(F32_FORM_TILES, F32_FORM_PERSISTENT, F32_FORM_SMALL, F32_FORM_SMALL_SPLITK, F32_FORM_SPLITK, F32_FORM_STREAMK_256,
+ F32_FORM_STREAMK_TAIL) = range(1, 8)
+STREAMK_WS_BYTES = 33558528      # the smallest gdr_linear_f32_splitk workspace that admits the stream-K forms: 512 x 64 KiB + 4 KiB
 
 
 class GdrError(RuntimeError):

@@ -35,7 +35,9 @@ struct SimPlan {
   size_t off_val, off_idx, off_cnt, off_thr, off_part, total;
 };
 
-static SimPlan make_plan(int B, int64_t N, int k, bool exhaustive) {
+// survivors: by how much the filter pass's threshold admits more docs than the k-th largest sample score would (1 = that score
+// itself; the pre-filter lowers it by 2 eps_q, see prefilter_survivor_factor).
+static SimPlan make_plan(int B, int64_t N, int k, bool exhaustive, double survivors = 1.0) {
   SimPlan p{};
   p.tiles_m = (N + TILE - 1) / TILE;
   double target = sqrt((double)k * (double)N);
@@ -54,7 +56,7 @@ static SimPlan make_plan(int B, int64_t N, int k, bool exhaustive) {
   } else {
     const double n_sample = (double)p.n_slots;
     const double expect = (double)k * (double)N / n_sample;
-    p.cap = p.n_slots + (int64_t)(4.0 * expect) + 4096;
+    p.cap = p.n_slots + (int64_t)(4.0 * expect * survivors) + 4096;
     p.cap = (p.cap + TILE - 1) / TILE * TILE;
   }
   size_t o = 0;
@@ -680,6 +682,9 @@ int gdr::sim_topk_impl(const void* Q, int B, const void* D, int64_t N, int d, in
                 (long long)N, d);
   GDR_CHECK_ARG(k >= 1 && k <= 1024 && k <= N, "sim_topk: k=%d must be in [1, min(1024, N)]", k);
   GDR_CHECK_ARG(N < 0x7fffffffLL - 256, "sim_topk: shard too large for int32 doc ids");
+  GDR_CHECK_ARG((int64_t)idx_offset + N <= 0x7fffffffLL,
+                "sim_topk: idx_offset=%d + N=%lld leaves int32 doc ids (the largest id, idx_offset + N - 1, must be < 2^31 - 1)", (int)idx_offset,
+                (long long)N);
   GDR_CHECK_ARG(((uintptr_t)Q & 15) == 0 && ((uintptr_t)D & 15) == 0 && ((uintptr_t)workspace & 255) == 0,
                 "sim_topk: Q, D must be 16-byte and workspace 256-byte aligned");
   const SimPlan p = make_plan(B, N, k, (flags & GDR_SIM_EXHAUSTIVE) != 0);
@@ -995,9 +1000,34 @@ struct PrefilterPlan {
   int cap2;
   size_t off_q16, off_eps, total;
 };
+// The pre-filter's filter pass keeps s~ >= L - 2 eps_q, not s~ >= L (L: the k-th largest sample score), so it appends more docs than the
+// k N / n_sample that make_plan's capacity expects — 3.6 times as many at N = 2.8 M, d = 768, k = 100, where the 4x headroom of the plain
+// plan left 2 of 40 queries of a Gaussian corpus with an overflowed list (status 1; 62 .. 91 k entries for 87 k slots:
+// tests/test_gpu_large_offsets.py).  For Gaussian scores of deviation |q| sigma (sigma: rms doc entry, sqrt(d) sigma: rms row norm) the
+// cut drops from z_L = Q^-1(k / n_sample) by
+//   dz = 2 eps_q / (|q| sigma) = 2 sqrt(d) (2^-7 + 2^-16 + d 2^-22) rho,   rho = max ||D[r]|| / rms ||D[r]||,
+// and the survivors grow by Q(z_L - dz) / Q(z_L).  Half of that ratio (at least 1) scales the capacity: twice the expected list.
+// rho is not known to the host (dnorm_max is, the rms norm is not): 1 for a normalised corpus, 1.13 for 2.8 M Gaussian rows of 768
+// entries; 1.25 is taken, so that corpora with moderately uneven norms keep the factor-two margin.  A corpus that is far from this
+// model (heavy-tailed scores, one row of a huge norm) costs what it cost before: a flagged query, repaired by the caller.
+static double prefilter_survivor_factor(int64_t N, int d, int k) {
+  const SimPlan p0 = make_plan(1, N, k, false);
+  if (p0.stride == 1) return 1.0;
+  const auto Qf = [](double z) { return 0.5 * erfc(z * 0.70710678118654752); };
+  const double tail = (double)k / (double)p0.n_slots;
+  double lo = -8.0, hi = 8.0;  // Q is decreasing: bisect Q(z) = tail
+  for (int it = 0; it < 60; ++it) {
+    const double mid = 0.5 * (lo + hi);
+    (Qf(mid) > tail ? lo : hi) = mid;
+  }
+  const double zl = 0.5 * (lo + hi);
+  const double dz = 2.0 * sqrt((double)d) * (0x1p-7 + 0x1p-16 + d * 0x1p-22) * 1.25;
+  const double f = 0.5 * Qf(zl - dz) / tail;
+  return f > 1.0 ? f : 1.0;
+}
 static PrefilterPlan make_prefilter_plan(int B, int64_t N, int d, int k) {
   PrefilterPlan pp{};
-  pp.p = make_plan(B, N, k, false);
+  pp.p = make_plan(B, N, k, false, prefilter_survivor_factor(N, d, k));
   pp.cap2 = prefilter_cap2(k);
   size_t o = pp.p.total;
   pp.off_q16 = o, o += align_up((size_t)B * d * 2, 256);
@@ -1038,6 +1068,9 @@ extern "C" int gdr_sim_topk_prefilter(const float* Q, int B, const float* D, con
                 (long long)N, d);
   GDR_CHECK_ARG(k >= 1 && k <= 1024 && k <= N, "sim_topk_prefilter: k=%d must be in [1, min(1024, N)]", k);
   GDR_CHECK_ARG(N < 0x7fffffffLL - 256, "sim_topk_prefilter: shard too large for int32 doc ids");
+  GDR_CHECK_ARG((int64_t)idx_offset + N <= 0x7fffffffLL,
+                "sim_topk_prefilter: idx_offset=%d + N=%lld leaves int32 doc ids (the largest id, idx_offset + N - 1, must be < 2^31 - 1)",
+                (int)idx_offset, (long long)N);
   GDR_CHECK_ARG(dnorm_max > 0.f && dnorm_max < INFINITY, "sim_topk_prefilter: dnorm_max must be the largest row norm of D (> 0, finite)");
   GDR_CHECK_ARG(((uintptr_t)Q & 15) == 0 && ((uintptr_t)D & 15) == 0 && ((uintptr_t)D_bf16 & 15) == 0 && ((uintptr_t)workspace & 255) == 0,
                 "sim_topk_prefilter: Q, D, D_bf16 must be 16-byte and workspace 256-byte aligned");

@@ -238,7 +238,8 @@ int gdr_t5_encoder_forward_bf16(const GdrT5EncoderWeights* w, const int64_t* ids
  * replaces `compute_similarity` (dense.py:53-54, encoder.py:128-129: q @ p.T) followed by
  * `Tensor.topk(k, largest=True, sorted=True)` (as at main_models.py:1625).
  *   Q fp32[B,d], D fp32[N,d] (the resident corpus shard) -> out_val fp32[B,k] descending,
- *   out_idx int32[B,k] = row in D + idx_offset.  Ties: higher score first, then lower id.  Scores are ordered by the IEEE
+ *   out_idx int32[B,k] = row in D + idx_offset (idx_offset + N <= 2^31 - 1, else GDR_EINVAL: the largest id is 2^31 - 2).
+ *   Ties: higher score first, then lower id.  Scores are ordered by the IEEE
  *   total order of their fp32 bit patterns (the kernels' sort keys), which differs from comparison by value in ONE place:
  *   +0.0 ranks above -0.0 whatever the ids.  The same holds for gdr_sim_topk_bf16 / _prefilter, gdr_topk_merge,
  *   gdr_topk_merge_packed and gdr_rerank_topk*; a NaN score is not ordered (inputs are finite).
@@ -271,7 +272,11 @@ int gdr_sim_topk_bf16(const void* Q, int B, const void* D, int64_t N, int d, int
  * that band provably contains the fp32 top-k including every doc tied at the cut (derivation: csrc/sim_topk.hip), so out_val / out_idx
  * are the top-k of the fp32 scores for every input, ties as in gdr_sim_topk (higher score, then lower id); the values are fp32 dot
  * products of the same operands in another summation order.  dnorm_max: the largest ||D[r]||_2 (sqrt of gdr_row_norm2_max's result).
- * status as in gdr_sim_topk (1 = an overflowed list: re-run that query with gdr_sim_topk).  d % 8 == 0, d <= 1024. */
+ * status as in gdr_sim_topk (1 = an overflowed list: re-run that query with gdr_sim_topk).  d % 8 == 0, d <= 1024.
+ * The workspace depends on d beyond the bf16 queries it holds: the filter pass keeps every doc above the sample threshold MINUS 2 eps_q,
+ * and 2 eps_q measured in deviations of a query's scores grows like sqrt(d), so the candidate list is sized for that lowered threshold
+ * (never smaller than gdr_sim_topk's list for the same B, N, k; non-decreasing in d).  The sizing is an expectation for scores that are
+ * roughly Gaussian and row norms within 1.25 of their rms; other corpora are served by the status contract above. */
 size_t gdr_sim_topk_prefilter_workspace_bytes(int B, int64_t N, int d, int k);
 int gdr_sim_topk_prefilter(const float* Q, int B, const float* D, const void* D_bf16, float dnorm_max, int64_t N, int d, int k,
                            int32_t idx_offset, float* out_val, int32_t* out_idx, int32_t* status, void* workspace,
