@@ -13,6 +13,11 @@
 //   rerank_select    a workgroup per (alpha, query): softmax of the R length-penalised beam scores (:1598-1601),
 //                    key = orderable(sim + alpha*p[cluster]) << 32 | ~position, one bitonic sort in LDS, first k
 //                    (ties: higher score, then earlier candidate — torch leaves tie order unspecified).
+//   rerank_chunk / rerank_merge   the same select for lists of more than 8 192 candidates (up to 2^20), which no single
+//                    LDS sort holds.  The keys are a strict total order, so the top-k of a list is the top-k of the union of
+//                    its pieces' top-k whatever the cut: a workgroup per (chunk of 4 096 positions, alpha, query) sorts its
+//                    chunk's keys and keeps the first k, then rounds of the same sort over up to 8 192 / k partial lists
+//                    leave one list per (alpha, query) — bit for bit what rerank_select would return from a larger LDS.
 // Sharded corpus (GDR mode): a rank passes its row block [doc_lo, doc_hi) — candidates outside are skipped —
 // and asks for candidate POSITIONS; per-candidate scores do not depend on the shard, and a merge by "higher score, then
 // lower position" (gdr_topk_merge_packed) of the per-shard lists reproduces the unsharded list bit for bit.
@@ -25,6 +30,13 @@ namespace gdr {
 constexpr int RR_MAX_CAND = 8192;
 constexpr int RR_MAX_BEAMS = 1024;
 constexpr int RR_CH = 16;  // candidates per workgroup of the dot pass: 4 waves x 4 rows in flight each
+// the long-list select (rerank_chunk_kernel / rerank_merge_kernel)
+constexpr int RR_LONG_MAX_CAND = 1 << 20;
+constexpr int RR_LCH = 4096;    // candidate positions per chunk: 32 KiB of keys, two 1024-thread workgroups per CU
+constexpr int RR_LONG_MAX_K = RR_MAX_BEAMS;
+constexpr int RR_ASLOTS = 8;    // alphas per pass over the partial-list scratch (gdr_rerank_workspace_bytes has no A)
+constexpr int RR_MIN_GROUP = RR_MAX_CAND / RR_LONG_MAX_K;  // partial lists one merge workgroup takes at the largest k
+static_assert(RR_LONG_MAX_K <= RR_LCH && RR_MIN_GROUP >= 2, "a chunk keeps k keys; a merge round must shrink the list count");
 
 __device__ __forceinline__ uint32_t rr_fkey(float v) {
   const uint32_t u = __float_as_uint(v);
@@ -143,6 +155,44 @@ __device__ __forceinline__ void rr_bitonic_desc(unsigned long long* keys, int np
   __syncthreads();
 }
 
+// ---- pieces shared by the one-sort select and the long-list select: they must produce the same bits ----------------
+// softmax over the R beam scores (main_models.py:1598-1601), by ONE wave: the summation order does not depend on the
+// workgroup size
+__device__ __forceinline__ void rr_beam_softmax(const float* __restrict__ bs, int R, float* prob, int lane) {
+  float mx = -INFINITY;
+  for (int j = lane; j < R; j += 64) mx = fmaxf(mx, bs[j]);
+  mx = wave_max(mx);
+  float sm = 0.f;
+  for (int j = lane; j < R; j += 64) {
+    const float e = expf(bs[j] - mx);
+    prob[j] = e;
+    sm += e;
+  }
+  sm = wave_sum(sm);
+  for (int j = lane; j < R; j += 64) prob[j] = prob[j] / sm;
+}
+// key of candidate position c: s + alpha*p with two roundings as in torch, then "earlier position first"
+__device__ __forceinline__ unsigned long long rr_key(float s0, float ap, int c) {
+  return ((unsigned long long)rr_fkey(__fadd_rn(s0, ap)) << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)c);
+}
+// the first k of the sorted keys -> one (alpha, query) row of out_val / out_idx; key 0 = no candidate: -inf / -1
+__device__ __forceinline__ void rr_write_topk(const unsigned long long* keys, int npad, int k,
+                                              const int32_t* __restrict__ cand_ids, int64_t base, int positions,
+                                              float* __restrict__ out_val, int32_t* __restrict__ out_idx) {
+  for (int i = threadIdx.x; i < k; i += blockDim.x) {
+    float v = -INFINITY;
+    int32_t id = -1;
+    const unsigned long long key = i < npad ? keys[i] : 0ull;
+    if (key != 0ull) {
+      v = rr_fkey_inv((uint32_t)(key >> 32));
+      const int c = (int)(0xFFFFFFFFu - (uint32_t)(key & 0xFFFFFFFFull));
+      id = positions ? c : cand_ids[base + c];
+    }
+    out_val[i] = v;
+    out_idx[i] = id;
+  }
+}
+
 // ---- per (alpha, query): sorted top-k of sim + alpha * softmax(beam scores)[cluster of the candidate] ---------------
 __global__ __launch_bounds__(1024) void rerank_select_kernel(const float* __restrict__ sim,
                                                              const int32_t* __restrict__ cand_offsets,
@@ -162,22 +212,7 @@ __global__ __launch_bounds__(1024) void rerank_select_kernel(const float* __rest
   ncand = ncand < npad ? ncand : npad;
   ncand = ncand < max_cand ? ncand : max_cand;
   for (int c = tid; c < npad; c += nthr) keys[c] = 0ull;
-  // softmax over the R beam scores (main_models.py:1598-1601), by the first wave: the summation order does not depend
-  // on the workgroup size
-  if (wave == 0) {
-    const float* bs = beam_scores + (int64_t)b * R;
-    float mx = -INFINITY;
-    for (int j = lane; j < R; j += 64) mx = fmaxf(mx, bs[j]);
-    mx = wave_max(mx);
-    float sm = 0.f;
-    for (int j = lane; j < R; j += 64) {
-      const float e = expf(bs[j] - mx);
-      prob[j] = e;
-      sm += e;
-    }
-    sm = wave_sum(sm);
-    for (int j = lane; j < R; j += 64) prob[j] = prob[j] / sm;
-  }
+  if (wave == 0) rr_beam_softmax(beam_scores + (int64_t)b * R, R, prob, lane);
   __syncthreads();
   const float alpha = alphas[ai];
   const float* sb = sim + (int64_t)b * max_cand;
@@ -186,25 +221,114 @@ __global__ __launch_bounds__(1024) void rerank_select_kernel(const float* __rest
     const float ap = __fmul_rn(alpha, prob[j]);
     for (int c = lo + lane; c < hi && c < ncand; c += 64) {
       const float s0 = sb[c];
-      if (s0 > -INFINITY)  // -inf marks a candidate outside this rank's shard
-        keys[c] = ((unsigned long long)rr_fkey(__fadd_rn(s0, ap)) << 32) |  // s + alpha*p: two roundings as in torch
-                  (unsigned long long)(0xFFFFFFFFu - (uint32_t)c);
+      if (s0 > -INFINITY) keys[c] = rr_key(s0, ap, c);  // -inf marks a candidate outside this rank's shard
     }
   }
   __syncthreads();
   rr_bitonic_desc(keys, npad);
-  for (int i = tid; i < k; i += nthr) {
-    float v = -INFINITY;
-    int32_t id = -1;
-    const unsigned long long key = i < npad ? keys[i] : 0ull;
-    if (key != 0ull) {
-      v = rr_fkey_inv((uint32_t)(key >> 32));
-      const int c = (int)(0xFFFFFFFFu - (uint32_t)(key & 0xFFFFFFFFull));
-      id = positions ? c : cand_ids[base + c];
-    }
-    out_val[((int64_t)b * A + ai) * k + i] = v;
-    out_idx[((int64_t)b * A + ai) * k + i] = id;
+  rr_write_topk(keys, npad, k, cand_ids, base, positions, out_val + ((int64_t)b * A + ai) * k,
+                out_idx + ((int64_t)b * A + ai) * k);
+}
+
+// ---- the select for long lists: per (chunk, alpha, query) the chunk's k best keys -----------------------------------
+// Same softmax, same two roundings, same keys (the position in the key is the candidate's position in the WHOLE list) and
+// the same sort as rerank_select_kernel, over candidate positions [chunk * RR_LCH, (chunk + 1) * RR_LCH).  A chunk
+// without a live key (past the query's count, or all of it outside [doc_lo, doc_hi)) leaves k zero keys.
+// part: [B][gridDim.x / nchunk alphas][nchunk][k].
+__global__ __launch_bounds__(1024) void rerank_chunk_kernel(const float* __restrict__ sim,
+                                                            const int32_t* __restrict__ cand_offsets,
+                                                            const float* __restrict__ beam_scores, int R,
+                                                            const float* __restrict__ alphas, int k, int npad, int nchunk,
+                                                            int max_cand, int cand_stride,
+                                                            unsigned long long* __restrict__ part) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  unsigned long long* keys = reinterpret_cast<unsigned long long*>(smem_raw);  // [npad]
+  float* prob = reinterpret_cast<float*>(keys + npad);                         // [R]
+  const int chunk = blockIdx.x % nchunk, as = blockIdx.x / nchunk, b = blockIdx.y;
+  const int tid = threadIdx.x, nthr = blockDim.x, wave = tid >> 6, lane = tid & 63, nwaves = nthr >> 6;
+  const CandSeg cs = cand_seg(cand_offsets, b, R, cand_stride);
+  int ncand = cs.off[R] - cs.off[0];
+  ncand = ncand < max_cand ? ncand : max_cand;
+  const int c_lo = chunk * RR_LCH, c_hi = c_lo + RR_LCH < ncand ? c_lo + RR_LCH : ncand;
+  unsigned long long* dst = part + ((int64_t)b * gridDim.x + blockIdx.x) * k;
+  if (c_lo >= ncand) {  // workgroup-uniform
+    for (int i = tid; i < k; i += nthr) dst[i] = 0ull;
+    return;
   }
+  for (int c = tid; c < npad; c += nthr) keys[c] = 0ull;
+  if (wave == 0) rr_beam_softmax(beam_scores + (int64_t)b * R, R, prob, lane);
+  __syncthreads();
+  const float alpha = alphas[as];
+  const float* sb = sim + (int64_t)b * max_cand;
+  for (int j = wave; j < R; j += nwaves) {  // a wave per cluster segment, the part of it inside the chunk
+    int lo = cs.off[j] - cs.off[0], hi = cs.off[j + 1] - cs.off[0];
+    lo = lo > c_lo ? lo : c_lo;
+    hi = hi < c_hi ? hi : c_hi;
+    const float ap = __fmul_rn(alpha, prob[j]);
+    for (int c = lo + lane; c < hi; c += 64) {
+      const float s0 = sb[c];
+      if (s0 > -INFINITY) keys[c - c_lo] = rr_key(s0, ap, c);
+    }
+  }
+  __syncthreads();
+  rr_bitonic_desc(keys, npad);
+  for (int i = tid; i < k; i += nthr) dst[i] = i < npad ? keys[i] : 0ull;
+}
+
+// One merge round: a workgroup per (group of up to G consecutive partial lists, alpha, query) sorts the group's keys
+// (G * k <= 8192) and keeps the first k.  src [B][ag][n_in][k] -> dst [B][ag][n_out][k]; the last round (n_out == 1,
+// dst == nullptr) writes alpha a0 + as of out_val / out_idx exactly as rerank_select_kernel does.
+__global__ __launch_bounds__(1024) void rerank_merge_kernel(const unsigned long long* __restrict__ src, int n_in, int G,
+                                                            int n_out, int k, int npad,
+                                                            unsigned long long* __restrict__ dst,
+                                                            const int32_t* __restrict__ cand_offsets,
+                                                            const int32_t* __restrict__ cand_ids, int R, int cand_stride,
+                                                            int positions, int A, int a0, float* __restrict__ out_val,
+                                                            int32_t* __restrict__ out_idx) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  unsigned long long* keys = reinterpret_cast<unsigned long long*>(smem_raw);  // [npad]
+  const int g = blockIdx.x % n_out, as = blockIdx.x / n_out, ag = gridDim.x / n_out, b = blockIdx.y;
+  const int tid = threadIdx.x, nthr = blockDim.x;
+  const int lists = n_in - g * G < G ? n_in - g * G : G;
+  const int cnt = lists * k;  // <= npad
+  const unsigned long long* in = src + (((int64_t)b * ag + as) * n_in + (int64_t)g * G) * k;
+  for (int t = tid; t < npad; t += nthr) keys[t] = t < cnt ? in[t] : 0ull;
+  __syncthreads();
+  rr_bitonic_desc(keys, npad);
+  if (dst != nullptr) {
+    unsigned long long* o = dst + ((int64_t)b * gridDim.x + blockIdx.x) * k;
+    for (int i = tid; i < k; i += nthr) o[i] = i < npad ? keys[i] : 0ull;
+    return;
+  }
+  rr_write_topk(keys, npad, k, cand_ids, cand_seg(cand_offsets, b, R, cand_stride).base, positions,
+                out_val + ((int64_t)b * A + a0 + as) * k, out_idx + ((int64_t)b * A + a0 + as) * k);
+}
+
+static int rr_pow2(int n) {  // sort width: the power of two >= n, at least one wave
+  int p = 64;
+  while (p < n) p <<= 1;
+  return p;
+}
+
+// Workspace of the long-list form: sim[B][max_cand], then the chunk pass's partial lists and the lists a merge round
+// writes (the rounds alternate between the two), both for RR_ASLOTS alphas at k = RR_LONG_MAX_K — the sizing call knows
+// neither A nor k.  At the largest k a round merges RR_MIN_GROUP lists, at a smaller k more: never more lists than sized.
+struct RrLongPlan {
+  int nchunk;
+  size_t sim_bytes, part0_bytes, part1_bytes;
+};
+static RrLongPlan rr_long_plan(int B, int max_cand) {
+  RrLongPlan p;
+  p.nchunk = (max_cand + RR_LCH - 1) / RR_LCH;
+  const size_t list = (size_t)B * RR_ASLOTS * RR_LONG_MAX_K * sizeof(unsigned long long);
+  p.sim_bytes = align_up((size_t)B * (size_t)max_cand * sizeof(float), 256);
+  p.part0_bytes = align_up(list * (size_t)p.nchunk, 256);
+  p.part1_bytes = align_up(list * (size_t)((p.nchunk + RR_MIN_GROUP - 1) / RR_MIN_GROUP), 256);
+  return p;
+}
+static size_t rr_long_workspace_bytes(int B, int max_cand) {
+  const RrLongPlan p = rr_long_plan(B, max_cand);
+  return p.sim_bytes + p.part0_bytes + p.part1_bytes;
 }
 
 static int rerank_impl(const float* q, const void* D, bool bf16, int d, const int32_t* cand_offsets, const int32_t* cand_ids,
@@ -216,18 +340,19 @@ static int rerank_impl(const float* q, const void* D, bool bf16, int d, const in
   GDR_CHECK_ARG(B > 0 && R > 0 && R <= RR_MAX_BEAMS && A > 0 && k > 0 && d > 0 && d % 4 == 0,
                 "rerank: bad shape B=%d R=%d A=%d k=%d d=%d", B, R, A, k, d);
   GDR_CHECK_ARG(func == 0 || func == 1, "rerank: func must be 0 (tanh) or 1 (sigmoid)");
-  GDR_CHECK_ARG(max_cand >= 1 && max_cand <= RR_MAX_CAND, "rerank: max_cand=%d must be in [1,%d]", max_cand, RR_MAX_CAND);
-  GDR_CHECK_ARG((flags & ~GDR_RERANK_POSITIONS) == 0, "rerank: unknown flags %d", flags);
+  GDR_CHECK_ARG(max_cand >= 1 && max_cand <= RR_LONG_MAX_CAND, "rerank: max_cand=%d must be in [1,%d]", max_cand, RR_LONG_MAX_CAND);
+  GDR_CHECK_ARG((flags & ~(GDR_RERANK_POSITIONS | GDR_RERANK_CHUNKED)) == 0, "rerank: unknown flags %d", flags);
+  const bool chunked = max_cand > RR_MAX_CAND || (flags & GDR_RERANK_CHUNKED) != 0;
+  GDR_CHECK_ARG(!chunked || k <= RR_LONG_MAX_K, "rerank: k=%d must be <= %d for a list of more than %d candidates (max_cand=%d) or with "
+                "GDR_RERANK_CHUNKED", k, RR_LONG_MAX_K, RR_MAX_CAND, max_cand);
   GDR_CHECK_ARG(cand_stride == 0 || cand_stride >= max_cand, "rerank: cand_stride=%d must be 0 (one CSR) or >= max_cand=%d",
                 cand_stride, max_cand);
-  const size_t need = gdr_rerank_workspace_bytes(B, max_cand);
+  const size_t need = chunked ? rr_long_workspace_bytes(B, max_cand) : gdr_rerank_workspace_bytes(B, max_cand);
   if (workspace_bytes < need) {
     set_error("rerank: workspace %zu < required %zu", workspace_bytes, need);
     return GDR_ENOSPC;
   }
   float* sim = static_cast<float*>(workspace);
-  int npad = 64;
-  while (npad < max_cand) npad <<= 1;
   const double bytes = (double)B * max_cand * d * (bf16 ? 2 : 4);  // upper bound: the live candidate count lives on the device
   {
     ProfScope prof(PROF_RERANK, bytes, stream);
@@ -240,13 +365,44 @@ static int rerank_impl(const float* q, const void* D, bool bf16, int d, const in
                          doc_hi, max_cand, cand_stride, sim);
     GDR_CHECK_LAUNCH("rerank_dot_kernel");
   }
-  const size_t lds = (size_t)npad * 8 + (size_t)R * 4;
-  if (int rc__ = ensure_dyn_lds(reinterpret_cast<const void*>(rerank_select_kernel), 80 * 1024, "rerank")) return rc__;
+  const int positions = (flags & GDR_RERANK_POSITIONS) ? 1 : 0;
   ProfScope prof(PROF_SELECT, 0.0, stream);
-  hipLaunchKernelGGL(rerank_select_kernel, dim3((unsigned)A, (unsigned)B), dim3(npad >= 2048 ? 1024 : 256), lds, stream, sim,
-                     cand_offsets, cand_ids, beam_scores, R, alphas, A, k, npad, max_cand, cand_stride,
-                     (flags & GDR_RERANK_POSITIONS) ? 1 : 0, out_val, out_idx);
-  GDR_CHECK_LAUNCH("rerank_select_kernel");
+  if (!chunked) {
+    const int npad = rr_pow2(max_cand);
+    const size_t lds = (size_t)npad * 8 + (size_t)R * 4;
+    if (int rc__ = ensure_dyn_lds(reinterpret_cast<const void*>(rerank_select_kernel), 80 * 1024, "rerank")) return rc__;
+    hipLaunchKernelGGL(rerank_select_kernel, dim3((unsigned)A, (unsigned)B), dim3(npad >= 2048 ? 1024 : 256), lds, stream, sim,
+                       cand_offsets, cand_ids, beam_scores, R, alphas, A, k, npad, max_cand, cand_stride, positions, out_val,
+                       out_idx);
+    GDR_CHECK_LAUNCH("rerank_select_kernel");
+    return GDR_OK;
+  }
+  // long lists: the two partial-list buffers follow sim, each sized for RR_ASLOTS alphas at k = RR_LONG_MAX_K
+  const RrLongPlan plan = rr_long_plan(B, max_cand);
+  unsigned char* ws = static_cast<unsigned char*>(workspace);
+  unsigned long long* part[2] = {reinterpret_cast<unsigned long long*>(ws + plan.sim_bytes),
+                                 reinterpret_cast<unsigned long long*>(ws + plan.sim_bytes + plan.part0_bytes)};
+  if (int rc__ = ensure_dyn_lds(reinterpret_cast<const void*>(rerank_merge_kernel), RR_MAX_CAND * 8, "rerank")) return rc__;
+  const int cpad = rr_pow2(max_cand < RR_LCH ? max_cand : RR_LCH);
+  const int G = RR_MAX_CAND / k;  // >= RR_MIN_GROUP
+  for (int a0 = 0; a0 < A; a0 += RR_ASLOTS) {  // the scratch holds RR_ASLOTS alphas: the groups follow each other on the stream
+    const int ag = A - a0 < RR_ASLOTS ? A - a0 : RR_ASLOTS;
+    hipLaunchKernelGGL(rerank_chunk_kernel, dim3((unsigned)(plan.nchunk * ag), (unsigned)B), dim3(cpad >= 2048 ? 1024 : 256),
+                       (size_t)cpad * 8 + (size_t)R * 4, stream, sim, cand_offsets, beam_scores, R, alphas + a0, k, cpad, plan.nchunk,
+                       max_cand, cand_stride, part[0]);
+    GDR_CHECK_LAUNCH("rerank_chunk_kernel");
+    int n = plan.nchunk, from = 0;
+    do {
+      const int n_out = (n + G - 1) / G;
+      const int npad = rr_pow2((n < G ? n : G) * k);
+      hipLaunchKernelGGL(rerank_merge_kernel, dim3((unsigned)(n_out * ag), (unsigned)B), dim3(npad >= 2048 ? 1024 : 256),
+                         (size_t)npad * 8, stream, part[from], n, G, n_out, k, npad, n_out == 1 ? nullptr : part[from ^ 1],
+                         cand_offsets, cand_ids, R, cand_stride, positions, A, a0, out_val, out_idx);
+      GDR_CHECK_LAUNCH("rerank_merge_kernel");
+      n = n_out;
+      from ^= 1;
+    } while (n > 1);
+  }
   return GDR_OK;
 }
 
@@ -401,6 +557,7 @@ extern "C" int gdr_rerank_positions_to_ids(const int32_t* pos, const int32_t* ca
 
 extern "C" size_t gdr_rerank_workspace_bytes(int B, int max_cand) {
   if (B <= 0 || max_cand <= 0) return 0;
+  if (max_cand > gdr::RR_MAX_CAND) return gdr::rr_long_workspace_bytes(B, max_cand);
   return gdr::align_up((size_t)B * (size_t)max_cand * sizeof(float), 256);
 }
 

@@ -83,8 +83,10 @@ class ShardedIndex:
             merge_packed = merge_packed or (lambda pairs: ops.topk_merge_packed(pairs, return_status=True))
         if local_rerank is None:
             from . import ops as _ops
+            # the bound comes from the GATHERED offsets, the same on every rank: all ranks take the same form of the select
             local_rerank = (lambda q, D, offs, ids, beam, alphas, k, lo, hi, func, positions: _ops.rerank_topk(
-                q, D, offs, ids, beam, alphas, k, func=func, max_cand=_ops.block_max_cand(offs, beam.shape[1], ids.shape[1]),
+                q, D, offs, ids, beam, alphas, k, func=func,
+                max_cand=_ops.block_max_cand(offs, beam.shape[1], ids.shape[1], cap=_ops.RERANK_LONG_MAX_CAND),
                 doc_range=(lo, hi), positions=positions, cand_stride=ids.shape[1]))
         self.local_topk, self.pack, self.merge_packed, self.local_rerank = local_topk, pack, merge_packed, local_rerank
         self.distributed = dist.is_initialized()      # a 1-rank group still runs the collectives (exercises RCCL)

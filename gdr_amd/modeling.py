@@ -535,7 +535,7 @@ class GDRRetriever:
             _cl, offs, dev_ids, stride = dci.candidates(state["ids"], B, R)
             # the sharded stage 2 takes its bound from the GATHERED offsets (dist.ShardedIndex): a rank-local decision here could
             # raise on one rank while its peers already sit in the fixed-size all-gather
-            max_cand = ops.block_max_cand(offs, R, stride) if self.sharded is None else 0
+            max_cand = 0 if self.sharded is not None else ops.block_max_cand(offs, R, stride, cap=ops.RERANK_LONG_MAX_CAND)
             beam_scores = state["scores"].to(torch.float32).view(B, R)          # fp64 -> fp32 as torch.tensor(list) rounds
         outs = scores = None
         if dci is None:

@@ -288,12 +288,15 @@ _RERANK_WS = {}
 
 
 def rerank_topk(q, D, cand_offsets, cand_ids, beam_scores, alphas, k, func="tanh", max_cand=None, doc_range=None,
-                positions=False, workspace=None, cand_stride=0):
+                positions=False, workspace=None, cand_stride=0, chunked=False):
     """In-cluster rerank — gdr_rerank_topk / gdr_rerank_topk_bf16 (chosen by D.dtype; a bf16 corpus is gathered as bf16,
     never up-cast).  Returns (values fp32[B,A,k], doc ids int32[B,A,k]).
     cand_stride=0: cand_offsets int32[B*R+1] is ONE CSR into cand_ids (the reference's concatenation order);
     cand_stride>0: per-query blocks — cand_offsets int32[B,R+1] relative, cand_ids int32[B,cand_stride] (DeviceClusterIndex).
-    max_cand: bound of any query's candidate count; None reads it from the CSR (one host sync).
+    max_cand: bound of any query's candidate count, at most RERANK_LONG_MAX_CAND; None reads it from the CSR (one host
+    sync).  Up to RERANK_MAX_CAND one LDS sort ranks a query's list; above, chunks of RERANK_CHUNK positions are sorted and
+    their first k merged (k <= 1024 there) — the same list bit for bit.  chunked=True takes that form at any max_cand
+    (GDR_RERANK_CHUNKED: the A/B switch of tests and tools).
     doc_range=(lo, hi): D holds rows [lo, hi) of the corpus, candidates outside are skipped (sharded GDR mode, dist.py);
     positions=True returns candidate positions within the query's list instead of doc ids (what the shard merge needs)."""
     _need_cuda(q, D, cand_offsets, cand_ids, beam_scores)
@@ -319,12 +322,13 @@ def rerank_topk(q, D, cand_offsets, cand_ids, beam_scores, alphas, k, func="tanh
     lo, hi = (0, D.shape[0]) if doc_range is None else (int(doc_range[0]), int(doc_range[1]))
     if hi - lo != D.shape[0]:
         raise _ffi.GdrError(f"rerank_topk: doc_range {(lo, hi)} does not match the {D.shape[0]} rows given")
-    ws = (workspace or _RERANK_WS.setdefault(q.device, Workspace(q.device))).get(lib().gdr_rerank_workspace_bytes(B, max_cand))
+    ws_bytes = lib().gdr_rerank_workspace_bytes(B, max(max_cand, RERANK_MAX_CAND + 1) if chunked else max_cand)
+    ws = (workspace or _RERANK_WS.setdefault(q.device, Workspace(q.device))).get(ws_bytes)
     ov = torch.empty((B, A, k), dtype=torch.float32, device=q.device)
     oi = torch.empty((B, A, k), dtype=torch.int32, device=q.device)
     check(fn(ptr(q), ptr(D), q.shape[1], ptr(cand_offsets), ptr(cand_ids), ptr(beam_scores), B, R, ptr(al), A, k,
              0 if func == "tanh" else 1, ptr(ov), ptr(oi), max_cand, int(cand_stride), lo, hi,
-             _ffi.RERANK_POSITIONS if positions else 0,
+             (_ffi.RERANK_POSITIONS if positions else 0) | (_ffi.RERANK_CHUNKED if chunked else 0),
              ptr(ws), ws.numel(), stream_ptr()), "gdr_rerank_topk")
     return ov, oi
 
@@ -371,20 +375,23 @@ def rerank_positions_to_ids(pos, cand_ids):
 
 
 RERANK_MAX_CAND = 8192          # csrc/rerank.hip RR_MAX_CAND: the LDS sort of one (alpha, query) list
+RERANK_LONG_MAX_CAND = 1 << 20  # RR_LONG_MAX_CAND: longer lists are sorted in chunks whose first k are merged
+RERANK_CHUNK = 4096             # RR_LCH: candidate positions per chunk of the long-list select
 
 
-def block_max_cand(cand_offsets, R, stride):
+def block_max_cand(cand_offsets, R, stride, cap=RERANK_MAX_CAND):
     """The `max_cand` to hand gdr_rerank_topk for candidate blocks of width `stride` = num beams x LARGEST cluster of the
-    corpus.  While that worst case fits the kernel's cap it is used as is — nothing synchronises.  One outlier cluster
-    (more than 81 docs at 100 beams) must not make every step fail when the clusters actually decoded are small: beyond
-    the cap the bound comes from the data (one read-back of the per-query counts, this case only), and only a query that
-    REALLY has more than 8192 candidates is refused (as the host CSR path refuses it)."""
+    corpus.  While that worst case fits ONE LDS sort (8192) it is used as is — nothing synchronises.  Beyond that the bound
+    comes from the data (one read-back of the per-query counts, this case only): one outlier cluster must not push every
+    step to the long-list form, or fail it, when the clusters actually decoded are small.  Only a query that REALLY has more
+    than `cap` candidates is refused: cap=RERANK_LONG_MAX_CAND is what the rerank accepts (the retriever passes it); the
+    default keeps a caller on the one-sort form and refuses above 8192, as the host CSR path once did."""
     if stride <= RERANK_MAX_CAND:
         return max(int(stride), 1)
     real = int(cand_offsets.view(-1, R + 1)[:, R].max().item())
-    if real > RERANK_MAX_CAND:
+    if real > cap:
         raise _ffi.GdrError(f"rerank: a query decoded {real} candidate docs; the in-cluster rerank ranks at most "
-                            f"{RERANK_MAX_CAND} per query")
+                            f"{cap} per query")
     return max(real, 1)
 
 

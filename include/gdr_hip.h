@@ -309,17 +309,28 @@ int gdr_topk_merge_packed(const void* pairs, int G, int B, int k, float* out_val
  *                       int32[B][cand_stride]: what gdr_cluster_candidates emits and what ranks exchange (fixed size);
  *   alphas fp32[A]; out_val fp32[B,A,k], out_idx int32[B,A,k] (doc ids; -1 / -inf padding when a
  *   query has fewer than k candidates — the reference raises there).  func: 0 tanh, 1 sigmoid.
- *   max_cand: upper bound of any query's candidate count (num beams x largest cluster; <= 8192) — sizes the score
- *   scratch and the LDS sort buffer; candidates past it are ignored.  The CSR may live on the device only
- *   (gdr_cluster_candidates below): nothing here needs its contents on the host.
+ *   max_cand: upper bound of any query's candidate count (num beams x largest cluster; 1 <= max_cand <= 2^20) — sizes the
+ *   score scratch and the sort; candidates past it are ignored.  The CSR may live on the device only
+ *   (gdr_cluster_candidates below): nothing here needs its contents on the host.  Two regimes, same result bit for bit:
+ *     max_cand <= 8192: ONE sort of the query's list in LDS per (alpha, query); any k.
+ *     max_cand  > 8192: the list is sorted in chunks of 4096 positions, the chunks' first k are merged in rounds of up to
+ *                       8192 / k lists (the order is total: the top-k of a list is the top-k of its pieces' top-k).
+ *                       Needs k <= 1024; a larger k, or max_cand > 2^20, is GDR_EINVAL before anything is launched.
+ *   GDR_RERANK_CHUNKED takes the second form whatever max_cand is (same k <= 1024 rule): the exact A/B switch, set by
+ *   nothing in the product.
  *   Row-sharded corpus (GDR mode): D points to rows [doc_lo, doc_hi) of the corpus; candidates outside
  *   the range are skipped.  Unsharded: doc_lo = 0, doc_hi = N.  With GDR_RERANK_POSITIONS out_idx holds the candidate's
  *   POSITION in its query's list (0-based) instead of the doc id: merging the per-shard lists by "higher score, then
  *   lower position" (gdr_topk_merge_packed over B*A rows) reproduces the unsharded list bit for bit, because a
  *   candidate's score does not depend on which shard computed it.
- *   workspace: gdr_rerank_workspace_bytes(B, max_cand).
+ *   workspace: gdr_rerank_workspace_bytes(B, max_cand) — the score scratch [B][max_cand] for max_cand <= 8192; above,
+ *   also the partial lists of 8 alphas at k = 1024 (more alphas run in groups of 8, one after the other on the stream),
+ *   so the size serves any A and any legal k.  Non-decreasing in both arguments.  A call with GDR_RERANK_CHUNKED at
+ *   max_cand <= 8192 needs the partial lists too: size it with gdr_rerank_workspace_bytes(B, max(max_cand, 8193)); a
+ *   smaller workspace is GDR_ENOSPC, the message states the required size.
  * ---------------------------------------------------------------------------------------------- */
 #define GDR_RERANK_POSITIONS 1
+#define GDR_RERANK_CHUNKED 2
 size_t gdr_rerank_workspace_bytes(int B, int max_cand);
 int gdr_rerank_topk(const float* q, const float* D, int d, const int32_t* cand_offsets, const int32_t* cand_ids,
                     const float* beam_scores, int B, int R, const float* alphas, int A, int k, int func,
