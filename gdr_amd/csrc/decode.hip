@@ -28,7 +28,6 @@
 #include <vector>
 
 #include "layers.h"
-#include "decode_fused.h"
 
 namespace gdr {
 
@@ -1095,21 +1094,49 @@ static const float* w_at(const float* W, size_t elems, bool bf16) {
   return reinterpret_cast<const float*>(reinterpret_cast<const char*>(W) + elems * (bf16 ? 2 : 4));
 }
 
-// GDR_DECODE_FUSED, read once: bit mask 1 self-attention, 2 cross-attention, 4 feed-forward sub-block fused (decode_fused.hip).
-// OFF by default: measured slower than the per-phase launches at every decode shape (profiles/r06_fused_decode_ab.txt: 64 x 10 beams
-// 11.97 -> 14.55 ms, 1 x 100 6.48 -> 7.54 with all three on; the self-attention form alone is neutral at 640 rows).  Kept exact and
-// tested (test_gpu_decode_knobs.py).  The slab scratch is only part of the workspace when the knob is on.
-static int decode_fused_mask() {
-  static const int mask = [] {
-    const char* e = getenv("GDR_DECODE_FUSED");
-    return e ? atoi(e) : 0;
-  }();
-  return mask;
+// One chain of decode linears: a stream with the scratch that only launches on that stream may touch — the bf16 mode's rounded
+// operand (abf), the split-K region (skw) with its stream-K hand-off (sk) and the bf16 image of the chain's last normed rows (img).
+// m_dev: device-side row count, or null for all M rows.
+struct DecChain {
+  bool bf16;
+  void* abf;
+  float* skw;
+  hipStream_t st;
+  StreamK* sk;
+  Bf16Image* img;
+  int linear(const float* A, int64_t lda, const float* W, int64_t ldw, float* C, int64_t ldc, int64_t M, const int64_t* m_dev, int N,
+             int K, int epi, const float* bias, const float* res, int64_t ldr) const {
+    return dec_linear(bf16, abf, A, lda, W, ldw, C, ldc, M, m_dev, N, K, epi, bias, res, ldr, skw, st, sk, img);
+  }
+  int linear_norm(const float* A, int64_t lda, const float* W, int64_t ldw, float* C, int64_t ldc, int64_t M, const int64_t* m_dev,
+                  int N, int K, int epi, const float* bias, const float* res, int64_t ldr, const NormEpilogue& ne,
+                  const Bf16Image* a_img = nullptr) const {
+    return dec_linear_norm(bf16, abf, A, lda, W, ldw, C, ldc, M, m_dev, N, K, epi, bias, res, ldr, skw, st, ne, sk, img, a_img);
+  }
+  int linear_out16(const float* A, int64_t lda, const float* W, int64_t ldw, const float* C, int64_t ldc, int64_t M,
+                   const int64_t* m_dev, int N, int K, int epi, const float* bias, Bf16Image* out) const {
+    return dec_linear_out16(abf, A, lda, W, ldw, C, ldc, M, m_dev, N, K, epi, bias, st, img, out);
+  }
+};
+
+// Self-attention of a decode step: one query row per batch entry against its Lk ancestors (itself last) in a [rows][3*width] cache
+// of (q | k | v) rows, key j of entry b at cache row kv_rows[b][j].  The caller sets the output (and b_count_dev / live).
+static AttnArgs ancestor_attn(const float* q, const float* cache, int width, int heads, int B, int Lk, const int32_t* kv_rows,
+                              float scale, const float* rel_bias, int buckets, const BucketLut& lut, int causal_neg_inf) {
+  AttnArgs at{};
+  at.q = q, at.k = cache + width, at.v = cache + 2 * width;
+  at.ldq = at.ldk = at.ldv = 3 * width, at.ldo = width;
+  at.q_bstride = 1, at.k_bstride = 0, at.o_bstride = 1;
+  at.B = B, at.H = heads, at.dk = width / heads, at.Lq = 1, at.Lk = Lk, at.q_pos0 = Lk - 1, at.scale = scale;
+  at.rel_bias = rel_bias, at.bidirectional = 0, at.num_buckets = buckets, at.lut = lut;
+  at.key_mask = nullptr, at.mask_bstride = 0, at.causal = 1, at.causal_neg_inf = causal_neg_inf;
+  at.kv_rows = kv_rows, at.kv_group = 1;
+  return at;
 }
 
 // ------------------------------------------------------------------------------------------ model workspace
 struct GenWs {
-  size_t beam, dcache, acache, crosskv, xd, xa, nx, ctx, qc, ff, tmp, A, hl, splitk, ctx2, ff2, splitk2, qkv_c, abf, abf2, img1, img2, c16a, c16b, f16a, f16b, fslab, total;
+  size_t beam, dcache, acache, crosskv, xd, xa, nx, ctx, qc, ff, tmp, A, hl, splitk, ctx2, ff2, splitk2, qkv_c, abf, abf2, img1, img2, c16a, c16b, f16a, f16b, total;
 };
 
 static GenWs gen_ws(const GdrT5DecoderWeights& w, const BeamDims& bd, int L) {
@@ -1146,9 +1173,6 @@ static GenWs gen_ws(const GdrT5DecoderWeights& w, const BeamDims& bd, int L) {
   g.c16b = carve(o, 2 * rows * d);                         // producers (a: decoder chain, b: adaptor chain) — the operand of
   g.f16a = carve(o, 2 * rows * ffw);                       // the linear behind them, which then needs no cast launch
   g.f16b = carve(o, 2 * rows * (size_t)w.adaptor_ff);
-  // fused sub-blocks (decode_fused.hip, <= 1 024 rows): the partial slabs of one sub-block, per chain
-  const bool fused = decode_fused_mask() != 0 && decode_fused_rt((int64_t)rows, (int)d, (int)inner, dm.d_kv) != 0;
-  g.fslab = carve(o, fused ? decode_fused_slab_bytes((int64_t)rows, (int)d, dm.d_ff, dm.num_heads) : 0);
   g.total = o;
   return g;
 }
@@ -1221,7 +1245,7 @@ static int generate_impl(const GdrT5DecoderWeights* w, const float* enc_hidden, 
   auto F = [&](size_t off) { return reinterpret_cast<float*>(base + off); };
   float *dcache = F(g.dcache), *acache = F(g.acache), *crosskv = F(g.crosskv), *xd = F(g.xd), *xa = F(g.xa),
         *nx = F(g.nx), *ctx = F(g.ctx), *qc = F(g.qc), *ff = F(g.ff), *tmp = F(g.tmp), *A = F(g.A), *hl = F(g.hl),
-        *skw = F(g.splitk), *ctx2 = F(g.ctx2), *ff2 = F(g.ff2), *skw2 = F(g.splitk2), *qkv_c = F(g.qkv_c), *fslab = F(g.fslab);
+        *skw = F(g.splitk), *ctx2 = F(g.ctx2), *ff2 = F(g.ff2), *skw2 = F(g.splitk2), *qkv_c = F(g.qkv_c);
   void *abf = base + g.abf, *abf2 = base + g.abf2;
   Bf16Image img1{nullptr, bf16 ? base + g.img1 : nullptr}, img2{nullptr, bf16 ? base + g.img2 : nullptr};
   Bf16Image c16a{nullptr, bf16 ? base + g.c16a : nullptr}, c16b{nullptr, bf16 ? base + g.c16b : nullptr};
@@ -1242,14 +1266,6 @@ static int generate_impl(const GdrT5DecoderWeights* w, const float* enc_hidden, 
   const size_t dlayer = (size_t)max_length * dslab, alayer = (size_t)max_length * aslab;
   const size_t ckv_layer = (size_t)B * L * 2 * inner;
 
-#define LIN(A_, lda_, W_, ldw_, C_, ldc_, M_, N_, K_, epi_, bias_, res_, ldr_) \
-  dec_linear(bf16, abf, A_, lda_, W_, ldw_, C_, ldc_, M_, nullptr, N_, K_, epi_, bias_, res_, ldr_, skw, stream, &sk1, &img1)
-#define LIN2(A_, lda_, W_, ldw_, C_, ldc_, M_, N_, K_, epi_, bias_, res_, ldr_) \
-  dec_linear(bf16, abf2, A_, lda_, W_, ldw_, C_, ldc_, M_, nullptr, N_, K_, epi_, bias_, res_, ldr_, skw2, as, &sk2, &img2)
-#define LINN(A_, lda_, W_, ldw_, C_, ldc_, M_, N_, K_, epi_, bias_, res_, ldr_, ne_) \
-  dec_linear_norm(bf16, abf, A_, lda_, W_, ldw_, C_, ldc_, M_, nullptr, N_, K_, epi_, bias_, res_, ldr_, skw, stream, ne_, &sk1, &img1)
-#define LIN2N(A_, lda_, W_, ldw_, C_, ldc_, M_, md_, N_, K_, epi_, bias_, res_, ldr_, ne_) \
-  dec_linear_norm(bf16, abf2, A_, lda_, W_, ldw_, C_, ldc_, M_, md_, N_, K_, epi_, bias_, res_, ldr_, skw2, as, ne_, &sk2, &img2)
   // the decoder's normed rows `nx` feed linears only; in the bf16 mode those read the bf16 image, so the fp32 copy is not written
   // (the final norm's rows `hl` go into the fp32 head dot: kept)
   auto rms = [&](const float* wgt, float* y) {
@@ -1299,6 +1315,9 @@ static int generate_impl(const GdrT5DecoderWeights* w, const float* enc_hidden, 
   SideLease lease;
   struct { bool ok; hipStream_t s; hipEvent_t fork, join; } ss{lease.ss != nullptr, lease.ss ? lease.ss->s : nullptr,
                                                             lease.ss ? lease.ss->fork : nullptr, lease.ss ? lease.ss->join : nullptr};
+  hipStream_t as = ss.ok ? ss.s : stream;  // adaptor stream
+  // the two chains of linears: the decoder stack on the caller's stream, the adaptor on `as` — each with scratch of its own
+  const DecChain main{bf16, abf, skw, stream, &sk1, &img1}, side{bf16, abf2, skw2, as, &sk2, &img2};
   // cross-attention K/V once per query and layer (modeling_t5.py:365-368 recomputes them per beam row per step).  They
   // depend on the encoder states only: with a side stream they are projected THERE (the adaptor chain's scratch), layer by
   // layer, while the main stream already runs step 0 — a chain of small latency-bound kernels over one row per query that
@@ -1309,9 +1328,10 @@ static int generate_impl(const GdrT5DecoderWeights* w, const float* enc_hidden, 
       set_error("generate: fork to the side stream failed");
       return GDR_EHIP;
     }
+    const DecChain ckv{bf16, abf2, skw2, ss.s, &sk2, nullptr};  // the side chain before its first norm: no bf16 image yet
     for (int l = 0; l < dm.num_layers; ++l) {
-      GDR_TRY(dec_linear(bf16, abf2, enc_hidden, d, w->layers[l].wkv_c, d, crosskv + l * ckv_layer, 2 * inner, (int64_t)B * L, nullptr,
-                         2 * inner, d, GDR_EPI_NONE, nullptr, nullptr, 0, skw2, ss.s, &sk2));
+      GDR_TRY(ckv.linear(enc_hidden, d, w->layers[l].wkv_c, d, crosskv + l * ckv_layer, 2 * inner, (int64_t)B * L, nullptr, 2 * inner, d,
+                         GDR_EPI_NONE, nullptr, nullptr, 0));
       if (hipEventRecord(lease.ss->ckv[l], ss.s) != hipSuccess) {
         set_error("generate: event record on the side stream failed");
         return GDR_EHIP;
@@ -1319,11 +1339,10 @@ static int generate_impl(const GdrT5DecoderWeights* w, const float* enc_hidden, 
     }
   } else {
     for (int l = 0; l < dm.num_layers; ++l)
-      GDR_TRY(LIN(enc_hidden, d, w->layers[l].wkv_c, d, crosskv + l * ckv_layer, 2 * inner, (int64_t)B * L,
-                                2 * inner, d, GDR_EPI_NONE, nullptr, nullptr, 0));
+      GDR_TRY(main.linear(enc_hidden, d, w->layers[l].wkv_c, d, crosskv + l * ckv_layer, 2 * inner, (int64_t)B * L, nullptr, 2 * inner, d,
+                          GDR_EPI_NONE, nullptr, nullptr, 0));
   }
 
-  static const int fused_mask = decode_fused_mask();
   static const bool slab_q_on = [] {
     const char* e = getenv("GDR_DECODE_SLAB_Q");  // A/B knob: 0 = reduce the cross-attention q projection in its own launch
     return e ? atoi(e) != 0 : true;
@@ -1336,7 +1355,6 @@ static int generate_impl(const GdrT5DecoderWeights* w, const float* enc_hidden, 
       g_early_exits.fetch_add(1);
       break;
     }
-    hipStream_t as = ss.ok ? ss.s : stream;   // adaptor stream
     img1.src = img2.src = nullptr;            // the embedding kernels below rewrite nx / xa without a bf16 image
     // Step 0: the R beam rows of a query hold the same START token and the same encoder states, so their decoder /
     // adaptor / head outputs are identical rows (generation_utils.py:437-442 expands the encoder states, :663-668 starts
@@ -1356,37 +1374,6 @@ static int generate_impl(const GdrT5DecoderWeights* w, const float* enc_hidden, 
     if (!ptab) {
       GDR_TRY(launch_embed(w->dec_embed, bb.cur_tok, rows_s, d, dm.vocab_size, xa, as));
     }
-    // ---------------- adaptor: post-LN nn.TransformerDecoder over decode_embeddings(ids) (modeling_t5.py:1615-1633)
-    auto ad_layer_plain = [&](int l) -> int {
-        const GdrAdaptorLayer& al = w->alayers[l];
-        float* cache = acache + l * alayer;
-        float* slot = cache + s * aslab;
-        GDR_TRY(LIN2(xa, d, al.in_w, d, slot, 3 * d, rows_s, 3 * d, d, GDR_EPI_BIAS, al.in_b, nullptr, 0));
-        AttnArgs at{};
-        at.q = slot, at.k = cache + d, at.v = cache + 2 * d;
-        ctx_to(at, c16b, ctx2);
-        at.ldq = at.ldk = at.ldv = 3 * d, at.ldo = d;
-        at.q_bstride = 1, at.k_bstride = 0, at.o_bstride = 1;
-        at.B = rows_s, at.H = aH, at.dk = ahd, at.Lq = 1, at.Lk = s + 1, at.q_pos0 = s;
-        at.scale = 1.0f / sqrtf((float)ahd);
-        at.rel_bias = nullptr, at.bidirectional = 0, at.num_buckets = 0, at.lut = lut_uni;
-        at.key_mask = nullptr, at.mask_bstride = 0, at.causal = 1, at.causal_neg_inf = 1;
-        at.kv_rows = bb.kv_rows, at.kv_group = 1;
-        GDR_TRY(launch_attention(at, as));
-        // tmp = norm2(norm1(out_proj(ctx) + xa) + cross_const); xa = norm3(lin2(relu(lin1(tmp))) + tmp)
-        GDR_TRY(dec_linear_norm(bf16, abf2, ctx2, d, al.out_w, d, tmp, d, rows_s, nullptr, d, d, GDR_EPI_BIAS_RESIDUAL, al.out_b, xa, d,
-                                skw2, as, ln2(al, tmp), &sk2, &img2, &c16b));
-        int r16 = bf16 ? dec_linear_out16(abf2, tmp, d, al.lin1_w, d, ff2, aff, rows_s, nullptr, aff, d, GDR_EPI_BIAS_RELU, al.lin1_b, as,
-                                          &img2, &f16b) : 1;
-        if (r16 < 0) return r16;
-        if (r16 == 1) {
-          f16b.src = nullptr;
-          GDR_TRY(LIN2(tmp, d, al.lin1_w, d, ff2, aff, rows_s, aff, d, GDR_EPI_BIAS_RELU, al.lin1_b, nullptr, 0));
-        }
-        GDR_TRY(dec_linear_norm(bf16, abf2, ff2, aff, al.lin2_w, aff, xa, d, rows_s, nullptr, d, aff, GDR_EPI_BIAS_RESIDUAL, al.lin2_b, tmp,
-                                d, skw2, as, ln(al.ln3_w, al.ln3_b, xa), &sk2, &img2, &f16b));
-        return GDR_OK;
-    };
     // prefix-table mode, steps at which every possible prefix is a table node (step 0: the root; deeper while the trie's
     // levels are complete, GdrPrefixTable.complete_levels): the adaptor chain and the head GEMM would run over zero rows
     // (34 launches per step that exit at once — 0.2 ms of the side queue and, at one query x 100 beams, of the host's time)
@@ -1406,89 +1393,52 @@ static int generate_impl(const GdrT5DecoderWeights* w, const float* enc_hidden, 
         GDR_CHECK_LAUNCH("embed_rows_kernel");
       }
     }
-#define LIN2D(A_, lda_, W_, ldw_, C_, ldc_, N_, K_, epi_, bias_, res_, ldr_) \
-  dec_linear(bf16, abf2, A_, lda_, W_, ldw_, C_, ldc_, rows_s, nm, N_, K_, epi_, bias_, res_, ldr_, skw2, as, &sk2, &img2)
-    auto ad_layer_tab = [&](int l) -> int {
-        const GdrAdaptorLayer& al = w->alayers[l];
-        float* cache = acache + l * alayer;
-        float* slot = cache + s * aslab;
-        GDR_TRY(LIN2D(xa, d, al.in_w, d, qkv_c, 3 * d, 3 * d, d, GDR_EPI_BIAS, al.in_b, nullptr, 0));
+    // ---------------- adaptor: post-LN nn.TransformerDecoder over decode_embeddings(ids) (modeling_t5.py:1615-1633)
+    const bool tab = ptab != nullptr;  // the compacted rows: (q,k,v) into qkv_c and from there to their cache slots; *nm rows
+    auto ad_layer = [&](int l) -> int {
+      const GdrAdaptorLayer& al = w->alayers[l];
+      float* cache = acache + l * alayer;
+      float* slot = cache + s * aslab;
+      float* qkv = tab ? qkv_c : slot;
+      const int64_t* m_dev = tab ? nm : nullptr;
+      GDR_TRY(side.linear(xa, d, al.in_w, d, qkv, 3 * d, rows_s, m_dev, 3 * d, d, GDR_EPI_BIAS, al.in_b, nullptr, 0));
+      if (tab) {
         hipLaunchKernelGGL(scatter_slot_kernel, dim3((unsigned)((rows_s + 3) / 4)), dim3(256), 0, as, qkv_c, bb.miss_rows, nm,
                            3 * d / 4, d / 4, slot);
         GDR_CHECK_LAUNCH("scatter_slot_kernel");
-        AttnArgs at{};
-        at.q = qkv_c, at.k = cache + d, at.v = cache + 2 * d;
-        ctx_to(at, c16b, ctx2);
-        at.ldq = at.ldk = at.ldv = 3 * d, at.ldo = d;
-        at.q_bstride = 1, at.k_bstride = 0, at.o_bstride = 1;
-        at.B = rows_s, at.H = aH, at.dk = ahd, at.Lq = 1, at.Lk = s + 1, at.q_pos0 = s;
-        at.scale = 1.0f / sqrtf((float)ahd);
-        at.rel_bias = nullptr, at.bidirectional = 0, at.num_buckets = 0, at.lut = lut_uni;
-        at.key_mask = nullptr, at.mask_bstride = 0, at.causal = 1, at.causal_neg_inf = 1;
-        at.kv_rows = bb.kv_rows_c, at.kv_group = 1, at.b_count_dev = nm;
-        GDR_TRY(launch_attention(at, as));
-        GDR_TRY(dec_linear_norm(bf16, abf2, ctx2, d, al.out_w, d, tmp, d, rows_s, nm, d, d, GDR_EPI_BIAS_RESIDUAL, al.out_b, xa, d, skw2,
-                                as, ln2(al, tmp), &sk2, &img2, &c16b));
-        int r16 = bf16 ? dec_linear_out16(abf2, tmp, d, al.lin1_w, d, ff2, aff, rows_s, nm, aff, d, GDR_EPI_BIAS_RELU, al.lin1_b, as, &img2,
-                                          &f16b) : 1;
-        if (r16 < 0) return r16;
-        if (r16 == 1) {
-          f16b.src = nullptr;
-          GDR_TRY(LIN2D(tmp, d, al.lin1_w, d, ff2, aff, aff, d, GDR_EPI_BIAS_RELU, al.lin1_b, nullptr, 0));
-        }
-        GDR_TRY(dec_linear_norm(bf16, abf2, ff2, aff, al.lin2_w, aff, xa, d, rows_s, nm, d, aff, GDR_EPI_BIAS_RESIDUAL, al.lin2_b, tmp, d,
-                                skw2, as, ln(al.ln3_w, al.ln3_b, xa), &sk2, &img2, &f16b));
-        return GDR_OK;
+      }
+      AttnArgs at = ancestor_attn(qkv, cache, d, aH, rows_s, s + 1, tab ? bb.kv_rows_c : bb.kv_rows, 1.0f / sqrtf((float)ahd), nullptr, 0,
+                                  lut_uni, 1);
+      at.b_count_dev = m_dev;
+      ctx_to(at, c16b, ctx2);
+      GDR_TRY(launch_attention(at, as));
+      // tmp = norm2(norm1(out_proj(ctx) + xa) + cross_const); xa = norm3(lin2(relu(lin1(tmp))) + tmp)
+      GDR_TRY(side.linear_norm(ctx2, d, al.out_w, d, tmp, d, rows_s, m_dev, d, d, GDR_EPI_BIAS_RESIDUAL, al.out_b, xa, d, ln2(al, tmp),
+                               &c16b));
+      int r16 = bf16 ? side.linear_out16(tmp, d, al.lin1_w, d, ff2, aff, rows_s, m_dev, aff, d, GDR_EPI_BIAS_RELU, al.lin1_b, &f16b) : 1;
+      if (r16 < 0) return r16;
+      if (r16 == 1) {
+        f16b.src = nullptr;
+        GDR_TRY(side.linear(tmp, d, al.lin1_w, d, ff2, aff, rows_s, m_dev, aff, d, GDR_EPI_BIAS_RELU, al.lin1_b, nullptr, 0));
+      }
+      GDR_TRY(side.linear_norm(ff2, aff, al.lin2_w, aff, xa, d, rows_s, m_dev, d, aff, GDR_EPI_BIAS_RESIDUAL, al.lin2_b, tmp, d,
+                               ln(al.ln3_w, al.ln3_b, xa), &f16b));
+      return GDR_OK;
     };
     // ---------------- T5 decoder stack (modeling_t5.py:498-584, 685-821)
     auto dec_layer = [&](int l) -> int {
       const GdrT5DecLayer& ly = w->layers[l];
       float* cache = dcache + l * dlayer;
       float* slot = cache + s * dslab;
-      // fused sub-blocks (decode_fused.hip): <= 1 024 rows, fp32, d_kv = 64 — (row panel, head / d_ff chunk) workgroups write
-      // partial slabs, one reduction launch folds them with the residual and the next norm
-      const int frt = (!bf16 && s + 1 <= 16 && dm.d_ff % 256 == 0) ? decode_fused_rt(rows_s, d, inner, dk) : 0;
-      const bool f_sa = frt && (fused_mask & 1), f_ca = frt && (fused_mask & 2) && R_s > 1, f_ff = frt && (fused_mask & 4);
-      FusedArgs fa{};
-      fa.X = nx, fa.slabs = fslab, fa.M = rows_s, fa.d = d, fa.live = sk1.live, fa.H = H, fa.q_pos0 = s, fa.scale = 1.0f;
-      fa.num_buckets = dm.rel_buckets;
-      if (f_sa) {
-        FusedArgs g1 = fa;
-        g1.W1 = ly.wqkv, g1.w1_seg_stride = inner, g1.w1_slice_rows = 64, g1.W3 = ly.wo, g1.ld3 = inner, g1.n_slices = H;
-        g1.slot = slot, g1.kbase = cache + inner, g1.vbase = cache + 2 * inner, g1.ld_kv = 3 * inner, g1.k_off = inner, g1.v_off = 2 * inner;
-        g1.kv_rows = bb.kv_rows, g1.Lk = s + 1, g1.rel_bias = w->self_rel_bias, g1.lut = lut_uni;
-        GDR_TRY(launch_decode_fused(FUSED_SA, g1, frt, 192, stream));
-        GDR_TRY(launch_slab_reduce_norm(fslab, H, rows_s, d, xd, d, nullptr, xd, d, rms(ly.ln_cross, nx), sk1.live, stream));
-      } else {
       // every later RMS norm rides on the reduction of the residual linear in front of it (dec_linear_norm)
       // (the first block's norm rides on the embedding launch: embed_rmsnorm_kernel)
-      GDR_TRY(LIN(nx, d, ly.wqkv, d, slot, 3 * inner, rows_s, 3 * inner, d, GDR_EPI_NONE, nullptr, nullptr, 0));
-      AttnArgs at{};
-      at.q = slot, at.k = cache + inner, at.v = cache + 2 * inner;
+      GDR_TRY(main.linear(nx, d, ly.wqkv, d, slot, 3 * inner, rows_s, nullptr, 3 * inner, d, GDR_EPI_NONE, nullptr, nullptr, 0));
+      AttnArgs at = ancestor_attn(slot, cache, inner, H, rows_s, s + 1, bb.kv_rows, 1.0f, w->self_rel_bias, dm.rel_buckets, lut_uni, 0);
       ctx_to(at, c16a, ctx);
-      at.ldq = at.ldk = at.ldv = 3 * inner, at.ldo = inner;
-      at.q_bstride = 1, at.k_bstride = 0, at.o_bstride = 1;
-      at.B = rows_s, at.H = H, at.dk = dk, at.Lq = 1, at.Lk = s + 1, at.q_pos0 = s, at.scale = 1.0f;
-      at.rel_bias = w->self_rel_bias, at.bidirectional = 0, at.num_buckets = dm.rel_buckets, at.lut = lut_uni;
-      at.key_mask = nullptr, at.mask_bstride = 0, at.causal = 1, at.causal_neg_inf = 0;
-      at.kv_rows = bb.kv_rows, at.kv_group = 1;
       GDR_TRY(launch_attention(at, stream));
-      GDR_TRY(dec_linear_norm(bf16, abf, ctx, inner, ly.wo, inner, xd, d, rows_s, nullptr, d, inner, GDR_EPI_RESIDUAL, nullptr, xd, d, skw,
-                              stream, rms(ly.ln_cross, nx), &sk1, &img1, &c16a));
-      }
+      GDR_TRY(main.linear_norm(ctx, inner, ly.wo, inner, xd, d, rows_s, nullptr, d, inner, GDR_EPI_RESIDUAL, nullptr, xd, d,
+                               rms(ly.ln_cross, nx), &c16a));
       // cross attention over the encoder states of the row's query
-      if (f_ca) {
-        FusedArgs g2 = fa;
-        g2.W1 = ly.wq_c, g2.w1_seg_stride = 0, g2.w1_slice_rows = 64, g2.W3 = ly.wo_c, g2.ld3 = inner, g2.n_slices = H;
-        g2.ck = crosskv + l * ckv_layer, g2.cv = crosskv + l * ckv_layer + inner, g2.ld_c = 2 * inner, g2.L = L, g2.R = R_s;
-        g2.key_mask = enc_mask, g2.rel_bias = w->cross_rel_bias, g2.lut = lut_bi;
-        if (s == 0 && ckv_side && hipStreamWaitEvent(stream, lease.ss->ckv[l], 0) != hipSuccess) {
-          set_error("generate: wait for the cross K/V of layer %d failed", l);
-          return GDR_EHIP;
-        }
-        GDR_TRY(launch_decode_fused(FUSED_CA, g2, frt, 64, stream));
-        GDR_TRY(launch_slab_reduce_norm(fslab, H, rows_s, d, xd, d, nullptr, xd, d, rms(ly.ln_ff, nx), sk1.live, stream));
-      } else {
       // the q projection's split-K slabs go to the attention kernel un-reduced (it sums them while it stages the beam rows_s'
       // queries): one dependent launch less per layer and step
       SlabRef qsl{nullptr, 1, 0};
@@ -1500,7 +1450,7 @@ static int generate_impl(const GdrT5DecoderWeights* w, const float* enc_hidden, 
         if (rc_ < 0) return rc_;
         q_from_slabs = rc_ == 0;
       }
-      if (!q_from_slabs) GDR_TRY(LIN(nx, d, ly.wq_c, d, qc, inner, rows_s, inner, d, GDR_EPI_NONE, nullptr, nullptr, 0));
+      if (!q_from_slabs) GDR_TRY(main.linear(nx, d, ly.wq_c, d, qc, inner, rows_s, nullptr, inner, d, GDR_EPI_NONE, nullptr, nullptr, 0));
       AttnArgs ca{};
       const float* ckv = crosskv + l * ckv_layer;
       // the R beam rows_s of a query are consecutive and share its K/V: one workgroup per (query, head) stages K/V
@@ -1519,35 +1469,24 @@ static int generate_impl(const GdrT5DecoderWeights* w, const float* enc_hidden, 
         return GDR_EHIP;
       }
       GDR_TRY(launch_attention(ca, stream));
-      GDR_TRY(dec_linear_norm(bf16, abf, ctx, inner, ly.wo_c, inner, xd, d, rows_s, nullptr, d, inner, GDR_EPI_RESIDUAL, nullptr, xd, d, skw,
-                              stream, rms(ly.ln_ff, nx), &sk1, &img1, &c16a));
-      }
+      GDR_TRY(main.linear_norm(ctx, inner, ly.wo_c, inner, xd, d, rows_s, nullptr, d, inner, GDR_EPI_RESIDUAL, nullptr, xd, d,
+                               rms(ly.ln_ff, nx), &c16a));
       const bool last = l + 1 == dm.num_layers;  // the norm behind the block: the next block's first, or final_layer_norm
-      if (f_ff) {
-        FusedArgs g3 = fa;
-        const int n1 = frt == 1 ? 128 : 256;
-        g3.W1 = ly.wi, g3.w1_seg_stride = 0, g3.w1_slice_rows = n1, g3.W3 = ly.wo_ff, g3.ld3 = dm.d_ff, g3.n_slices = dm.d_ff / n1;
-        GDR_TRY(launch_decode_fused(FUSED_FFN, g3, frt, n1, stream));
-        GDR_TRY(launch_slab_reduce_norm(fslab, dm.d_ff / n1, rows_s, d, xd, d, nullptr, xd, d,
-                                        rms(last ? w->final_ln : w->layers[l + 1].ln_self, last ? hl : nx), sk1.live, stream));
-        return GDR_OK;
-      }
-      int r16 = bf16 ? dec_linear_out16(abf, nx, d, ly.wi, d, ff, dm.d_ff, rows_s, nullptr, dm.d_ff, d, GDR_EPI_RELU, nullptr, stream, &img1,
-                                        &f16a) : 1;
+      int r16 = bf16 ? main.linear_out16(nx, d, ly.wi, d, ff, dm.d_ff, rows_s, nullptr, dm.d_ff, d, GDR_EPI_RELU, nullptr, &f16a) : 1;
       if (r16 < 0) return r16;
       if (r16 == 1) {
-          f16a.src = nullptr;
-          GDR_TRY(LIN(nx, d, ly.wi, d, ff, dm.d_ff, rows_s, dm.d_ff, d, GDR_EPI_RELU, nullptr, nullptr, 0));
-        }
-      GDR_TRY(dec_linear_norm(bf16, abf, ff, dm.d_ff, ly.wo_ff, dm.d_ff, xd, d, rows_s, nullptr, d, dm.d_ff, GDR_EPI_RESIDUAL, nullptr, xd, d,
-                              skw, stream, rms(last ? w->final_ln : w->layers[l + 1].ln_self, last ? hl : nx), &sk1, &img1, &f16a));
+        f16a.src = nullptr;
+        GDR_TRY(main.linear(nx, d, ly.wi, d, ff, dm.d_ff, rows_s, nullptr, dm.d_ff, d, GDR_EPI_RELU, nullptr, nullptr, 0));
+      }
+      GDR_TRY(main.linear_norm(ff, dm.d_ff, ly.wo_ff, dm.d_ff, xd, d, rows_s, nullptr, d, dm.d_ff, GDR_EPI_RESIDUAL, nullptr, xd, d,
+                               rms(last ? w->final_ln : w->layers[l + 1].ln_self, last ? hl : nx), &f16a));
       return GDR_OK;
     };
     // The two chains are enqueued layer by layer in turn: a host thread that first enqueued the whole adaptor chain left
     // the main stream idle for as long as those ~55 launches take to issue (measured: a fifth of a 100-beam step).
     for (int l = 0; l < dm.num_layers || l < w->adaptor_layers; ++l) {
       if (l < dm.num_layers) GDR_TRY(dec_layer(l));
-      if (l < w->adaptor_layers && !adaptor_idle) GDR_TRY(ptab ? ad_layer_tab(l) : ad_layer_plain(l));
+      if (l < w->adaptor_layers && !adaptor_idle) GDR_TRY(ad_layer(l));
     }
     // bf16 mode from ~1 000 beam rows on: the head GEMM waits for the decoder stack and takes the dot with its hidden state in its own
     // epilogue (launch_linear_bf16_headdot) instead of writing rows x (V+1) x d floats for head_logits to read back (1.46 GB per step at
@@ -1561,9 +1500,8 @@ static int generate_impl(const GdrT5DecoderWeights* w, const float* enc_hidden, 
     }();
     const bool fuse_head = bf16 && ptab && !adaptor_idle && head_dot_on && rows_s >= HEAD_DOT_ROWS && d % 128 == 0;
     if (ptab && !adaptor_idle && !fuse_head)  // the head GEMM of the compacted rows belongs to the adaptor chain (it needs nothing from the decoder stack)
-      GDR_TRY(LIN2D(xa, d, w_at(w->head_w, (size_t)s * V1 * d * d, bf16), d, A, (int64_t)V1 * d, V1 * d, d, GDR_EPI_NONE, nullptr,
-                    nullptr, 0));
-#undef LIN2D
+      GDR_TRY(side.linear(xa, d, w_at(w->head_w, (size_t)s * V1 * d * d, bf16), d, A, (int64_t)V1 * d, rows_s, nm, V1 * d, d, GDR_EPI_NONE,
+                          nullptr, nullptr, 0));
     if (ss.ok) {
       if (hipEventRecord(ss.join, ss.s) != hipSuccess) {
         set_error("generate: adaptor stream join failed");
@@ -1578,7 +1516,7 @@ static int generate_impl(const GdrT5DecoderWeights* w, const float* enc_hidden, 
     const float* hw = w_at(w->head_w, (size_t)s * V1 * d * d, bf16);
     const float* he = w->head_e + (size_t)s * V1 * d;
     if (!ptab) {
-      GDR_TRY(LIN(xa, d, hw, d, A, (int64_t)V1 * d, rows_s, V1 * d, d, GDR_EPI_NONE, nullptr, nullptr, 0));
+      GDR_TRY(main.linear(xa, d, hw, d, A, (int64_t)V1 * d, rows_s, nullptr, V1 * d, d, GDR_EPI_NONE, nullptr, nullptr, 0));
       const int64_t items = (int64_t)rows_s * V1;
       hipLaunchKernelGGL(head_logits_kernel, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, stream, hl, A, he, rows_s, V1, d,
                          1.0f / sqrtf((float)d), bb.logits, bb.live_gate);
@@ -1596,9 +1534,11 @@ static int generate_impl(const GdrT5DecoderWeights* w, const float* enc_hidden, 
         if (rc_ < 0) return rc_;
         if (rc_ == 0)
           partial = A;
-        else  // shape not served: the plain form, now behind the join
-          GDR_TRY(dec_linear(bf16, abf2, xa, d, hw, d, A, (int64_t)V1 * d, rows_s, nm, V1 * d, d, GDR_EPI_NONE, nullptr, nullptr, 0, skw2,
-                             stream, &sk2, &img2));
+        else {  // shape not served: the plain form, now behind the join — the side chain's scratch, the caller's stream
+          DecChain joined = side;
+          joined.st = stream;
+          GDR_TRY(joined.linear(xa, d, hw, d, A, (int64_t)V1 * d, rows_s, nm, V1 * d, d, GDR_EPI_NONE, nullptr, nullptr, 0));
+        }
       }
       const int64_t items = (int64_t)rows_s * V1;
       hipLaunchKernelGGL(head_logits_table_kernel, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, stream, hl, A, he, ptab->W,
@@ -1611,10 +1551,6 @@ static int generate_impl(const GdrT5DecoderWeights* w, const float* enc_hidden, 
   }
   return beam_end(bb, bd, max_length, cur, out_ids, out_len, out_scores, stream);
 #undef GDR_TRY
-#undef LIN
-#undef LIN2
-#undef LINN
-#undef LIN2N
 }
 }  // namespace gdr
 
@@ -1706,8 +1642,7 @@ static int table_build_impl(const GdrT5DecoderWeights* w, int n_levels, const in
   const size_t layer_stride = (size_t)n_table * 3 * d;
   const BucketLut lut = make_bucket_lut(dm.rel_buckets, dm.rel_max_distance);
   int rc;
-#define TLIN(A_, lda_, W_, ldw_, C_, ldc_, M_, N_, K_, epi_, bias_, res_, ldr_) \
-  dec_linear(bf16, abf, A_, lda_, W_, ldw_, C_, ldc_, M_, nullptr, N_, K_, epi_, bias_, res_, ldr_, skw, stream)
+  const DecChain chain{bf16, abf, skw, stream, nullptr, nullptr};
 #define T_TRY(x)              \
   do {                        \
     if ((rc = (x))) return rc; \
@@ -1720,30 +1655,22 @@ static int table_build_impl(const GdrT5DecoderWeights* w, int n_levels, const in
       const GdrAdaptorLayer& al = w->alayers[l];
       float* tab = kv + l * layer_stride;       // [n_table][3d] of this layer
       float* slot = tab + (size_t)lo * 3 * d;   // this level's rows
-      T_TRY(TLIN(xa, d, al.in_w, d, slot, 3 * d, n, 3 * d, d, GDR_EPI_BIAS, al.in_b, nullptr, 0));
-      AttnArgs at{};
-      at.q = slot, at.k = tab + d, at.v = tab + 2 * d, at.out = ctx;
-      at.ldq = at.ldk = at.ldv = 3 * d, at.ldo = d;
-      at.q_bstride = 1, at.k_bstride = 0, at.o_bstride = 1;
-      at.B = n, at.H = aH, at.dk = ahd, at.Lq = 1, at.Lk = s + 1, at.q_pos0 = s;
-      at.scale = 1.0f / sqrtf((float)ahd);
-      at.rel_bias = nullptr, at.bidirectional = 0, at.num_buckets = 0, at.lut = lut;
-      at.key_mask = nullptr, at.mask_bstride = 0, at.causal = 1, at.causal_neg_inf = 1;
-      at.kv_rows = node_anc + anc_off, at.kv_group = 1;
+      T_TRY(chain.linear(xa, d, al.in_w, d, slot, 3 * d, n, nullptr, 3 * d, d, GDR_EPI_BIAS, al.in_b, nullptr, 0));
+      AttnArgs at = ancestor_attn(slot, tab, d, aH, n, s + 1, node_anc + anc_off, 1.0f / sqrtf((float)ahd), nullptr, 0, lut, 1);
+      at.out = ctx;
       T_TRY(launch_attention(at, stream));
-      T_TRY(TLIN(ctx, d, al.out_w, d, tmp, d, n, d, d, GDR_EPI_BIAS_RESIDUAL, al.out_b, xa, d));
+      T_TRY(chain.linear(ctx, d, al.out_w, d, tmp, d, n, nullptr, d, d, GDR_EPI_BIAS_RESIDUAL, al.out_b, xa, d));
       T_TRY(launch_layernorm(tmp, al.ln1_w, al.ln1_b, xa, n, d, w->adaptor_eps, nullptr, stream));
       T_TRY(launch_layernorm(xa, al.ln2_w, al.ln2_b, tmp, n, d, w->adaptor_eps, al.cross_const, stream));
-      T_TRY(TLIN(tmp, d, al.lin1_w, d, ff, aff, n, aff, d, GDR_EPI_BIAS_RELU, al.lin1_b, nullptr, 0));
-      T_TRY(TLIN(ff, aff, al.lin2_w, aff, xa, d, n, d, aff, GDR_EPI_BIAS_RESIDUAL, al.lin2_b, tmp, d));
+      T_TRY(chain.linear(tmp, d, al.lin1_w, d, ff, aff, n, nullptr, aff, d, GDR_EPI_BIAS_RELU, al.lin1_b, nullptr, 0));
+      T_TRY(chain.linear(ff, aff, al.lin2_w, aff, xa, d, n, nullptr, d, aff, GDR_EPI_BIAS_RESIDUAL, al.lin2_b, tmp, d));
       T_TRY(launch_layernorm(xa, al.ln3_w, al.ln3_b, xa, n, d, w->adaptor_eps, nullptr, stream));
     }
     // W[node][c][i] = sum_k xa[node][k] * head_w[s][c][i][k] + head_e[s][c][i]      (modeling_t5.py:1634-1639)
-    T_TRY(TLIN(xa, d, w_at(w->head_w, (size_t)s * V1 * d * d, bf16), d, W + (size_t)lo * V1 * d, (int64_t)V1 * d, n, V1 * d, d,
-               GDR_EPI_BIAS, w->head_e + (size_t)s * V1 * d, nullptr, 0));
+    T_TRY(chain.linear(xa, d, w_at(w->head_w, (size_t)s * V1 * d * d, bf16), d, W + (size_t)lo * V1 * d, (int64_t)V1 * d, n, nullptr, V1 * d,
+                       d, GDR_EPI_BIAS, w->head_e + (size_t)s * V1 * d, nullptr, 0));
     anc_off += (size_t)n * (s + 1);
   }
-#undef TLIN
 #undef T_TRY
   return GDR_OK;
 }
