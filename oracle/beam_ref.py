@@ -39,11 +39,11 @@ class BeamHypotheses:
         return self.worst_score >= cur_score
 
 
-def trie_mask(input_ids, decode_tree, vocab_size):
+def trie_mask(input_ids, decode_tree, vocab_size, dtype=torch.float32):
     """The trie constraint of the un-imported earlier generation_utils_previous.py:714-729 (NCI semantics, `--tree 1`):
     -inf on every token that is not a child of the node reached by the row's prefix; a prefix that left the tree may
     only emit EOS.  `decode_tree` is a nested dict {token: subtree} (the reference's Node.children)."""
-    mask = torch.full((input_ids.shape[0], vocab_size), float("-inf"))
+    mask = torch.full((input_ids.shape[0], vocab_size), float("-inf"), dtype=dtype)
     for i in range(input_ids.shape[0]):
         cur = decode_tree
         for value in input_ids[i, 1:].tolist():
@@ -73,7 +73,7 @@ def beam_search(step_fn, batch_size, num_beams, vocab_size, max_length, length_p
                 num_return_sequences=None, eos_token_id=1, pad_token_id=0, start_token_id=0,
                 trace=None, decode_tree=None, prefix_trace=None):
     """step_fn(seq int64[B*R, cur_len]) -> next-token logits fp32[B*R, vocab_size] (last position,
-    positional mask already applied).  Returns (decoded int64[B*nret, <=max_length], scores list[float]).
+    positional mask already applied; float64 logits are ranked and summed in float64).  Returns (decoded int64[B*nret, <=max_length], scores list[float]).
     ``trace`` (a list) receives per step (top_scores[B,2R], top_tokens[B,2R]) for golden comparison; ``prefix_trace`` (a
     list) the beams' token prefixes int64[B*R, cur_len] as they stand BEFORE that step — together they let a test explain why a
     hypothesis is absent from the final list (which cut it fell at, and by how much)."""
@@ -88,9 +88,10 @@ def beam_search(step_fn, batch_size, num_beams, vocab_size, max_length, length_p
     cur_len = 1
     while cur_len < max_length:                                           # :676
         logits = step_fn(input_ids)
+        beam_scores = beam_scores.to(logits.dtype)                        # float64 logits keep their width (0 and -1e9 are exact in both)
         scores = F.log_softmax(logits, dim=-1)                            # :698
         if decode_tree is not None:                                       # generation_utils_previous.py:714-729
-            scores = scores + trie_mask(input_ids, decode_tree, vocab_size)
+            scores = scores + trie_mask(input_ids, decode_tree, vocab_size, scores.dtype)
         next_scores = (scores + beam_scores[:, None]).view(batch_size, R * vocab_size)
         next_scores, next_tokens = torch.topk(next_scores, 2 * R, dim=1, largest=True, sorted=True)  # :775
         if trace is not None:

@@ -19,7 +19,8 @@ def gelu(x):
 
 
 def _r16(t):
-    return t.to(torch.bfloat16).to(torch.float32)
+    """Round to bf16 (nearest even), kept in t's own dtype: under a float64 state_dict only the accumulation widens."""
+    return t.to(torch.bfloat16).to(t.dtype)
 
 
 def bert_forward(sd, bcfg, input_ids, attention_mask, token_type_ids=None, bf16=False):
@@ -27,7 +28,9 @@ def bert_forward(sd, bcfg, input_ids, attention_mask, token_type_ids=None, bf16=
     bf16=True emulates the rounding points of gdr_bert_encoder_forward_ragged_bf16 (the reference has no such mode: this is the
     build's own definition of it, "parity unpinned"): every linear rounds its activation and weight operands to bf16 (RNE) and
     accumulates in fp32; q, k, v are emitted as bf16 (q already scaled by 1/sqrt(dh), an exact power of two at dh = 64);
-    embeddings, biases, LayerNorm, softmax and the residual stream stay fp32."""
+    embeddings, biases, LayerNorm, softmax and the residual stream stay fp32.
+    Every tensor follows the dtype of the weights: a float64 state_dict gives float64 end to end (bf16=True keeps its rounding
+    points and sums in float64)."""
     d, H, eps = bcfg["hidden_size"], bcfg["num_heads"], bcfg["eps"]
     dh = d // H
     B, L = input_ids.shape
@@ -37,7 +40,7 @@ def bert_forward(sd, bcfg, input_ids, attention_mask, token_type_ids=None, bf16=
     x = sd[e + "word_embeddings.weight"][input_ids] + sd[e + "position_embeddings.weight"][torch.arange(L)][None] \
         + sd[e + "token_type_embeddings.weight"][token_type_ids]
     x = F.layer_norm(x, (d,), sd[e + "LayerNorm.weight"], sd[e + "LayerNorm.bias"], eps)
-    ext = (1.0 - attention_mask[:, None, None, :].to(torch.float32)) * -1e9
+    ext = (1.0 - attention_mask[:, None, None, :].to(x.dtype)) * -1e9
 
     def heads(t):
         return t.view(B, L, H, dh).permute(0, 2, 1, 3)

@@ -4,6 +4,9 @@ Every function cites the reference lines it restates (paths relative to
 /root/reference/GDR_model/transformers/).  Plain torch-CPU fp32 ops in the reference's order;
 weights come in as a ``state_dict`` with the reference's key names.
 Pinned by tests/golden/*.npz generated from the imported reference (tests/golden/make_golden.py).
+
+Every tensor made here takes the dtype of the weights: a float64 state_dict gives float64 end to end (the higher-precision
+reference of tests/peaked.py), a float32 one the reference's own fp32 arithmetic, bit for bit.
 """
 import math
 
@@ -40,9 +43,22 @@ def compute_bias(qlen, klen, table, bidirectional, num_buckets=32):
 
 
 # --------------------------------------------------------------------------- layers
+def _f32_or_wider(x):
+    return x if x.dtype == torch.float64 else x.to(torch.float32)
+
+
+def _softmax(scores):
+    return F.softmax(_f32_or_wider(scores), dim=-1).type_as(scores)
+
+
+def _r16(t):
+    """Round to bf16 (nearest even), kept in t's own dtype: the rounding point stays, the sum that follows is as wide as t."""
+    return t.to(torch.bfloat16).to(t.dtype)
+
+
 def t5_layer_norm(x, w, eps=1e-6):
-    """modeling_t5.py:164-171 (RMS norm: fp32 variance, no mean subtraction, no bias)."""
-    variance = x.to(torch.float32).pow(2).mean(-1, keepdim=True)
+    """modeling_t5.py:164-171 (RMS norm: fp32 variance, no mean subtraction, no bias; float64 stays float64)."""
+    variance = _f32_or_wider(x).pow(2).mean(-1, keepdim=True)
     x = x / torch.sqrt(variance + eps)
     return w * x
 
@@ -53,7 +69,7 @@ GEMM_BF16 = False   # set by bf16_linears(): emulate the C5 precision mode (line
 class bf16_linears:
     """Context manager: every T5 linear rounds its activation and weight operands to bf16 (round-to-nearest-even) and
     accumulates in fp32 — what gdr_t5_encoder_forward_bf16 computes.  Norms, softmax, QK^T / PV and the residual
-    stream stay fp32."""
+    stream stay fp32.  Under a float64 state_dict the rounding points are the same and every sum is float64."""
 
     def __enter__(self):
         global GEMM_BF16
@@ -66,7 +82,7 @@ class bf16_linears:
 
 def _lin(x, w):
     if GEMM_BF16:
-        x, w = x.to(torch.bfloat16).to(torch.float32), w.to(torch.bfloat16).to(torch.float32)
+        x, w = _r16(x), _r16(w)
     return x @ w.T
 
 
@@ -77,7 +93,7 @@ def t5_attention(x, kv, sd, prefix, H, dk, position_bias, round_qkv=False):
 
     def shape(t):
         if round_qkv:
-            t = t.to(torch.bfloat16).to(torch.float32)
+            t = _r16(t)
         return t.view(bs, -1, H, dk).transpose(1, 2)
 
     q = shape(_lin(x, sd[prefix + ".q.weight"]))
@@ -86,7 +102,7 @@ def t5_attention(x, kv, sd, prefix, H, dk, position_bias, round_qkv=False):
     v = shape(_lin(src, sd[prefix + ".v.weight"]))
     scores = torch.matmul(q, k.transpose(3, 2))
     scores = scores + position_bias
-    weights = F.softmax(scores.float(), dim=-1).type_as(scores)
+    weights = _softmax(scores)
     ctx = torch.matmul(weights, v).transpose(1, 2).contiguous().view(bs, -1, H * dk)
     return _lin(ctx, sd[prefix + ".o.weight"])
 
@@ -102,7 +118,7 @@ def encoder_forward(sd, cfg, input_ids, attention_mask, return_bias=False):
     H, dk, eps = cfg.num_heads, cfg.d_kv, cfg.layer_norm_epsilon
     h = sd["shared.weight"][input_ids]                                    # :725
     L = input_ids.shape[1]
-    ext = (1.0 - attention_mask[:, None, None, :].to(torch.float32)) * -1e9   # modeling_utils.py:271-272
+    ext = (1.0 - attention_mask[:, None, None, :].to(h.dtype)) * -1e9     # modeling_utils.py:271-272
     bias = compute_bias(L, L, sd["encoder.block.0.layer.0.SelfAttention.relative_attention_bias.weight"],
                         bidirectional=True, num_buckets=cfg.relative_attention_num_buckets)
     position_bias = bias + ext                                            # :399-400
@@ -125,11 +141,11 @@ def decoder_forward(sd, cfg, dec_ids, enc_hidden, enc_mask):
     L = enc_hidden.shape[1]
     h = sd["decode_embeddings.weight"][dec_ids]
     seq = torch.arange(t)
-    causal = (seq[None, None, :].repeat(R, t, 1) <= seq[None, :, None]).to(torch.float32)
+    causal = (seq[None, None, :].repeat(R, t, 1) <= seq[None, :, None]).to(h.dtype)
     ext = (1.0 - causal[:, None, :, :]) * -1e9                            # modeling_utils.py:236-272
     self_bias = compute_bias(t, t, sd["decoder.block.0.layer.0.SelfAttention.relative_attention_bias.weight"],
                              bidirectional=False, num_buckets=cfg.relative_attention_num_buckets) + ext
-    enc_ext = (1.0 - enc_mask[:, None, None, :].to(torch.float32)) * -1e9  # modeling_utils.py:179-211
+    enc_ext = (1.0 - enc_mask[:, None, None, :].to(h.dtype)) * -1e9       # modeling_utils.py:179-211
     cross_bias = compute_bias(t, L, sd["decoder.block.0.layer.1.EncDecAttention.relative_attention_bias.weight"],
                               bidirectional=True, num_buckets=cfg.relative_attention_num_buckets) + enc_ext
     for i in range(cfg.num_decoder_layers):
@@ -159,7 +175,7 @@ def _mha(x_q, x_kv, sd, prefix, nhead, attn_mask=None):
     s = torch.bmm(q, k.transpose(1, 2))
     if attn_mask is not None:
         s = s + attn_mask
-    w = F.softmax(s, dim=-1)
+    w = _softmax(s)
     o = torch.bmm(w, v).transpose(0, 1).contiguous().view(T, R, d)
     return _lin(o, sd[prefix + ".out_proj.weight"]) + sd[prefix + ".out_proj.bias"]
 
@@ -171,8 +187,8 @@ def adaptor_forward(sd, cfg, dec_ids):
     R, t = dec_ids.shape
     d = cfg.d_model
     x = sd["decode_embeddings.weight"][dec_ids].transpose(0, 1)           # [t,R,d]
-    mem = (sd["adaptor_embeddings"] + torch.zeros(R, 1, 1)).transpose(0, 1)   # [1,R,d]
-    mask = torch.full((t, t), float("-inf")).triu(1)
+    mem = (sd["adaptor_embeddings"] + torch.zeros(R, 1, 1, dtype=x.dtype)).transpose(0, 1)   # [1,R,d]
+    mask = torch.full((t, t), float("-inf"), dtype=x.dtype).triu(1)
     eps = cfg.adaptor_ln_eps
     for i in range(cfg.adaptor_layer_num):
         p = f"adaptor.layers.{i}"
@@ -192,9 +208,9 @@ def valid_columns(p, V):
     return list(range(p * V + 2, p * V + V + 2)) + [1]
 
 
-def positional_mask(t, Vd, V):
+def positional_mask(t, Vd, V, dtype=torch.float32):
     """select_valid_embedding's additive mask (modeling_t5.py:1546-1571) for positions 0..t-1: [t,Vd]."""
-    m = torch.full((t, Vd), -1e9)
+    m = torch.full((t, Vd), -1e9, dtype=dtype)
     for p in range(t):
         m[p, valid_columns(p, V)] = 0.0
     return m
@@ -208,7 +224,7 @@ def head_full(sd, cfg, dec_hidden, adapt_out):
     A = (adapt_out @ sd["adaptor_linear.weight"].T).reshape(R, t, d, -1)
     W = A + sd["lm_head.weight"].T.unsqueeze(0).unsqueeze(0)
     logits = torch.matmul(seq_out.unsqueeze(-2), W).squeeze(-2)
-    return logits + positional_mask(t, Vd, cfg.output_vocab_size)[None]
+    return logits + positional_mask(t, Vd, cfg.output_vocab_size, logits.dtype)[None]
 
 
 def head_last_restricted(sd, cfg, dec_hidden_last, adapt_last, p):
@@ -219,12 +235,12 @@ def head_last_restricted(sd, cfg, dec_hidden_last, adapt_last, p):
     cols = valid_columns(p, cfg.output_vocab_size)
     Wl = sd["adaptor_linear.weight"].view(d, Vd, d)[:, cols, :]           # [i, c', k]
     if GEMM_BF16:                                                         # the head GEMM is a linear of the C5 mode too
-        adapt_last, Wl = adapt_last.to(torch.bfloat16).float(), Wl.to(torch.bfloat16).float()
+        adapt_last, Wl = _r16(adapt_last), _r16(Wl)
     A = torch.einsum("rk,ick->ric", adapt_last, Wl)                       # [R, d(i), 31]
     W = A + sd["lm_head.weight"][cols].T.unsqueeze(0)
     h = dec_hidden_last * (d ** -0.5)
     lg = torch.einsum("ri,ric->rc", h, W)
-    out = torch.full((R, Vd), -1e9)
+    out = torch.full((R, Vd), -1e9, dtype=lg.dtype)
     out[:, cols] = lg
     return out
 
