@@ -43,30 +43,83 @@ __device__ __forceinline__ uint2 long_pack_bf16x4(float a, float b, float c, flo
 // ---------------------------------------------------------------------------------------------------------------- fp32 q / k / v
 // LDS: 2 buffers x (K[64][68] + V[64][68] + mask[64]) floats = 70 144 B (two workgroups per CU).  Row stride 68 floats: the
 // per-lane ds_read_b128 of "my key's row" is conflict-free, as in attention_mfma16_kernel.
+//
+// Three forms of one body:
+//   LONG_PLAIN     the doc tower: no position bias; the per-key cell of a block holds the additive mask.
+//   LONG_T5_SELF   the T5 encoder: + rel_bias[bucket(k - q)][h].  The bias depends on k - q alone (positions local to the sequence in
+//                  both layouts), so the workgroup builds its head's table over the 2 * 512 - 1 offsets once, RelT[(q - k) + 511]
+//                  (4 KB behind the two buffers: 74 240 B, still two workgroups per CU), from the bucket table and rel_bias; a score
+//                  is s + (RelT + mask), the one-pass kernels' and the reference's order (modeling_t5.py:399-400).
+//   LONG_T5_CROSS  decode-time cross-attention: the Lq <= 256 beam rows of a query (all at decoder position q_pos0, q_same_pos) against
+//                  the query's Lk encoder keys, K / V rows of batch entry b / kv_group.  The additive term of a key,
+//                  cross_rel_bias[bucket(q_pos0 - j)][h] + mask, is the same for every row: it is staged with the block in the
+//                  per-key cell, and the block loop is LONG_PLAIN's.  q rows come finished from memory or as the projection's split-K
+//                  slabs (q_part), summed in the reduction kernel's order as attention_kernel does.  One row (step 0) is a tile too.
+// Keys past the end inside the last block carry -inf in the two T5 forms (exactly probability 0 even when every real key is masked;
+// key 0 of every visited block is real, so the running maximum stays finite); LONG_PLAIN keeps the -1e9 it shipped with.
+enum { LONG_PLAIN = 0, LONG_T5_SELF = 1, LONG_T5_CROSS = 2 };
+constexpr int ATTN_LONG_MAXL = 512;  // RelT spans the offsets of this many positions; launch_attention bounds Lk by it
+
+// T5's bucket of (query position - key position) = n, modeling_t5.py:242-288 through the 128-entry table
+__device__ __forceinline__ int long_rel_bucket(const AttnArgs& a, int n) {
+  int bucket = 0;
+  if (a.bidirectional) {
+    if (n < 0) {
+      bucket = a.num_buckets >> 1;
+      n = -n;
+    }
+  } else if (n < 0) {
+    n = 0;
+  }
+  return bucket + a.lut.v[n < 127 ? n : 127];
+}
+
+template <int FORM>
 __global__ __launch_bounds__(512) void attention_long_f32_kernel(const AttnArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr int DK = 64, DS = DK + 4, KB = ATTN_LONG_KB, QB = ATTN_LONG_QB, BUF = 2 * KB * DS + KB;
+  constexpr bool CROSS = FORM == LONG_T5_CROSS;
+  if (CROSS && a.live && *a.live == 0) return;  // uniform: every query of the generate call is done
   const int b = blockIdx.x / a.H, h = blockIdx.x % a.H, tid = threadIdx.x;
-  const int L = a.seq_len ? a.seq_len[b] : a.Lk;  // ragged: this sequence's own length
+  const int kvb = CROSS ? b / a.kv_group : b;                     // whose K / V rows and mask
+  const int L = (!CROSS && a.seq_len) ? a.seq_len[b] : a.Lk;      // keys; ragged: this sequence's own length
+  const int Lq = CROSS ? a.Lq : L;                                // query rows
   const int q0 = blockIdx.y * QB;
-  if (q0 >= L) return;  // uniform: a query block past this sequence's end
-  const int64_t qrow0 = a.seq_off ? a.seq_off[b] : (int64_t)b * a.q_bstride;
-  const int64_t krow0 = a.seq_off ? a.seq_off[b] : (int64_t)b * a.k_bstride;
-  const int64_t orow0 = a.seq_off ? a.seq_off[b] : (int64_t)b * a.o_bstride;
+  if (q0 >= Lq) return;  // uniform: a query block past this sequence's end
+  const bool packed = !CROSS && a.seq_off;
+  const int64_t qrow0 = packed ? a.seq_off[b] : (int64_t)b * a.q_bstride;
+  const int64_t krow0 = packed ? a.seq_off[b] : (int64_t)kvb * a.k_bstride;
+  const int64_t orow0 = packed ? a.seq_off[b] : (int64_t)b * a.o_bstride;
   const int w = tid >> 6, lane = tid & 63, c16 = lane & 15, q4 = lane >> 4;
-  const bool active = q0 + 16 * w < L;  // wave-uniform; an idle wave still stages and meets the barriers
-  const int nkb = (L + KB - 1) / KB;    // key blocks wholly past the end are never visited
+  const bool active = q0 + 16 * w < Lq;  // wave-uniform; an idle wave still stages and meets the barriers
+  const int nkb = (L + KB - 1) / KB;     // key blocks wholly past the end are never visited
 
   // this wave's query fragments (B operand of S^T = K.Q^T): lane (c16, q4) holds Q[q0 + 16w + c16][16jj + 4q4 .. +3]
   float4 qv[DK / 16];
   {
-    const float* q32 = a.q + (qrow0 + min(q0 + 16 * w + c16, L - 1)) * a.ldq + h * DK + 4 * q4;
+    const int64_t qr = qrow0 + min(q0 + 16 * w + c16, Lq - 1);
+    if (CROSS && a.q_part) {  // the projection's split-K slabs, summed in the reduction kernel's order
 #pragma unroll
-    for (int jj = 0; jj < DK / 16; ++jj) qv[jj] = *reinterpret_cast<const float4*>(q32 + 16 * jj);
+      for (int jj = 0; jj < DK / 16; ++jj) {
+        const int n = h * DK + 16 * jj + 4 * q4;
+        const float* p = a.q_part + ((qr >> 6) * a.q_tiles_n + (n >> 6)) * (int64_t)a.q_S * 4096 + (qr & 63) * 64 + (n & 63);
+        float4 q = *reinterpret_cast<const float4*>(p);
+        for (int s = 1; s < a.q_S; ++s) {
+          const float4 u = *reinterpret_cast<const float4*>(p + (int64_t)s * 4096);
+          q.x += u.x, q.y += u.y, q.z += u.z, q.w += u.w;
+        }
+        qv[jj] = q;
+      }
+    } else {
+      const float* q32 = a.q + qr * a.ldq + h * DK + 4 * q4;
+#pragma unroll
+      for (int jj = 0; jj < DK / 16; ++jj) qv[jj] = *reinterpret_cast<const float4*>(q32 + 16 * jj);
+    }
   }
   // staging registers of one key block: 64 keys x 16 float4 of K and of V over 512 threads, one mask word for the first 64
   float4 kst0, kst1, vst0, vst1;  // (separate registers, not arrays: arrays captured by the lambdas below end up in scratch)
   int64_t mk_raw = 1;
+  float kbias = 0.f;  // LONG_T5_CROSS: the position bias of this thread's key
   const int sr = tid >> 4, sc = tid & 15;  // this thread's pieces: rows sr and sr + 32 of the block, float4 column sc
   auto load_block = [&](int kb) {
     const int64_t row0 = krow0 + min(kb * KB + sr, L - 1), row1 = krow0 + min(kb * KB + sr + 32, L - 1);
@@ -75,17 +128,28 @@ __global__ __launch_bounds__(512) void attention_long_f32_kernel(const AttnArgs 
     kst1 = *reinterpret_cast<const float4*>(a.k + row1 * a.ldk + h * DK + 4 * sc);
     vst1 = *reinterpret_cast<const float4*>(a.v + row1 * a.ldv + h * DK + 4 * sc);
     mk_raw = 1;
-    if (tid < KB && a.key_mask && kb * KB + tid < L) mk_raw = a.key_mask[(int64_t)b * a.mask_bstride + kb * KB + tid];
+    if (tid < KB && a.key_mask && kb * KB + tid < L) mk_raw = a.key_mask[(int64_t)kvb * a.mask_bstride + kb * KB + tid];
+    if (CROSS && a.rel_bias && tid < KB && kb * KB + tid < L)
+      kbias = a.rel_bias[long_rel_bucket(a, a.q_pos0 - (kb * KB + tid)) * a.H + h];
   };
   auto store_block = [&](int kb, float* buf) {
     *reinterpret_cast<float4*>(buf + sr * DS + 4 * sc) = kst0;
     *reinterpret_cast<float4*>(buf + KB * DS + sr * DS + 4 * sc) = vst0;
     *reinterpret_cast<float4*>(buf + (sr + 32) * DS + 4 * sc) = kst1;
     *reinterpret_cast<float4*>(buf + KB * DS + (sr + 32) * DS + 4 * sc) = vst1;
-    if (tid < KB) buf[2 * KB * DS + tid] = (kb * KB + tid < L && mk_raw != 0) ? 0.f : -1e9f;
+    if (FORM == LONG_PLAIN) {
+      if (tid < KB) buf[2 * KB * DS + tid] = (kb * KB + tid < L && mk_raw != 0) ? 0.f : -1e9f;
+    } else if (tid < KB) {  // (bias first, then one -1e9, as attention_cross_mfma16_kernel)
+      buf[2 * KB * DS + tid] = kb * KB + tid < L ? (mk_raw != 0 ? kbias : kbias + -1e9f) : -INFINITY;
+    }
   };
   load_block(0);
   store_block(0, smem);
+  if (FORM == LONG_T5_SELF) {
+    float* RelT = smem + 2 * BUF;  // RelT[(q - k) + 511]
+    for (int c = tid; c < 2 * ATTN_LONG_MAXL - 1; c += 512)
+      RelT[c] = a.rel_bias[long_rel_bucket(a, c - (ATTN_LONG_MAXL - 1)) * a.H + h];
+  }
 #pragma unroll
   for (int jj = 0; jj < DK / 16; ++jj) qv[jj].x *= a.scale, qv[jj].y *= a.scale, qv[jj].z *= a.scale, qv[jj].w *= a.scale;
   __syncthreads();
@@ -125,13 +189,17 @@ __global__ __launch_bounds__(512) void attention_long_f32_kernel(const AttnArgs 
       float bm = -INFINITY;
 #pragma unroll
       for (int t = 0; t < KB / 16; ++t) {
-        const float4 mk = *reinterpret_cast<const float4*>(Mk + 16 * t + 4 * q4);
+        float4 mk = *reinterpret_cast<const float4*>(Mk + 16 * t + 4 * q4);
+        if (FORM == LONG_T5_SELF) {  // (bias + mask) first, as the reference; key kb * KB + 16t + 4q4 + r sits r cells below
+          const float* rb = smem + 2 * BUF + (q0 + 16 * w + c16) - (kb * KB + 16 * t + 4 * q4) + (ATTN_LONG_MAXL - 1);
+          mk.x += rb[0], mk.y += rb[-1], mk.z += rb[-2], mk.w += rb[-3];
+        }
         st[t][0] += mk.x, st[t][1] += mk.y, st[t][2] += mk.z, st[t][3] += mk.w;
         bm = fmaxf(bm, fmaxf(fmaxf(st[t][0], st[t][1]), fmaxf(st[t][2], st[t][3])));
       }
       bm = fmaxf(bm, __shfl_xor(bm, 16));
       bm = fmaxf(bm, __shfl_xor(bm, 32));
-      const float m_new = fmaxf(m, bm);          // finite: every score is (the mask is additive -1e9, never -inf)
+      const float m_new = fmaxf(m, bm);          // finite: a masked key adds -1e9, and the -inf tail cells of the T5 forms follow real key 0 of the block
       const float alpha = __expf(m - m_new);     // first block: exp(-inf) = 0 over l = 0, o = 0
       m = m_new;
       float bs = 0.f;
@@ -167,7 +235,7 @@ __global__ __launch_bounds__(512) void attention_long_f32_kernel(const AttnArgs 
   l += __shfl_xor(l, 32);
   const float inv = 1.0f / l;
   const int i = q0 + 16 * w + c16;
-  if (i < L) {
+  if (i < Lq) {
 #pragma unroll
     for (int dt = 0; dt < DK / 16; ++dt) {
       const int64_t off = (orow0 + i) * a.ldo + h * DK + 16 * dt + 4 * q4;
@@ -343,10 +411,21 @@ __global__ __launch_bounds__(512) void attention_long_bf16_kernel(const AttnArgs
   }
 }
 
-// d_kv = 64 full self-attention over 128 < Lk <= 512 keys; launch_attention has checked the form (no position bias, no causal mask,
-// Lq == Lk, q_pos0 == 0, own K / V rows) and opened the ProfScope.
+// d_kv = 64 full self-attention over 128 < Lk <= 512 keys; launch_attention has checked the form (no causal mask, Lq == Lk,
+// q_pos0 == 0, own K / V rows) and opened the ProfScope.  With rel_bias: the T5 encoder's form, fp32 q / k / v only.
 int launch_attention_long(const AttnArgs& a, hipStream_t stream) {
+  static_assert(ATTN_LONG_MAXL >= ATTN_LONG_QB, "RelT index range");
+  GDR_CHECK_ARG(a.Lk <= ATTN_LONG_MAXL, "attention: L=%d above the key-block form's %d", a.Lk, ATTN_LONG_MAXL);
   const dim3 grid((unsigned)(a.B * a.H), (unsigned)((a.Lk + ATTN_LONG_QB - 1) / ATTN_LONG_QB));
+  if (a.rel_bias) {
+    GDR_CHECK_ARG(!a.qkv_bf16, "attention: bf16 q/k/v with a position bias stop at 128 keys (L=%d): hand in fp32 q/k/v", a.Lk);
+    const size_t lds = 2 * sizeof(float) * (size_t)(2 * ATTN_LONG_KB * 68 + ATTN_LONG_KB) + sizeof(float) * 2 * ATTN_LONG_MAXL;
+    if (int rc__ = ensure_dyn_lds(reinterpret_cast<const void*>(attention_long_f32_kernel<LONG_T5_SELF>), 80 * 1024, "attention"))
+      return rc__;
+    hipLaunchKernelGGL(attention_long_f32_kernel<LONG_T5_SELF>, grid, dim3(512), lds, stream, a);
+    GDR_CHECK_LAUNCH("attention_long_f32_kernel<T5 self>");
+    return GDR_OK;
+  }
   if (a.qkv_bf16) {
     GDR_CHECK_ARG(a.scale == 1.0f, "attention: bf16 q/k/v over L=%d > 128 keys need the scale folded into wqkv (scale=%g)", a.Lk,
                   (double)a.scale);
@@ -357,9 +436,23 @@ int launch_attention_long(const AttnArgs& a, hipStream_t stream) {
     return GDR_OK;
   }
   const size_t lds = 2 * sizeof(float) * (size_t)(2 * ATTN_LONG_KB * 68 + ATTN_LONG_KB);
-  if (int rc__ = ensure_dyn_lds(reinterpret_cast<const void*>(attention_long_f32_kernel), 80 * 1024, "attention")) return rc__;
-  hipLaunchKernelGGL(attention_long_f32_kernel, grid, dim3(512), lds, stream, a);
+  if (int rc__ = ensure_dyn_lds(reinterpret_cast<const void*>(attention_long_f32_kernel<LONG_PLAIN>), 80 * 1024, "attention")) return rc__;
+  hipLaunchKernelGGL(attention_long_f32_kernel<LONG_PLAIN>, grid, dim3(512), lds, stream, a);
   GDR_CHECK_LAUNCH("attention_long_f32_kernel");
+  return GDR_OK;
+}
+
+// d_kv = 64 beam rows x encoder keys over 128 < Lk <= 512 keys (LONG_T5_CROSS above); launch_attention has checked the form
+// (q_same_pos, own K / V rows through kv_group, no causal mask, fp32, 16-byte rows) and opened the ProfScope.  Lq >= 1: a workgroup
+// per 128 beam rows of a (query, head) stages the key blocks for its waves.
+int launch_attention_long_cross(const AttnArgs& a, hipStream_t stream) {
+  GDR_CHECK_ARG(a.Lk <= ATTN_LONG_MAXL, "attention: L=%d above the key-block form's %d", a.Lk, ATTN_LONG_MAXL);
+  const dim3 grid((unsigned)(a.B * a.H), (unsigned)((a.Lq + ATTN_LONG_QB - 1) / ATTN_LONG_QB));
+  const size_t lds = 2 * sizeof(float) * (size_t)(2 * ATTN_LONG_KB * 68 + ATTN_LONG_KB);
+  if (int rc__ = ensure_dyn_lds(reinterpret_cast<const void*>(attention_long_f32_kernel<LONG_T5_CROSS>), 80 * 1024, "attention"))
+    return rc__;
+  hipLaunchKernelGGL(attention_long_f32_kernel<LONG_T5_CROSS>, grid, dim3(512), lds, stream, a);
+  GDR_CHECK_LAUNCH("attention_long_f32_kernel<T5 cross>");
   return GDR_OK;
 }
 

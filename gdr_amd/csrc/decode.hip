@@ -1224,7 +1224,7 @@ static int generate_impl(const GdrT5DecoderWeights* w, const float* enc_hidden, 
               trie ? trie->n_nodes : (ptab ? ptab->n_nodes : 0)};
   int rc = check_beam_dims(bd, max_length);
   if (rc) return rc;
-  GDR_CHECK_ARG(L >= 1 && L <= 128, "generate: L=%d must be in [1,128]", L);
+  GDR_CHECK_ARG(L >= 1 && L <= T5_MAX_LEN, "generate: L=%d must be in [1,%d]", L, T5_MAX_LEN);
   GDR_CHECK_ARG(max_length <= w->max_out_len, "generate: max_length=%d > max_output_length=%d of the head", max_length,
                 w->max_out_len);
   GDR_CHECK_ARG(dm.d_model % 4 == 0 && dm.d_kv % 4 == 0 && dm.d_model % w->adaptor_nhead == 0 &&

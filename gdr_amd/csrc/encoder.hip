@@ -7,7 +7,7 @@
 //                 one [3*inner,d] GEMM,
 //                 residual add and ReLU fused into the GEMM epilogues        (:360-364,:413,:182-185,:199)
 //   attn          layers.hip  attention_mfma16_kernel (d_kv = 64: S^T = K·Q^T and O^T = V^T·P^T on v_mfma_f32_16x16x4_f32, one
-//                 wave per 16-query tile) or attention_kernel (any d_kv): QKᵀ (no 1/sqrt(d)) + bucketed relative bias +
+//                 wave per 16-query tile; above 128 tokens attention_long.hip's key-block form) or attention_kernel (any d_kv): QKᵀ (no 1/sqrt(d)) + bucketed relative bias +
 //                 pad mask (1-m)*-1e9 + fp32 softmax + PV                           (:384-413, :290-314)
 // The position bias is never materialised as a [B,H,L,L] tensor: the kernel re-derives it from the
 // [buckets,H] table (layer 0's, shared by all layers as in :790-795).
@@ -68,7 +68,7 @@ static int t5_encoder_impl(const GdrT5EncoderWeights* w, const int64_t* ids, con
   if (B == 0) return GDR_OK;  // empty batch
   GDR_CHECK_ARG(w && ids && out_hidden && workspace, "t5_encoder: null pointer");
   const GdrT5Dims& dm = w->dims;
-  GDR_CHECK_ARG(B > 0 && L > 0 && L <= 128, "t5_encoder: B=%d L=%d (L must be in [1,128])", B, L);
+  GDR_CHECK_ARG(B > 0 && L > 0 && L <= T5_MAX_LEN, "t5_encoder: B=%d L=%d (L must be in [1,%d])", B, L, T5_MAX_LEN);
   GDR_CHECK_ARG(dm.d_model % 4 == 0 && dm.d_kv % 4 == 0 && dm.d_ff % 4 == 0, "t5_encoder: dims must be multiples of 4");
   GDR_CHECK_ARG(w->embed && w->rel_bias && w->final_ln && w->layers, "t5_encoder: null weight pointer");
   const int64_t M = (int64_t)B * L;
@@ -230,7 +230,7 @@ static int ragged_impl(const GdrT5EncoderWeights* w, const int64_t* ids, const i
   if (B == 0) return GDR_OK;
   GDR_CHECK_ARG(w && ids && mask && workspace && (out_hidden || out_pooled), "t5_encoder_ragged: null pointer");
   const GdrT5Dims& dm = w->dims;
-  GDR_CHECK_ARG(B > 0 && L > 0 && L <= 128, "t5_encoder_ragged: B=%d L=%d (L must be in [1,128])", B, L);
+  GDR_CHECK_ARG(B > 0 && L > 0 && L <= T5_MAX_LEN, "t5_encoder_ragged: B=%d L=%d (L must be in [1,%d])", B, L, T5_MAX_LEN);
   GDR_CHECK_ARG(dm.d_model % 4 == 0 && dm.d_kv % 4 == 0 && dm.d_ff % 4 == 0, "t5_encoder_ragged: dims must be multiples of 4");
   GDR_CHECK_ARG(w->embed && w->rel_bias && w->final_ln && w->layers, "t5_encoder_ragged: null weight pointer");
   const int64_t M = (int64_t)B * L;
@@ -285,10 +285,15 @@ static int ragged_impl(const GdrT5EncoderWeights* w, const int64_t* ids, const i
     };
     if ((rc = launch_embed_packed(w->embed, ids, row_src, rows_dev, M, d, dm.vocab_size, h, stream))) return rc;
     AttnArgs at{};
-    {
-      const __bf16* q16 = reinterpret_cast<const __bf16*>(qkv);  // the packed form always runs the d_kv = 64 MFMA attention
+    // the packed form always runs a d_kv = 64 MFMA attention: up to 128 tokens on bf16 q / k / v; above, the key-block form with
+    // position bias is fp32 (as the padded form above): the qkv linear stores fp32 and the context still leaves as bf16
+    const bool qkv16 = L <= 128;
+    if (qkv16) {
+      const __bf16* q16 = reinterpret_cast<const __bf16*>(qkv);
       at.q = reinterpret_cast<const float*>(q16), at.k = reinterpret_cast<const float*>(q16 + inner);
       at.v = reinterpret_cast<const float*>(q16 + 2 * inner), at.qkv_bf16 = 1;
+    } else {
+      at.q = qkv, at.k = qkv + inner, at.v = qkv + 2 * inner;
     }
     at.out = nullptr, at.out_bf16 = abf;
     at.ldq = at.ldk = at.ldv = 3 * inner, at.ldo = inner;
@@ -305,7 +310,7 @@ static int ragged_impl(const GdrT5EncoderWeights* w, const int64_t* ids, const i
       const GdrT5EncLayer& ly = w->layers[i];
       GDR_CHECK_ARG(ly.ln_attn && ly.wqkv && ly.wo && ly.ln_ff && ly.wi && ly.wo_ff, "t5_encoder_ragged: layer %d null weight", i);
       if ((rc = launch_rmsnorm_bf16_dev(h, ly.ln_attn, abf, rows_dev, M, d, dm.eps, stream))) return rc;
-      if ((rc = lin16(abf, ly.wqkv, qkv, 3 * inner, M, rows_dev, 3 * inner, d, 0, nullptr, 1))) return rc;  // q,k,v as bf16
+      if ((rc = lin16(abf, ly.wqkv, qkv, 3 * inner, M, rows_dev, 3 * inner, d, 0, nullptr, qkv16 ? 1 : 0))) return rc;  // q,k,v: bf16 up to 128 tokens, fp32 above
       if ((rc = launch_attention(at, stream))) return rc;  // ctx -> abf as bf16 [rows, inner]
       if (pooled_only && i == dm.num_layers - 1) {
         // bf16 rows are inner/2 (d/2, d_ff/2) floats wide for the row mover
@@ -465,7 +470,7 @@ static int ragged_split_impl(const GdrT5EncoderWeights* w, const int64_t* ids, c
   const int f16 = terms == 2 ? 1 : 0;
   GDR_CHECK_ARG(w && ids && mask && workspace && (out_hidden || out_pooled), "t5_encoder_split: null pointer");
   const GdrT5Dims& dm = w->dims;
-  GDR_CHECK_ARG(B > 0 && L > 0 && L <= 128, "t5_encoder_split: B=%d L=%d (L must be in [1,128])", B, L);
+  GDR_CHECK_ARG(B > 0 && L > 0 && L <= T5_MAX_LEN, "t5_encoder_split: B=%d L=%d (L must be in [1,%d])", B, L, T5_MAX_LEN);
   GDR_CHECK_ARG(w->embed && w->rel_bias && w->final_ln && w->layers, "t5_encoder_split: null weight pointer");
   const int d = dm.d_model, H = dm.num_heads, dk = dm.d_kv, inner = H * dk, dff = dm.d_ff;
   GDR_CHECK_ARG(dk == 64 && d % 64 == 0 && inner % 64 == 0 && dff % 64 == 0,

@@ -52,9 +52,14 @@ struct AttnArgs {
   const int32_t* live;
 };
 int launch_attention(const AttnArgs& a, hipStream_t stream);
+// input tokens per sequence in every T5 entry point (encoder forms, generate): what launch_attention serves (ops.T5_MAX_LEN)
+constexpr int T5_MAX_LEN = 512;
 // attention_long.hip: d_kv = 64 full self-attention over 128 < Lk <= 512 keys (key-block walk, online softmax), fp32 or bf16 q / k / v,
-// padded or packed layout.  Reached through launch_attention only, which checks the form and opens the ProfScope.
+// padded or packed layout; with rel_bias (the T5 encoder) fp32 only.  Reached through launch_attention only, which checks the form and
+// opens the ProfScope.
 int launch_attention_long(const AttnArgs& a, hipStream_t stream);
+// the same walk for the Lq >= 1 beam rows of a decode step (q_same_pos) against 128 < Lk <= 512 encoder keys, d_kv = 64, fp32
+int launch_attention_long_cross(const AttnArgs& a, hipStream_t stream);
 
 int launch_embed(const float* table, const int64_t* ids, int64_t rows, int d, int vocab, float* out,
                  hipStream_t stream);

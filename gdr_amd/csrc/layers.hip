@@ -582,8 +582,8 @@ int launch_layernorm_dev(const float* x, const float* w, const float* b, float* 
 // ------------------------------------------------------------------------------------------ attention
 // One workgroup per (batch, head): K and V rows of that head are staged once in LDS (row stride dk+4 floats:
 // ≡ 4 mod 64 banks for dk = 64, so the per-lane ds_read_b128 of "my key's row" is conflict-free); each of
-// the 4 waves then walks query rows: lane j scores keys j, j+64, ... (KT strips of 64 keys: 2 serves Lk <= 128, every call of the T5
-// paths; 8 serves the doc tower's other head widths up to 512 keys), softmax by wave shuffles, PV with lane = d.
+// the 4 waves then walks query rows: lane j scores keys j, j+64, ... (KT strips of 64 keys: 2 serves Lk <= 128; 8 serves head
+// widths other than 64 up to 512 keys, in the doc tower and, with position bias, in the T5 paths), softmax by wave shuffles, PV with lane = d.
 template <int KT>
 __global__ __launch_bounds__(256) void attention_kernel(const AttnArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -1646,11 +1646,11 @@ __global__ __launch_bounds__(256) void attention_decode_heads4_kernel(const Attn
 int launch_attention(const AttnArgs& a, hipStream_t stream) {
   GDR_CHECK_ARG(a.dk % 4 == 0 && a.dk >= 4 && a.dk <= 256, "attention: dk=%d unsupported", a.dk);
   GDR_CHECK_ARG(a.Lk >= 1 && a.Lk <= 512, "attention: Lk=%d must be in [1,512]", a.Lk);
-  // more than 128 keys: full self-attention without position bias (the doc tower) only — every other form keeps its whole K / V strip
-  // in LDS or in registers sized for 128 keys
-  GDR_CHECK_ARG(a.Lk <= 128 || (a.Lq == a.Lk && a.q_pos0 == 0 && !a.kv_rows && a.kv_group == 1 && !a.q_same_pos && !a.rel_bias &&
-                                !a.causal && !a.q_part && !a.b_count_dev),
-                "attention: Lk=%d > 128 serves full self-attention without position bias or causal mask only (Lq=%d)", a.Lk, a.Lq);
+  // more than 128 keys: the one-pass MFMA forms and the Lq = 1 row-group forms keep their K / V or score strip sized for 128 keys.
+  // d_kv = 64 has key-block forms (attention_long.hip) for full self-attention — without position bias (the doc tower) and with T5's —
+  // and for the beam rows of a decode step against the encoder keys; everything else takes the generic kernel where its LDS check
+  // passes.  A device-side batch count exists in the row-group form alone.
+  GDR_CHECK_ARG(a.Lk <= 128 || !a.b_count_dev, "attention: a device-side batch count stops at 128 keys (Lk=%d)", a.Lk);
   GDR_CHECK_ARG(a.ldq % 4 == 0 && a.ldk % 4 == 0 && a.ldv % 4 == 0, "attention: row strides must be multiples of 4");
   GDR_CHECK_ARG(!a.rel_bias || (a.num_buckets >= 2 && a.num_buckets <= 256), "attention: bad num_buckets");
   GDR_CHECK_ARG(a.kv_group >= 1, "attention: kv_group must be >= 1");
@@ -1664,7 +1664,7 @@ int launch_attention(const AttnArgs& a, hipStream_t stream) {
   GDR_CHECK_ARG(!(a.Lq == 1 && a.b_count_dev && !(a.dk <= 128 && a.ldo % 4 == 0)),
                 "attention: a device-side batch count needs the Lq = 1 row-group form (dk <= 128, ldo %% 4 == 0; dk=%d ldo=%lld)", a.dk,
                 (long long)a.ldo);
-  if (a.Lq == 1 && a.dk <= 128 && a.ldo % 4 == 0) {
+  if (a.Lq == 1 && a.dk <= 128 && a.ldo % 4 == 0 && a.Lk <= 128) {
     if (a.Lk <= (a.dk <= 64 ? 16 : 12)) {  // a decode step's key list
       // the beam rows of a query share their ancestors: one workgroup per (query, head) stages the distinct K / V rows once
 #ifndef GDR_LAB_ATTN_NO_HEADS4
@@ -1706,7 +1706,10 @@ int launch_attention(const AttnArgs& a, hipStream_t stream) {
                 "attention: the packed (ragged) form and bf16 q/k/v serve full self-attention with d_kv = 64 only");
   GDR_CHECK_ARG(!a.qkv_bf16 || (a.ldq % 8 == 0 && a.ldk % 8 == 0 && a.ldv % 8 == 0), "attention: bf16 q/k/v need row strides %% 8 == 0");
   if (a.Lq == a.Lk && a.q_pos0 == 0 && !a.kv_rows && a.kv_group == 1 && !a.q_same_pos && a.dk == 64 && a.ldo % 4 == 0) {
-    if (a.Lk > 128) return launch_attention_long(a, stream);  // K / V no longer fit in LDS: key-block walk (attention_long.hip)
+    if (a.Lk > 128) {  // K / V no longer fit in LDS: key-block walk (attention_long.hip)
+      GDR_CHECK_ARG(!a.causal && !a.q_part, "attention: Lk=%d > 128 self-attention has no causal or slab-sourced form", a.Lk);
+      return launch_attention_long(a, stream);
+    }
     if (a.qkv_bf16 && a.scale == 1.0f) {  // bf16 operands as they stand: the bf16-MFMA form
       switch ((a.Lk + 15) / 16) {
         case 1: return launch_attention_mfma_bf16<1>(a, stream);
@@ -1730,7 +1733,10 @@ int launch_attention(const AttnArgs& a, hipStream_t stream) {
       default: return launch_attention_mfma16<8>(a, stream);
     }
   }
-  if (cross_mfma_wanted(a)) {
+  // the shared-K/V decode shape over more than 128 encoder keys, one beam row (step 0) or many, finished or slab-sourced q rows
+  if (a.Lk > 128 && a.q_same_pos && a.dk == 64 && !a.kv_rows && !a.causal && !a.seq_off && !a.qkv_bf16 && a.ldo % 4 == 0)
+    return launch_attention_long_cross(a, stream);
+  if (a.Lk <= 128 && cross_mfma_wanted(a)) {
     switch ((a.Lk + 15) / 16) {
       case 1: return launch_attention_cross_mfma16<1>(a, stream);
       case 2: return launch_attention_cross_mfma16<2>(a, stream);

@@ -34,6 +34,7 @@ if __package__ in (None, ""):
 
 from . import _ffi, codec, launch, synth        # noqa: E402
 from .config import GDRConfig, unsupported_variant   # noqa: E402
+from .ops import T5_MAX_LEN                           # noqa: E402
 
 # (flag, type, default[, choices]) — names, types and defaults of main.py:262-396
 _FLAGS = [
@@ -104,6 +105,10 @@ def parsers_parser(argv=None):
     parser.add_argument("--score_rate", type=float, nargs="+", default=[0, 0.5, 1, 1.5, 2, 2.5, 3])
     parser.add_argument("--expand", type=bool, default=True)
     a = parser.parse_args(argv)
+    for flag in ("max_input_length", "inf_max_input_length"):   # before any model is built: what the T5 kernels take (ops.T5_MAX_LEN)
+        if getattr(a, flag) > T5_MAX_LEN:
+            raise SystemExit(f"gdr_amd: --{flag} {getattr(a, flag)} exceeds the {T5_MAX_LEN} input tokens the query tower and "
+                             f"generate() take.")
     # the reference's post-processing (main.py:398-447)
     a.dataset_name = "Self_NQ_{}_{}{}".format(a.kmeans_model, str(a.docnum), a.data_suffix)
     a.tokenizer_name_or_path += a.model_info

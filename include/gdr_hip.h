@@ -168,7 +168,12 @@ typedef struct {
 
 size_t gdr_t5_encoder_workspace_bytes(const GdrT5Dims* dims, int B, int L);
 /* ids/mask int64[B,L]; out_hidden fp32[B,L,d]; optional out_pooled fp32[B,d] = hidden[:,0]
- * (CLS pool, main_models.py:102-109 / dense.py:39,50) or NULL. */
+ * (CLS pool, main_models.py:102-109 / dense.py:39,50) or NULL.
+ * 1 <= L <= 512 in every T5 encoder form below (the reference's T5Stack takes any length; --max_input_length is a free flag).  Up to
+ * 128 tokens the one-pass attention kernels serve every head width; above, d_kv = 64 takes the key-block kernel with T5's relative
+ * position bias (csrc/attention_long.hip, padded and packed layout, fp32 q / k / v in every precision mode: the bf16 mode keeps
+ * q, k, v in fp32 there), another head width the generic kernel while the K / V rows of one (sequence, head) fit in LDS (d_kv = 16 at
+ * L = 512 does; d_kv = 128 does not: GDR_EINVAL naming d_kv and L). */
 int gdr_t5_encoder_forward(const GdrT5EncoderWeights* w, const int64_t* ids, const int64_t* mask, int B, int L,
                            float* out_hidden, float* out_pooled, void* workspace, size_t workspace_bytes,
                            void* stream);
@@ -224,7 +229,7 @@ int gdr_t5_encoder_forward_ragged_split(const GdrT5EncoderWeights* w, const int6
 /* bf16 precision mode (BASELINE config C5): the SAME structs, but the four linear weights of every layer (wqkv, wo, wi,
  * wo_ff) point to bf16 [N,K] matrices (round-to-nearest-even of the fp32 checkpoint, e.g. gdr_cast_f32_bf16); the
  * `const float*` field type is nominal for them.  Each linear rounds its activation operand to bf16 and accumulates in
- * fp32; with d_kv = 64 (the MFMA attention form) the qkv linear also EMITS q, k, v as bf16 — QK^T and PV take those
+ * fp32; with d_kv = 64 (the MFMA attention form) and L <= 128 the qkv linear also EMITS q, k, v as bf16 — QK^T and PV take those
  * rounded operands, accumulate in fp32, softmax in fp32; embedding, norms, the residual stream and both outputs stay fp32.  The
  * reference has no such mode (it runs precision=32, main.py:61,91): parity is against the fp32 path within bf16
  * tolerance and against the oracle's bf16 emulation (oracle/t5_ref.py bf16_linears). */
@@ -632,7 +637,10 @@ int gdr_t5_prefix_table_build(const GdrT5DecoderWeights* w, int n_levels, const 
                               void* stream);
 
 size_t gdr_t5_generate_workspace_bytes(const GdrT5DecoderWeights* w, int B, int L, int num_beams, int max_length);
-/* enc_hidden fp32[B,L,d] (NOT beam-expanded), enc_mask int64[B,L].
+/* enc_hidden fp32[B,L,d] (NOT beam-expanded), enc_mask int64[B,L], 1 <= L <= 512 (both modes).  Over more than 128 encoder keys the
+ * cross-attention of d_kv = 64 is the key-block kernel of csrc/attention_long.hip (beam rows as 16-row MFMA tiles, 64-key blocks,
+ * online softmax; also step 0's single row per query); another head width takes the generic kernel while K / V fit in LDS, else
+ * GDR_EINVAL naming d_kv and L.
  * out_ids int64[B*nret, max_length] (hypothesis tokens incl. START, then EOS if it fits, then PAD),
  * out_len int32[B*nret] (= len(hyp), EOS excluded), out_scores fp64[B*nret] (sum_logprobs / len^length_penalty,
  * computed in double like the reference's Python floats).  Optional trace (NULL to skip):
