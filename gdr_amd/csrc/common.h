@@ -33,6 +33,10 @@ void count_launch();
 
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
+// Most beams per query of the two-stage path: the beam decode (decode.hip: check_beam_dims) produces up to this many rows per
+// query and the stage behind it (rerank.hip: RR_MAX_BEAMS, k of the long-list select) takes as many.
+constexpr int GDR_MAX_BEAMS = 1024;
+
 // Raises a kernel's dynamic-LDS limit (hipFuncAttributeMaxDynamicSharedMemorySize) once per (kernel, device): the
 // attribute lives on the device's code object, so a process that drives several GPUs must set it on each of them.
 // Thread-safe.  Returns GDR_OK or GDR_EHIP (message set).

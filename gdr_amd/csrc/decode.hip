@@ -61,6 +61,8 @@ struct BeamBufs {
   int32_t* done;        // [B]
   int32_t* n_done;      // [1] queries whose beam search is done (generation_utils.py:827-829)
   int32_t* live;        // [1] 1 until n_done reaches B: the linears and the miss-row chain of later steps look at it
+  float* lse;                     // chunked select only: [rows][2] every beam row's (max, log-sum-exp) of the step
+  unsigned long long* part[2];    // chunked select only: [B][lists][2R] sorted partial lists of keys, ping-pong over the merge rounds
   const int32_t* live_gate;  // = live when the call may skip the steps behind the last query's end (no per-step trace wanted), else
                              // null: the attention / reduction / head / beam kernels of such a step exit at once through it
   int32_t* all_done_host;  // host-mapped word (may be null): receives `done_epoch` when n_done reaches B
@@ -77,6 +79,28 @@ struct BeamDims {
   const int32_t* trie_eos;
   int trie_nodes;
 };
+
+// ---- the top-2R select of a step: one LDS sort per query while its R*(V+1) candidates fit BEAM_SORT_MAX keys, above that (or
+// with GDR_DECODE_BEAM_CHUNKED=1, an exact A/B knob nothing in the product sets) chunks of BEAM_CHUNK candidate positions are
+// sorted on their own and their first 2R keys merged — the same list bit for bit (beam_chunk_kernel).
+constexpr int BEAM_SORT_MAX = 8192;    // keys of one LDS sort (beam_topk_kernel, a beam_merge_kernel workgroup)
+constexpr int BEAM_CHUNK = 4096;       // candidate positions per chunk workgroup: 32 KiB of keys
+constexpr int BEAM_MAX_CAND = 1 << 17; // num_beams * (V+1): 1024 beams up to V = 127; flat indices stay far inside 32 bits
+constexpr int BEAM_LDS_LIMIT = 160 * 1024;  // LDS of a CU = the most one workgroup may hold (static + dynamic)
+static_assert(2 * GDR_MAX_BEAMS <= BEAM_CHUNK && BEAM_SORT_MAX / (2 * GDR_MAX_BEAMS) >= 2,
+              "a chunk keeps 2R keys; a merge round must shrink the list count");
+
+static bool beam_chunked_forced() {
+  static const bool on = [] {
+    const char* e = getenv("GDR_DECODE_BEAM_CHUNKED");  // read once per process, like the other GDR_DECODE_* switches
+    return e ? atoi(e) != 0 : false;
+  }();
+  return on;
+}
+static bool beam_chunked(int R, int V) { return beam_chunked_forced() || (int64_t)R * (V + 1) > BEAM_SORT_MAX; }
+static int beam_chunks(int R, int V) { return (int)(((int64_t)R * (V + 1) + BEAM_CHUNK - 1) / BEAM_CHUNK); }
+// partial lists (2R keys each) one merge workgroup sorts; >= 4 for every accepted R (the size functions take any R)
+static int beam_merge_fan(int R) { return BEAM_SORT_MAX / (2 * R) > 2 ? BEAM_SORT_MAX / (2 * R) : 2; }
 
 static size_t carve(size_t& o, size_t bytes) {
   const size_t at = o;
@@ -119,6 +143,12 @@ static size_t beam_layout(const BeamDims& bd, char* base, BeamBufs* bb) {
   CARVE(done, int32_t, bd.B);
   CARVE(n_done, int32_t, 1);
   CARVE(live, int32_t, 1);
+  // the chunked select's scratch: nothing (zero bytes, the offsets above unchanged) for a call that stays in the one-sort form
+  const bool chunked = beam_chunked(bd.R, bd.V);
+  const size_t lists = chunked ? (size_t)beam_chunks(bd.R, bd.V) : 0, fan = beam_merge_fan(bd.R);
+  CARVE(lse, float, chunked ? rows * 2 : 0);
+  CARVE(part[0], unsigned long long, (size_t)bd.B * lists * 2 * bd.R);
+  CARVE(part[1], unsigned long long, (size_t)bd.B * ((lists + fan - 1) / fan) * 2 * bd.R);
 #undef CARVE
   return o;
 }
@@ -503,6 +533,130 @@ __global__ __launch_bounds__(1024) void beam_topk_kernel(BeamBufs bb, BeamDims b
   }
 }
 
+// ---- the chunked select (R*(V+1) > BEAM_SORT_MAX candidates per query, or forced) ---------------------------------------------
+// Three kinds of launches leave in cand_score / cand_idx (and the trace) what beam_topk_kernel leaves, bit for bit:
+//   beam_norm_kernel   every beam row's max and log-sum-exp — a wave per row with beam_topk_kernel's lane assignment and order, so
+//                      the log-probabilities get the same bits;
+//   beam_chunk_kernel  a workgroup per (chunk of BEAM_CHUNK candidate positions, query) builds beam_topk_kernel's keys for its
+//                      positions (key 0 past the query's last candidate), sorts them and files its first 2R;
+//   beam_merge_kernel  a workgroup per (group of lists, query) sorts the group's keys and files the first 2R; the round that is left
+//                      with one list per query writes the result instead.
+// The keys are distinct (the flat index is the low word), so their order is total: the first 2R of the whole list are the first 2R
+// of the chunks' first 2R, whatever the grouping.  No atomics, nothing depends on the order workgroups run in.
+
+// Bitonic sort of n keys in LDS (n a power of two >= 64, a multiple of 2 * the workgroup's waves), descending; the whole workgroup
+// calls it after a barrier behind the last store to keys[], and meets a barrier before it reads the result.  Stages whose pairs
+// stay inside one wave's block of n / nwaves keys cost a wave barrier only (LDS operations of a wave execute in order).
+__device__ __forceinline__ void beam_bitonic_desc(unsigned long long* keys, int n, int tid, int nthr) {
+  const int wave = tid >> 6, lane = tid & 63, epw = n / (nthr >> 6);
+  for (int size = 2; size <= n; size <<= 1) {
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      if (2 * stride <= epw) {
+        for (int q = lane; q < (epw >> 1); q += 64) {
+          const int t = (epw >> 1) * wave + q;
+          const int lo = (t / stride) * (stride << 1) + (t % stride), hi = lo + stride;
+          const bool desc = ((lo & size) == 0);
+          const unsigned long long x = keys[lo], y = keys[hi];
+          if ((x < y) == desc) keys[lo] = y, keys[hi] = x;
+        }
+        wave_sync();
+      } else {
+        __syncthreads();
+        for (int t = tid; t < (n >> 1); t += nthr) {
+          const int lo = (t / stride) * (stride << 1) + (t % stride), hi = lo + stride;
+          const bool desc = ((lo & size) == 0);
+          const unsigned long long x = keys[lo], y = keys[hi];
+          if ((x < y) == desc) keys[lo] = y, keys[hi] = x;
+        }
+        __syncthreads();
+      }
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void beam_norm_kernel(BeamBufs bb, BeamDims bd, int bcast) {
+  if (bb.live_gate && *bb.live_gate == 0) return;
+  const int b = blockIdx.x, lane = threadIdx.x & 63, V1 = bd.V + 1;
+  const int j = blockIdx.y * 4 + (threadIdx.x >> 6);
+  if (j >= bd.R) return;
+  const float* lg = bb.logits + (bcast ? (size_t)b * V1 : ((size_t)b * bd.R + j) * V1);
+  float mx = -INFINITY;
+  for (int c = lane; c < V1; c += 64) mx = fmaxf(mx, lg[c]);
+  mx = wave_max(mx);
+  float sm = 0.f;
+  for (int c = lane; c < V1; c += 64) sm += expf(lg[c] - mx);
+  sm = wave_sum(sm);
+  if (lane == 0) {
+    bb.lse[((size_t)b * bd.R + j) * 2] = mx;
+    bb.lse[((size_t)b * bd.R + j) * 2 + 1] = logf(sm);
+  }
+}
+
+__global__ __launch_bounds__(1024) void beam_chunk_kernel(BeamBufs bb, BeamDims bd, int pos, int cur, int bcast, int nchunks) {
+  __shared__ __attribute__((aligned(16))) unsigned long long keys[BEAM_CHUNK];
+  if (bb.live_gate && *bb.live_gate == 0) return;
+  const int b = blockIdx.x, ch = blockIdx.y, tid = threadIdx.x;
+  const int R = bd.R, V1 = bd.V + 1, ncand = R * V1, keep = 2 * R;
+  for (int i = tid; i < BEAM_CHUNK; i += 1024) {
+    const int e = ch * BEAM_CHUNK + i;
+    unsigned long long key = 0ull;
+    if (e < ncand) {
+      const int j = e / V1, c = e - j * V1;
+      const float lgt = bcast ? bb.logits[(size_t)b * V1 + c] : bb.logits[(size_t)b * ncand + e];
+      const float* nrm = bb.lse + ((size_t)b * R + j) * 2;
+      const float logp = (lgt - nrm[0]) - nrm[1];
+      float s = logp + bb.beam_scores[(size_t)b * R + j];
+      if (bd.trie_eos) {
+        const int nd = bb.node[cur][(size_t)b * R + j];
+        const bool ok = c < bd.V ? (nd >= 0 && bd.trie_child[(size_t)nd * bd.V + c] >= 0) : (nd < 0 || bd.trie_eos[nd] != 0);
+        if (!ok) s = -INFINITY;
+      }
+      const int tok = c < bd.V ? pos * bd.V + 2 + c : EOS_ID;
+      const uint32_t flat = (uint32_t)(j * bd.Vd + tok);
+      key = ((unsigned long long)dfkey(s) << 32) | (unsigned long long)(0xFFFFFFFFu - flat);
+    }
+    keys[i] = key;
+  }
+  __syncthreads();
+  beam_bitonic_desc(keys, BEAM_CHUNK, tid, 1024);
+  __syncthreads();
+  unsigned long long* dst = bb.part[0] + ((size_t)b * nchunks + ch) * keep;
+  for (int i = tid; i < keep; i += 1024) dst[i] = keys[i];
+}
+
+// in: [B][n_in][2R] sorted lists; workgroup (b, g) takes lists g*fan .. of query b.  final: n_in <= fan, one workgroup per query.
+__global__ __launch_bounds__(1024) void beam_merge_kernel(BeamBufs bb, BeamDims bd, const unsigned long long* __restrict__ in,
+                                                         int n_in, int fan, int npad, unsigned long long* __restrict__ out,
+                                                         int n_out, int final, float* __restrict__ step_scores,
+                                                         int32_t* __restrict__ step_tokens) {
+  extern __shared__ __attribute__((aligned(16))) unsigned long long keys[];  // [npad]
+  if (bb.live_gate && *bb.live_gate == 0) return;
+  const int b = blockIdx.x, g = blockIdx.y, tid = threadIdx.x, nthr = blockDim.x;
+  const int keep = 2 * bd.R;
+  const int l0 = g * fan, nl = min(fan, n_in - l0), have = nl * keep;
+  const unsigned long long* src = in + ((size_t)b * n_in + l0) * keep;
+  for (int i = tid; i < npad; i += nthr) keys[i] = i < have ? src[i] : 0ull;
+  __syncthreads();
+  beam_bitonic_desc(keys, npad, tid, nthr);
+  __syncthreads();
+  if (!final) {
+    unsigned long long* dst = out + ((size_t)b * n_out + g) * keep;
+    for (int i = tid; i < keep; i += nthr) dst[i] = keys[i];
+    return;
+  }
+  for (int i = tid; i < keep; i += nthr) {
+    const unsigned long long key = keys[i];
+    const float s = dfkey_inv((uint32_t)(key >> 32));
+    const int32_t flat = (int32_t)(0xFFFFFFFFu - (uint32_t)(key & 0xFFFFFFFFull));
+    bb.cand_score[(size_t)b * keep + i] = s;
+    bb.cand_idx[(size_t)b * keep + i] = flat;
+    if (step_scores) {
+      step_scores[(size_t)b * keep + i] = s;
+      step_tokens[(size_t)b * keep + i] = flat;
+    }
+  }
+}
+
 // ---- BeamHypotheses of one query, held in LDS by the single wave that serves the query -------------------------------
 // The reference keeps `self.beams` as a Python list (generation_utils.py:1052-1099): add() appends, an over-full list
 // drops its worst entry with `del` (order of the rest kept), the final pick is a stable sort by score popped from the
@@ -868,28 +1022,65 @@ static int next_pow2i(int x) {
   return p;
 }
 
+// dynamic LDS of the two kernels that hold a query's hypothesis heap
+static size_t beam_update_lds(const BeamDims& bd) {
+  return ((hyp_lds_bytes(bd.R, bd.maxlen) + 15) & ~(size_t)15) + (size_t)bd.R * 4 + (size_t)bd.R * 16;
+}
+static size_t beam_finalize_lds(const BeamDims& bd) {
+  return ((hyp_lds_bytes(bd.R, bd.maxlen) + 15) & ~(size_t)15) + (size_t)bd.nret * 4 +
+         (size_t)bd.R * bd.maxlen * 4 + (size_t)(bd.R + 2) * 4 +   // + the staged beam rows and scores
+         (size_t)(2 * bd.R + 2) * 12 + 16;                         // + all scores (double) and survivor slots
+}
+
 static int check_beam_dims(const BeamDims& bd, int max_length) {
-  GDR_CHECK_ARG(bd.B > 0 && bd.R >= 2 && bd.R <= 256, "beam: B=%d num_beams=%d (need 2..256)", bd.B, bd.R);
+  GDR_CHECK_ARG(bd.B > 0 && bd.R >= 2 && bd.R <= GDR_MAX_BEAMS, "beam: B=%d num_beams=%d (need 2..%d)", bd.B, bd.R, GDR_MAX_BEAMS);
   GDR_CHECK_ARG(bd.nret >= 1 && bd.nret <= bd.R, "beam: num_return_sequences=%d must be in [1,num_beams]", bd.nret);
   GDR_CHECK_ARG(max_length >= 2 && max_length <= MAXLEN_CAP, "beam: max_length=%d must be in [2,%d]", max_length,
                 MAXLEN_CAP);
   GDR_CHECK_ARG(bd.V >= 1 && bd.Vd >= bd.V * (max_length - 1) + 2, "beam: decode vocab %d too small for V=%d, max_length=%d",
                 bd.Vd, bd.V, max_length);
-  GDR_CHECK_ARG(bd.R * (bd.V + 1) <= 8192, "beam: num_beams*(V+1)=%d exceeds the 8192-entry sort buffer", bd.R * (bd.V + 1));
+  GDR_CHECK_ARG((int64_t)bd.R * (bd.V + 1) <= BEAM_MAX_CAND, "beam: num_beams*(V+1)=%lld exceeds the %d candidates per query of the select",
+                (long long)bd.R * (bd.V + 1), BEAM_MAX_CAND);
   GDR_CHECK_ARG(bd.lp > 0.0, "beam: length_penalty must be > 0");
+  // the hypothesis heap of a query (R+1 entries of max_length tokens) lives in one workgroup's LDS, beside the finalisation's staged
+  // beam rows: 64 bytes are left for the kernels' static words
+  const size_t heap = beam_update_lds(bd) > beam_finalize_lds(bd) ? beam_update_lds(bd) : beam_finalize_lds(bd);
+  GDR_CHECK_ARG(heap + 64 <= (size_t)BEAM_LDS_LIMIT,
+                "beam: num_beams=%d at max_length=%d needs %zu B of LDS for a query's hypothesis heap (limit %d): fewer beams or a shorter max_length",
+                bd.R, max_length, heap + 64, BEAM_LDS_LIMIT);
   return GDR_OK;
 }
 
 // One decode step's beam machinery after bb.logits holds the step's unmasked-column logits.
 static int beam_step(const BeamBufs& bb, const BeamDims& bd, int pos, int cur, float* step_scores,
                      int32_t* step_tokens, hipStream_t stream, bool bcast = false) {
-  const int npad = next_pow2i(bd.R * (bd.V + 1));
-  const size_t lds = (size_t)npad * 8 + (size_t)bd.R * 8 + (size_t)bd.R * (bd.V + 1) * 4;
   const size_t tr = (size_t)pos * bd.B * 2 * bd.R;
-  hipLaunchKernelGGL(beam_topk_kernel, dim3(bd.B), dim3(npad >= 2048 ? 1024 : 256), lds, stream, bb, bd, pos, npad, cur,
-                     bcast ? 1 : 0, step_scores ? step_scores + tr : nullptr, step_tokens ? step_tokens + tr : nullptr);
-  GDR_CHECK_LAUNCH("beam_topk_kernel");
-  const size_t hyp_lds = ((hyp_lds_bytes(bd.R, bd.maxlen) + 15) & ~(size_t)15) + (size_t)bd.R * 4 + (size_t)bd.R * 16;
+  float* tr_s = step_scores ? step_scores + tr : nullptr;
+  int32_t* tr_t = step_tokens ? step_tokens + tr : nullptr;
+  if (!beam_chunked(bd.R, bd.V)) {
+    const int npad = next_pow2i(bd.R * (bd.V + 1));
+    const size_t lds = (size_t)npad * 8 + (size_t)bd.R * 8 + (size_t)bd.R * (bd.V + 1) * 4;
+    hipLaunchKernelGGL(beam_topk_kernel, dim3(bd.B), dim3(npad >= 2048 ? 1024 : 256), lds, stream, bb, bd, pos, npad, cur,
+                       bcast ? 1 : 0, tr_s, tr_t);
+    GDR_CHECK_LAUNCH("beam_topk_kernel");
+  } else {
+    const int nchunks = beam_chunks(bd.R, bd.V), fan = beam_merge_fan(bd.R), keep = 2 * bd.R;
+    hipLaunchKernelGGL(beam_norm_kernel, dim3(bd.B, (bd.R + 3) / 4), dim3(256), 0, stream, bb, bd, bcast ? 1 : 0);
+    GDR_CHECK_LAUNCH("beam_norm_kernel");
+    hipLaunchKernelGGL(beam_chunk_kernel, dim3(bd.B, nchunks), dim3(1024), 0, stream, bb, bd, pos, cur, bcast ? 1 : 0, nchunks);
+    GDR_CHECK_LAUNCH("beam_chunk_kernel");
+    int n_in = nchunks, side = 0;  // at most 3 rounds: 32 chunks, 4 lists per workgroup at 1024 beams
+    for (;;) {
+      const int n_out = (n_in + fan - 1) / fan, final = n_out == 1 ? 1 : 0;
+      const int npad = next_pow2i((n_in < fan ? n_in : fan) * keep);
+      hipLaunchKernelGGL(beam_merge_kernel, dim3(bd.B, n_out), dim3(npad >= 2048 ? 1024 : 256), (size_t)npad * 8, stream, bb, bd,
+                         bb.part[side], n_in, fan, npad, bb.part[side ^ 1], n_out, final, tr_s, tr_t);
+      GDR_CHECK_LAUNCH("beam_merge_kernel");
+      if (final) break;
+      n_in = n_out, side ^= 1;
+    }
+  }
+  const size_t hyp_lds = beam_update_lds(bd);
   hipLaunchKernelGGL(beam_update_kernel, dim3(bd.B), dim3(256), hyp_lds, stream, bb, bd, pos + 1, cur);
   GDR_CHECK_LAUNCH("beam_update_kernel");
   return GDR_OK;  // the ancestor table of the next position is rebuilt at the end of beam_update_kernel
@@ -897,8 +1088,12 @@ static int beam_step(const BeamBufs& bb, const BeamDims& bd, int pos, int cur, f
 
 static int beam_begin(const BeamBufs& bb, const BeamDims& bd, hipStream_t stream, bool dedup0 = false) {
   const int rows = bd.B * bd.R;
-  if (int rc__ = ensure_dyn_lds(reinterpret_cast<const void*>(beam_topk_kernel), 96 * 1024, "beam")) return rc__;
-  if (int rc__ = ensure_dyn_lds(reinterpret_cast<const void*>(beam_finalize_kernel), 96 * 1024, "beam")) return rc__;
+  // 1024 beams: the one-sort form's keys + staged logits reach 104 KiB (7 columns), a query's hypothesis heap whatever
+  // check_beam_dims lets through
+  if (int rc__ = ensure_dyn_lds(reinterpret_cast<const void*>(beam_topk_kernel), BEAM_LDS_LIMIT, "beam")) return rc__;
+  if (int rc__ = ensure_dyn_lds(reinterpret_cast<const void*>(beam_update_kernel), BEAM_LDS_LIMIT - 64, "beam")) return rc__;
+  if (int rc__ = ensure_dyn_lds(reinterpret_cast<const void*>(beam_finalize_kernel), BEAM_LDS_LIMIT - 64, "beam")) return rc__;
+  if (int rc__ = ensure_dyn_lds(reinterpret_cast<const void*>(beam_merge_kernel), BEAM_SORT_MAX * 8, "beam")) return rc__;
   hipLaunchKernelGGL(beam_init_kernel, dim3((rows + 255) / 256), dim3(256), 0, stream, bb, bd, dedup0 ? 1 : 0);
   GDR_CHECK_LAUNCH("beam_init_kernel");
   return GDR_OK;
@@ -906,9 +1101,7 @@ static int beam_begin(const BeamBufs& bb, const BeamDims& bd, hipStream_t stream
 
 static int beam_end(const BeamBufs& bb, const BeamDims& bd, int max_length, int cur, int64_t* out_ids,
                     int32_t* out_len, double* out_scores, hipStream_t stream) {
-  const size_t hyp_lds = ((hyp_lds_bytes(bd.R, bd.maxlen) + 15) & ~(size_t)15) + (size_t)bd.nret * 4 +
-                         (size_t)bd.R * bd.maxlen * 4 + (size_t)(bd.R + 2) * 4 +   // + the staged beam rows and scores
-                         (size_t)(2 * bd.R + 2) * 12 + 16;                         // + all scores (double) and survivor slots
+  const size_t hyp_lds = beam_finalize_lds(bd);
   hipLaunchKernelGGL(beam_finalize_kernel, dim3(bd.B), dim3(256), hyp_lds, stream, bb, bd, max_length, cur, max_length, out_ids,
                      out_len, out_scores);
   GDR_CHECK_LAUNCH("beam_finalize_kernel");

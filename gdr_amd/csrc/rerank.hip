@@ -28,7 +28,7 @@
 namespace gdr {
 
 constexpr int RR_MAX_CAND = 8192;
-constexpr int RR_MAX_BEAMS = 1024;
+constexpr int RR_MAX_BEAMS = GDR_MAX_BEAMS;  // common.h: the beam decode's ceiling
 constexpr int RR_CH = 16;  // candidates per workgroup of the dot pass: 4 waves x 4 rows in flight each
 // the long-list select (rerank_chunk_kernel / rerank_merge_kernel)
 constexpr int RR_LONG_MAX_CAND = 1 << 20;

@@ -645,7 +645,17 @@ size_t gdr_t5_generate_workspace_bytes(const GdrT5DecoderWeights* w, int B, int 
  * out_len int32[B*nret] (= len(hyp), EOS excluded), out_scores fp64[B*nret] (sum_logprobs / len^length_penalty,
  * computed in double like the reference's Python floats).  Optional trace (NULL to skip):
  * step_scores fp32[max_length-1, B, 2R], step_tokens int32[...] = the per-step topk(2R) (generation_utils.py:775).
- * 2 <= num_beams <= 256, num_return_sequences <= num_beams, max_length <= max_out_len. */
+ * 2 <= num_beams <= 1024 (what the stage behind it takes: gdr_rerank_topk / gdr_cluster_candidates), num_beams * (V+1) <= 131072
+ * candidates per query and step, num_return_sequences <= num_beams, max_length <= max_out_len (<= 32).
+ *   The top-2*num_beams of a step: ONE sort of the query's candidates in LDS while num_beams * (V+1) <= 8192; above, chunks of
+ *   4096 candidate positions are sorted on their own and their first 2*num_beams merged in rounds of up to 8192 / (2*num_beams)
+ *   lists — the same list bit for bit (distinct keys: the top of a list is the top of its pieces' tops).  The environment switch
+ *   GDR_DECODE_BEAM_CHUNKED=1 (read once per process; an exact A/B knob, nothing in the product sets it) takes the chunked form
+ *   at every size; gdr_t5_generate_workspace_bytes / gdr_beam_search_table_workspace_bytes account for it (the chunked form adds
+ *   its partial lists; a call that stays in the one-sort form needs what it always needed).
+ *   A query's hypothesis heap (num_beams + 1 entries of max_length tokens) and, at the end, its open beam rows live in one
+ *   workgroup's LDS (160 KiB): roughly num_beams * (8 * max_length + 32) bytes.  1024 beams fit up to max_length = 13, 512 beams
+ *   up to 32; a combination that does not fit is refused with GDR_EINVAL naming num_beams and max_length before any launch. */
 int gdr_t5_generate(const GdrT5DecoderWeights* w, const float* enc_hidden, const int64_t* enc_mask, int B, int L,
                     int num_beams, int max_length, double length_penalty, int num_return_sequences,
                     const GdrTrie* trie, const GdrPrefixTable* prefix_table /* NULL: compute every row */, int64_t* out_ids,
@@ -689,7 +699,8 @@ int gdr_t5_prefix_table_build_bf16(const GdrT5DecoderWeights* w, int n_levels, c
 
 /* The same device beam search driven by a logit table instead of the model (teacher forcing):
  * logits(prefix) = table[b, pos, last_token, :] (fp32 [B, max_length, Vd, Vd]) with the positional mask.
- * Exercises EOS / early-done / eviction paths that random weights never reach. */
+ * Exercises EOS / early-done / eviction paths that random weights never reach.  num_beams, num_beams * (out_vocab+1) and
+ * max_length obey gdr_t5_generate's rules (the chunked select and GDR_DECODE_BEAM_CHUNKED included). */
 size_t gdr_beam_search_table_workspace_bytes(int B, int num_beams, int max_length, int out_vocab);
 int gdr_beam_search_table(const float* table, int B, int out_vocab, int num_beams, int max_length,
                           double length_penalty, int num_return_sequences, const GdrTrie* trie, int64_t* out_ids,
