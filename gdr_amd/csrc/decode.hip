@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "layers.h"
+#include "select.h"
 
 namespace gdr {
 
@@ -80,15 +81,12 @@ struct BeamDims {
   int trie_nodes;
 };
 
-// ---- the top-2R select of a step: one LDS sort per query while its R*(V+1) candidates fit BEAM_SORT_MAX keys, above that (or
-// with GDR_DECODE_BEAM_CHUNKED=1, an exact A/B knob nothing in the product sets) chunks of BEAM_CHUNK candidate positions are
-// sorted on their own and their first 2R keys merged — the same list bit for bit (beam_chunk_kernel).
-constexpr int BEAM_SORT_MAX = 8192;    // keys of one LDS sort (beam_topk_kernel, a beam_merge_kernel workgroup)
-constexpr int BEAM_CHUNK = 4096;       // candidate positions per chunk workgroup: 32 KiB of keys
+// ---- the top-2R select of a step: one LDS sort per query while its R*(V+1) candidates fit SEL_SORT_MAX keys, above that (or
+// with GDR_DECODE_BEAM_CHUNKED=1, an exact A/B knob nothing in the product sets) chunks of SEL_CHUNK candidate positions are
+// sorted on their own and their first 2R keys merged — the same list bit for bit (beam_chunk_kernel, select.h's merge rounds).
 constexpr int BEAM_MAX_CAND = 1 << 17; // num_beams * (V+1): 1024 beams up to V = 127; flat indices stay far inside 32 bits
 constexpr int BEAM_LDS_LIMIT = 160 * 1024;  // LDS of a CU = the most one workgroup may hold (static + dynamic)
-static_assert(2 * GDR_MAX_BEAMS <= BEAM_CHUNK && BEAM_SORT_MAX / (2 * GDR_MAX_BEAMS) >= 2,
-              "a chunk keeps 2R keys; a merge round must shrink the list count");
+static_assert(2 * GDR_MAX_BEAMS <= SEL_MAX_KEEP, "select.h's merge rounds are sized for lists of up to SEL_MAX_KEEP keys");
 
 static bool beam_chunked_forced() {
   static const bool on = [] {
@@ -97,10 +95,8 @@ static bool beam_chunked_forced() {
   }();
   return on;
 }
-static bool beam_chunked(int R, int V) { return beam_chunked_forced() || (int64_t)R * (V + 1) > BEAM_SORT_MAX; }
-static int beam_chunks(int R, int V) { return (int)(((int64_t)R * (V + 1) + BEAM_CHUNK - 1) / BEAM_CHUNK); }
-// partial lists (2R keys each) one merge workgroup sorts; >= 4 for every accepted R (the size functions take any R)
-static int beam_merge_fan(int R) { return BEAM_SORT_MAX / (2 * R) > 2 ? BEAM_SORT_MAX / (2 * R) : 2; }
+static bool beam_chunked(int R, int V) { return beam_chunked_forced() || (int64_t)R * (V + 1) > SEL_SORT_MAX; }
+static int beam_chunks(int R, int V) { return (int)(((int64_t)R * (V + 1) + SEL_CHUNK - 1) / SEL_CHUNK); }
 
 static size_t carve(size_t& o, size_t bytes) {
   const size_t at = o;
@@ -145,7 +141,8 @@ static size_t beam_layout(const BeamDims& bd, char* base, BeamBufs* bb) {
   CARVE(live, int32_t, 1);
   // the chunked select's scratch: nothing (zero bytes, the offsets above unchanged) for a call that stays in the one-sort form
   const bool chunked = beam_chunked(bd.R, bd.V);
-  const size_t lists = chunked ? (size_t)beam_chunks(bd.R, bd.V) : 0, fan = beam_merge_fan(bd.R);
+  // a merge workgroup sorts `fan` partial lists of 2R keys: >= 4 for every accepted R (the size functions take any R)
+  const size_t lists = chunked ? (size_t)beam_chunks(bd.R, bd.V) : 0, fan = sel_merge_fan(2 * bd.R);
   CARVE(lse, float, chunked ? rows * 2 : 0);
   CARVE(part[0], unsigned long long, (size_t)bd.B * lists * 2 * bd.R);
   CARVE(part[1], unsigned long long, (size_t)bd.B * ((lists + fan - 1) / fan) * 2 * bd.R);
@@ -174,14 +171,6 @@ __global__ void beam_init_kernel(BeamBufs bb, BeamDims bd, int dedup0) {
     bb.done[r] = 0;
   }
   if (r == 0) *bb.n_done = 0, *bb.live = 1;
-}
-
-__device__ __forceinline__ uint32_t dfkey(float v) {
-  const uint32_t u = __float_as_uint(v);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float dfkey_inv(uint32_t k) {
-  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
 }
 
 // logits[r][c] = sum_i (h[r][i] * d^-0.5) * (A[r][c*d + i] + E[c][i])      (modeling_t5.py:1575-1576,1637-1639)
@@ -386,13 +375,29 @@ __global__ void table_logits_kernel(const float* __restrict__ table, const int64
   logits[item] = table[(((size_t)b * maxlen + pos) * Vd + (size_t)cur_tok[r]) * Vd + tok];
 }
 
-// LDS operations of one wave execute in order: between steps that only exchange data inside a wave this wave-level barrier
-// (plus fences for the compiler) is all the synchronisation needed.
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
+// The first `keep` = 2R of a query's sorted keys -> cand_score / cand_idx [B][2R] and, when wanted, the step's trace.  What the one-sort
+// select and the last merge round of the chunked one (select.h sel_merge_kernel; its lane is the query) both end with.
+struct BeamEmit {
+  const int32_t* live_gate;
+  float* cand_score;
+  int32_t* cand_idx;
+  float* step_scores;
+  int32_t* step_tokens;
+  __device__ bool skip() const { return live_gate && *live_gate == 0; }  // every query is done, nothing is ranked any more
+  __device__ void operator()(int b, const unsigned long long* keys, int /*npad*/, int keep) const {
+    const int nthr = blockDim.x;
+    for (int i = threadIdx.x; i < keep; i += nthr) {
+      const float s = sel_score(keys[i]);
+      const int32_t flat = (int32_t)sel_low(keys[i]);
+      cand_score[(size_t)b * keep + i] = s;
+      cand_idx[(size_t)b * keep + i] = flat;
+      if (step_scores) {
+        step_scores[(size_t)b * keep + i] = s;
+        step_tokens[(size_t)b * keep + i] = flat;
+      }
+    }
+  }
+};
 
 // Per query: log_softmax of every beam's row (masked columns contribute exp(-1e9 - max) = 0 exactly), add the
 // beam score, take the 2R best of the R*(V+1) unmasked candidates, sorted (generation_utils.py:698,766-775).
@@ -437,7 +442,7 @@ __global__ __launch_bounds__(1024) void beam_topk_kernel(BeamBufs bb, BeamDims b
       }
       const int tok = c < bd.V ? pos * bd.V + 2 + c : EOS_ID;
       const uint32_t flat = (uint32_t)(j * bd.Vd + tok);
-      key = ((unsigned long long)dfkey(s) << 32) | (unsigned long long)(0xFFFFFFFFu - flat);
+      key = sel_pack(s, flat);
     }
     keys[e] = key;
   }
@@ -458,12 +463,7 @@ __global__ __launch_bounds__(1024) void beam_topk_kernel(BeamBufs bb, BeamDims b
     unsigned long long* blk = keys + wave * epw;
     for (int size = 2; size <= epw; size <<= 1) {
       for (int stride = size >> 1; stride > 0; stride >>= 1) {
-        for (int q = lane; q < (epw >> 1); q += 64) {
-          const int lo = (q / stride) * (stride << 1) + (q % stride), hi = lo + stride;
-          const bool desc = ((lo & size) == 0);
-          const unsigned long long x = blk[lo], y = blk[hi];
-          if ((x < y) == desc) blk[lo] = y, blk[hi] = x;
-        }
+        for (int q = lane; q < (epw >> 1); q += 64) sel_cmpx(blk, q, stride, size);
         wave_sync();
       }
     }
@@ -477,102 +477,28 @@ __global__ __launch_bounds__(1024) void beam_topk_kernel(BeamBufs bb, BeamDims b
         }
         wave_sync();
         for (int stride = epw >> 1; stride > 0; stride >>= 1) {
-          for (int q = lane; q < (epw >> 1); q += 64) {
-            const int lo = (q / stride) * (stride << 1) + (q % stride), hi = lo + stride;
-            const unsigned long long x = blk[lo], y = blk[hi];
-            if (x < y) blk[lo] = y, blk[hi] = x;
-          }
+          for (int q = lane; q < (epw >> 1); q += 64) sel_cmpx(blk, q, stride, 0);
           wave_sync();
         }
       }
     }
   } else {
-  for (int size = 2; size <= npad; size <<= 1) {
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      if (2 * stride <= epw) {
-        for (int q = lane; q < (epw >> 1); q += 64) {
-          const int t = (epw >> 1) * wave + q;
-          const int lo = (t / stride) * (stride << 1) + (t % stride), hi = lo + stride;
-          const bool desc = ((lo & size) == 0);
-          const unsigned long long x = keys[lo], y = keys[hi];
-          if ((x < y) == desc) {
-            keys[lo] = y;
-            keys[hi] = x;
-          }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      } else {
-        __syncthreads();
-        for (int t = tid; t < (npad >> 1); t += nthr) {
-          const int lo = (t / stride) * (stride << 1) + (t % stride), hi = lo + stride;
-          const bool desc = ((lo & size) == 0);
-          const unsigned long long x = keys[lo], y = keys[hi];
-          if ((x < y) == desc) {
-            keys[lo] = y;
-            keys[hi] = x;
-          }
-        }
-        __syncthreads();
-      }
-    }
-  }
+    bitonic_stages(keys, npad, nthr);
   }
   __syncthreads();
-  for (int i = tid; i < 2 * R; i += nthr) {
-    const unsigned long long key = keys[i];
-    const float s = dfkey_inv((uint32_t)(key >> 32));
-    const int32_t flat = (int32_t)(0xFFFFFFFFu - (uint32_t)(key & 0xFFFFFFFFull));
-    bb.cand_score[(size_t)b * 2 * R + i] = s;
-    bb.cand_idx[(size_t)b * 2 * R + i] = flat;
-    if (step_scores) {
-      step_scores[(size_t)b * 2 * R + i] = s;
-      step_tokens[(size_t)b * 2 * R + i] = flat;
-    }
-  }
+  BeamEmit{nullptr, bb.cand_score, bb.cand_idx, step_scores, step_tokens}(b, keys, npad, 2 * R);  // the gate was taken above: only the write-out
 }
 
-// ---- the chunked select (R*(V+1) > BEAM_SORT_MAX candidates per query, or forced) ---------------------------------------------
+// ---- the chunked select (R*(V+1) > SEL_SORT_MAX candidates per query, or forced) ---------------------------------------------
 // Three kinds of launches leave in cand_score / cand_idx (and the trace) what beam_topk_kernel leaves, bit for bit:
 //   beam_norm_kernel   every beam row's max and log-sum-exp — a wave per row with beam_topk_kernel's lane assignment and order, so
 //                      the log-probabilities get the same bits;
-//   beam_chunk_kernel  a workgroup per (chunk of BEAM_CHUNK candidate positions, query) builds beam_topk_kernel's keys for its
+//   beam_chunk_kernel  a workgroup per (chunk of SEL_CHUNK candidate positions, query) builds beam_topk_kernel's keys for its
 //                      positions (key 0 past the query's last candidate), sorts them and files its first 2R;
-//   beam_merge_kernel  a workgroup per (group of lists, query) sorts the group's keys and files the first 2R; the round that is left
-//                      with one list per query writes the result instead.
+//   sel_merge_kernel   (select.h) a workgroup per (group of lists, query) sorts the group's keys and files the first 2R; the round
+//                      that is left with one list per query writes the result instead (BeamEmit).
 // The keys are distinct (the flat index is the low word), so their order is total: the first 2R of the whole list are the first 2R
 // of the chunks' first 2R, whatever the grouping.  No atomics, nothing depends on the order workgroups run in.
-
-// Bitonic sort of n keys in LDS (n a power of two >= 64, a multiple of 2 * the workgroup's waves), descending; the whole workgroup
-// calls it after a barrier behind the last store to keys[], and meets a barrier before it reads the result.  Stages whose pairs
-// stay inside one wave's block of n / nwaves keys cost a wave barrier only (LDS operations of a wave execute in order).
-__device__ __forceinline__ void beam_bitonic_desc(unsigned long long* keys, int n, int tid, int nthr) {
-  const int wave = tid >> 6, lane = tid & 63, epw = n / (nthr >> 6);
-  for (int size = 2; size <= n; size <<= 1) {
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      if (2 * stride <= epw) {
-        for (int q = lane; q < (epw >> 1); q += 64) {
-          const int t = (epw >> 1) * wave + q;
-          const int lo = (t / stride) * (stride << 1) + (t % stride), hi = lo + stride;
-          const bool desc = ((lo & size) == 0);
-          const unsigned long long x = keys[lo], y = keys[hi];
-          if ((x < y) == desc) keys[lo] = y, keys[hi] = x;
-        }
-        wave_sync();
-      } else {
-        __syncthreads();
-        for (int t = tid; t < (n >> 1); t += nthr) {
-          const int lo = (t / stride) * (stride << 1) + (t % stride), hi = lo + stride;
-          const bool desc = ((lo & size) == 0);
-          const unsigned long long x = keys[lo], y = keys[hi];
-          if ((x < y) == desc) keys[lo] = y, keys[hi] = x;
-        }
-        __syncthreads();
-      }
-    }
-  }
-}
 
 __global__ __launch_bounds__(256) void beam_norm_kernel(BeamBufs bb, BeamDims bd, int bcast) {
   if (bb.live_gate && *bb.live_gate == 0) return;
@@ -593,12 +519,12 @@ __global__ __launch_bounds__(256) void beam_norm_kernel(BeamBufs bb, BeamDims bd
 }
 
 __global__ __launch_bounds__(1024) void beam_chunk_kernel(BeamBufs bb, BeamDims bd, int pos, int cur, int bcast, int nchunks) {
-  __shared__ __attribute__((aligned(16))) unsigned long long keys[BEAM_CHUNK];
+  __shared__ __attribute__((aligned(16))) unsigned long long keys[SEL_CHUNK];
   if (bb.live_gate && *bb.live_gate == 0) return;
   const int b = blockIdx.x, ch = blockIdx.y, tid = threadIdx.x;
   const int R = bd.R, V1 = bd.V + 1, ncand = R * V1, keep = 2 * R;
-  for (int i = tid; i < BEAM_CHUNK; i += 1024) {
-    const int e = ch * BEAM_CHUNK + i;
+  for (int i = tid; i < SEL_CHUNK; i += 1024) {
+    const int e = ch * SEL_CHUNK + i;
     unsigned long long key = 0ull;
     if (e < ncand) {
       const int j = e / V1, c = e - j * V1;
@@ -613,48 +539,14 @@ __global__ __launch_bounds__(1024) void beam_chunk_kernel(BeamBufs bb, BeamDims 
       }
       const int tok = c < bd.V ? pos * bd.V + 2 + c : EOS_ID;
       const uint32_t flat = (uint32_t)(j * bd.Vd + tok);
-      key = ((unsigned long long)dfkey(s) << 32) | (unsigned long long)(0xFFFFFFFFu - flat);
+      key = sel_pack(s, flat);
     }
     keys[i] = key;
   }
   __syncthreads();
-  beam_bitonic_desc(keys, BEAM_CHUNK, tid, 1024);
-  __syncthreads();
+  bitonic_desc(keys, SEL_CHUNK, 1024);
   unsigned long long* dst = bb.part[0] + ((size_t)b * nchunks + ch) * keep;
   for (int i = tid; i < keep; i += 1024) dst[i] = keys[i];
-}
-
-// in: [B][n_in][2R] sorted lists; workgroup (b, g) takes lists g*fan .. of query b.  final: n_in <= fan, one workgroup per query.
-__global__ __launch_bounds__(1024) void beam_merge_kernel(BeamBufs bb, BeamDims bd, const unsigned long long* __restrict__ in,
-                                                         int n_in, int fan, int npad, unsigned long long* __restrict__ out,
-                                                         int n_out, int final, float* __restrict__ step_scores,
-                                                         int32_t* __restrict__ step_tokens) {
-  extern __shared__ __attribute__((aligned(16))) unsigned long long keys[];  // [npad]
-  if (bb.live_gate && *bb.live_gate == 0) return;
-  const int b = blockIdx.x, g = blockIdx.y, tid = threadIdx.x, nthr = blockDim.x;
-  const int keep = 2 * bd.R;
-  const int l0 = g * fan, nl = min(fan, n_in - l0), have = nl * keep;
-  const unsigned long long* src = in + ((size_t)b * n_in + l0) * keep;
-  for (int i = tid; i < npad; i += nthr) keys[i] = i < have ? src[i] : 0ull;
-  __syncthreads();
-  beam_bitonic_desc(keys, npad, tid, nthr);
-  __syncthreads();
-  if (!final) {
-    unsigned long long* dst = out + ((size_t)b * n_out + g) * keep;
-    for (int i = tid; i < keep; i += nthr) dst[i] = keys[i];
-    return;
-  }
-  for (int i = tid; i < keep; i += nthr) {
-    const unsigned long long key = keys[i];
-    const float s = dfkey_inv((uint32_t)(key >> 32));
-    const int32_t flat = (int32_t)(0xFFFFFFFFu - (uint32_t)(key & 0xFFFFFFFFull));
-    bb.cand_score[(size_t)b * keep + i] = s;
-    bb.cand_idx[(size_t)b * keep + i] = flat;
-    if (step_scores) {
-      step_scores[(size_t)b * keep + i] = s;
-      step_tokens[(size_t)b * keep + i] = flat;
-    }
-  }
 }
 
 // ---- BeamHypotheses of one query, held in LDS by the single wave that serves the query -------------------------------
@@ -1016,12 +908,6 @@ __global__ __launch_bounds__(256) void beam_finalize_kernel(BeamBufs bb, BeamDim
 }
 
 // ------------------------------------------------------------------------------------------ driver pieces
-static int next_pow2i(int x) {
-  int p = 64;
-  while (p < x) p <<= 1;
-  return p;
-}
-
 // dynamic LDS of the two kernels that hold a query's hypothesis heap
 static size_t beam_update_lds(const BeamDims& bd) {
   return ((hyp_lds_bytes(bd.R, bd.maxlen) + 15) & ~(size_t)15) + (size_t)bd.R * 4 + (size_t)bd.R * 16;
@@ -1058,27 +944,20 @@ static int beam_step(const BeamBufs& bb, const BeamDims& bd, int pos, int cur, f
   float* tr_s = step_scores ? step_scores + tr : nullptr;
   int32_t* tr_t = step_tokens ? step_tokens + tr : nullptr;
   if (!beam_chunked(bd.R, bd.V)) {
-    const int npad = next_pow2i(bd.R * (bd.V + 1));
+    const int npad = sel_pow2(bd.R * (bd.V + 1));
     const size_t lds = (size_t)npad * 8 + (size_t)bd.R * 8 + (size_t)bd.R * (bd.V + 1) * 4;
     hipLaunchKernelGGL(beam_topk_kernel, dim3(bd.B), dim3(npad >= 2048 ? 1024 : 256), lds, stream, bb, bd, pos, npad, cur,
                        bcast ? 1 : 0, tr_s, tr_t);
     GDR_CHECK_LAUNCH("beam_topk_kernel");
   } else {
-    const int nchunks = beam_chunks(bd.R, bd.V), fan = beam_merge_fan(bd.R), keep = 2 * bd.R;
+    const int nchunks = beam_chunks(bd.R, bd.V);
     hipLaunchKernelGGL(beam_norm_kernel, dim3(bd.B, (bd.R + 3) / 4), dim3(256), 0, stream, bb, bd, bcast ? 1 : 0);
     GDR_CHECK_LAUNCH("beam_norm_kernel");
     hipLaunchKernelGGL(beam_chunk_kernel, dim3(bd.B, nchunks), dim3(1024), 0, stream, bb, bd, pos, cur, bcast ? 1 : 0, nchunks);
     GDR_CHECK_LAUNCH("beam_chunk_kernel");
-    int n_in = nchunks, side = 0;  // at most 3 rounds: 32 chunks, 4 lists per workgroup at 1024 beams
-    for (;;) {
-      const int n_out = (n_in + fan - 1) / fan, final = n_out == 1 ? 1 : 0;
-      const int npad = next_pow2i((n_in < fan ? n_in : fan) * keep);
-      hipLaunchKernelGGL(beam_merge_kernel, dim3(bd.B, n_out), dim3(npad >= 2048 ? 1024 : 256), (size_t)npad * 8, stream, bb, bd,
-                         bb.part[side], n_in, fan, npad, bb.part[side ^ 1], n_out, final, tr_s, tr_t);
-      GDR_CHECK_LAUNCH("beam_merge_kernel");
-      if (final) break;
-      n_in = n_out, side ^= 1;
-    }
+    // at most 3 rounds: 32 chunks, 4 lists per workgroup at 1024 beams
+    const BeamEmit emit{bb.live_gate, bb.cand_score, bb.cand_idx, tr_s, tr_t};
+    if (int rc__ = sel_merge_rounds(bb.part, nchunks, 2 * bd.R, bd.B, 1, emit, "sel_merge_kernel<beam>", stream)) return rc__;
   }
   const size_t hyp_lds = beam_update_lds(bd);
   hipLaunchKernelGGL(beam_update_kernel, dim3(bd.B), dim3(256), hyp_lds, stream, bb, bd, pos + 1, cur);
@@ -1093,7 +972,7 @@ static int beam_begin(const BeamBufs& bb, const BeamDims& bd, hipStream_t stream
   if (int rc__ = ensure_dyn_lds(reinterpret_cast<const void*>(beam_topk_kernel), BEAM_LDS_LIMIT, "beam")) return rc__;
   if (int rc__ = ensure_dyn_lds(reinterpret_cast<const void*>(beam_update_kernel), BEAM_LDS_LIMIT - 64, "beam")) return rc__;
   if (int rc__ = ensure_dyn_lds(reinterpret_cast<const void*>(beam_finalize_kernel), BEAM_LDS_LIMIT - 64, "beam")) return rc__;
-  if (int rc__ = ensure_dyn_lds(reinterpret_cast<const void*>(beam_merge_kernel), BEAM_SORT_MAX * 8, "beam")) return rc__;
+  if (int rc__ = ensure_dyn_lds(reinterpret_cast<const void*>(sel_merge_kernel<BeamEmit>), SEL_SORT_MAX * 8, "beam")) return rc__;
   hipLaunchKernelGGL(beam_init_kernel, dim3((rows + 255) / 256), dim3(256), 0, stream, bb, bd, dedup0 ? 1 : 0);
   GDR_CHECK_LAUNCH("beam_init_kernel");
   return GDR_OK;

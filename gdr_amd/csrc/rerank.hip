@@ -13,38 +13,31 @@
 //   rerank_select    a workgroup per (alpha, query): softmax of the R length-penalised beam scores (:1598-1601),
 //                    key = orderable(sim + alpha*p[cluster]) << 32 | ~position, one bitonic sort in LDS, first k
 //                    (ties: higher score, then earlier candidate — torch leaves tie order unspecified).
-//   rerank_chunk / rerank_merge   the same select for lists of more than 8 192 candidates (up to 2^20), which no single
+//   rerank_chunk / sel_merge   the same select for lists of more than 8 192 candidates (up to 2^20), which no single
 //                    LDS sort holds.  The keys are a strict total order, so the top-k of a list is the top-k of the union of
 //                    its pieces' top-k whatever the cut: a workgroup per (chunk of 4 096 positions, alpha, query) sorts its
-//                    chunk's keys and keeps the first k, then rounds of the same sort over up to 8 192 / k partial lists
+//                    chunk's keys and keeps the first k, then the merge rounds of select.h over up to 8 192 / k partial lists
 //                    leave one list per (alpha, query) — bit for bit what rerank_select would return from a larger LDS.
 // Sharded corpus (GDR mode): a rank passes its row block [doc_lo, doc_hi) — candidates outside are skipped —
 // and asks for candidate POSITIONS; per-candidate scores do not depend on the shard, and a merge by "higher score, then
 // lower position" (gdr_topk_merge_packed) of the per-shard lists reproduces the unsharded list bit for bit.
 #include <math.h>
 
-#include "common.h"
+#include "select.h"
 
 namespace gdr {
 
-constexpr int RR_MAX_CAND = 8192;
+constexpr int RR_MAX_CAND = 8192;  // = select.h SEL_SORT_MAX (asserted below); spelled out for the binding's test, which evaluates this line
 constexpr int RR_MAX_BEAMS = GDR_MAX_BEAMS;  // common.h: the beam decode's ceiling
 constexpr int RR_CH = 16;  // candidates per workgroup of the dot pass: 4 waves x 4 rows in flight each
-// the long-list select (rerank_chunk_kernel / rerank_merge_kernel)
+// the long-list select (rerank_chunk_kernel, then select.h's merge rounds)
 constexpr int RR_LONG_MAX_CAND = 1 << 20;
-constexpr int RR_LCH = 4096;    // candidate positions per chunk: 32 KiB of keys, two 1024-thread workgroups per CU
+constexpr int RR_LCH = 4096;    // = select.h SEL_CHUNK: candidate positions per chunk
 constexpr int RR_LONG_MAX_K = RR_MAX_BEAMS;
 constexpr int RR_ASLOTS = 8;    // alphas per pass over the partial-list scratch (gdr_rerank_workspace_bytes has no A)
 constexpr int RR_MIN_GROUP = RR_MAX_CAND / RR_LONG_MAX_K;  // partial lists one merge workgroup takes at the largest k
-static_assert(RR_LONG_MAX_K <= RR_LCH && RR_MIN_GROUP >= 2, "a chunk keeps k keys; a merge round must shrink the list count");
-
-__device__ __forceinline__ uint32_t rr_fkey(float v) {
-  const uint32_t u = __float_as_uint(v);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float rr_fkey_inv(uint32_t k) {
-  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
+static_assert(RR_MAX_CAND == SEL_SORT_MAX && RR_LCH == SEL_CHUNK, "the rerank's limits are select.h's");
+static_assert(RR_LONG_MAX_K <= SEL_MAX_KEEP, "select.h's merge rounds are sized for lists of up to SEL_MAX_KEEP keys");
 
 // ---- sim[b][c] = f(q[b] . D[cand c of query b]) ---------------------------------------------------------------------
 // Candidate lists come in two layouts (include/gdr_hip.h): cand_stride == 0 — ONE CSR over all B*R segments, the
@@ -121,40 +114,6 @@ __global__ __launch_bounds__(256) void rerank_dot_kernel(const float* __restrict
   }
 }
 
-// Bitonic sort of npad (power of two) 64-bit keys in LDS, descending.  A wave owns a block of npad / nwaves consecutive
-// keys: every stage whose compare-exchange pairs stay inside a block needs no workgroup barrier (LDS operations of one
-// wave execute in order), so of the 66 stages of a 2048-key sort on 16 waves only the ones with stride >= 64 cost one.
-__device__ __forceinline__ void rr_bitonic_desc(unsigned long long* keys, int npad) {
-  const int tid = threadIdx.x, nthr = blockDim.x, wave = tid >> 6, lane = tid & 63, nwaves = nthr >> 6;
-  const int epw = npad / nwaves;
-  for (int size = 2; size <= npad; size <<= 1) {
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      if (2 * stride <= epw) {
-        for (int p = lane; p < (epw >> 1); p += 64) {
-          const int t = (epw >> 1) * wave + p;
-          const int lo = (t / stride) * (stride << 1) + (t % stride), hi = lo + stride;
-          const bool desc = ((lo & size) == 0);
-          const unsigned long long x = keys[lo], y = keys[hi];
-          if ((x < y) == desc) keys[lo] = y, keys[hi] = x;
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      } else {
-        __syncthreads();
-        for (int t = tid; t < (npad >> 1); t += nthr) {
-          const int lo = (t / stride) * (stride << 1) + (t % stride), hi = lo + stride;
-          const bool desc = ((lo & size) == 0);
-          const unsigned long long x = keys[lo], y = keys[hi];
-          if ((x < y) == desc) keys[lo] = y, keys[hi] = x;
-        }
-        __syncthreads();
-      }
-    }
-  }
-  __syncthreads();
-}
-
 // ---- pieces shared by the one-sort select and the long-list select: they must produce the same bits ----------------
 // softmax over the R beam scores (main_models.py:1598-1601), by ONE wave: the summation order does not depend on the
 // workgroup size
@@ -173,7 +132,7 @@ __device__ __forceinline__ void rr_beam_softmax(const float* __restrict__ bs, in
 }
 // key of candidate position c: s + alpha*p with two roundings as in torch, then "earlier position first"
 __device__ __forceinline__ unsigned long long rr_key(float s0, float ap, int c) {
-  return ((unsigned long long)rr_fkey(__fadd_rn(s0, ap)) << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)c);
+  return sel_pack(__fadd_rn(s0, ap), (uint32_t)c);
 }
 // the first k of the sorted keys -> one (alpha, query) row of out_val / out_idx; key 0 = no candidate: -inf / -1
 __device__ __forceinline__ void rr_write_topk(const unsigned long long* keys, int npad, int k,
@@ -184,8 +143,8 @@ __device__ __forceinline__ void rr_write_topk(const unsigned long long* keys, in
     int32_t id = -1;
     const unsigned long long key = i < npad ? keys[i] : 0ull;
     if (key != 0ull) {
-      v = rr_fkey_inv((uint32_t)(key >> 32));
-      const int c = (int)(0xFFFFFFFFu - (uint32_t)(key & 0xFFFFFFFFull));
+      v = sel_score(key);
+      const int c = (int)sel_low(key);
       id = positions ? c : cand_ids[base + c];
     }
     out_val[i] = v;
@@ -225,7 +184,7 @@ __global__ __launch_bounds__(1024) void rerank_select_kernel(const float* __rest
     }
   }
   __syncthreads();
-  rr_bitonic_desc(keys, npad);
+  bitonic_desc(keys, npad);
   rr_write_topk(keys, npad, k, cand_ids, base, positions, out_val + ((int64_t)b * A + ai) * k,
                 out_idx + ((int64_t)b * A + ai) * k);
 }
@@ -271,44 +230,25 @@ __global__ __launch_bounds__(1024) void rerank_chunk_kernel(const float* __restr
     }
   }
   __syncthreads();
-  rr_bitonic_desc(keys, npad);
+  bitonic_desc(keys, npad);
   for (int i = tid; i < k; i += nthr) dst[i] = i < npad ? keys[i] : 0ull;
 }
 
-// One merge round: a workgroup per (group of up to G consecutive partial lists, alpha, query) sorts the group's keys
-// (G * k <= 8192) and keeps the first k.  src [B][ag][n_in][k] -> dst [B][ag][n_out][k]; the last round (n_out == 1,
-// dst == nullptr) writes alpha a0 + as of out_val / out_idx exactly as rerank_select_kernel does.
-__global__ __launch_bounds__(1024) void rerank_merge_kernel(const unsigned long long* __restrict__ src, int n_in, int G,
-                                                            int n_out, int k, int npad,
-                                                            unsigned long long* __restrict__ dst,
-                                                            const int32_t* __restrict__ cand_offsets,
-                                                            const int32_t* __restrict__ cand_ids, int R, int cand_stride,
-                                                            int positions, int A, int a0, float* __restrict__ out_val,
-                                                            int32_t* __restrict__ out_idx) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  unsigned long long* keys = reinterpret_cast<unsigned long long*>(smem_raw);  // [npad]
-  const int g = blockIdx.x % n_out, as = blockIdx.x / n_out, ag = gridDim.x / n_out, b = blockIdx.y;
-  const int tid = threadIdx.x, nthr = blockDim.x;
-  const int lists = n_in - g * G < G ? n_in - g * G : G;
-  const int cnt = lists * k;  // <= npad
-  const unsigned long long* in = src + (((int64_t)b * ag + as) * n_in + (int64_t)g * G) * k;
-  for (int t = tid; t < npad; t += nthr) keys[t] = t < cnt ? in[t] : 0ull;
-  __syncthreads();
-  rr_bitonic_desc(keys, npad);
-  if (dst != nullptr) {
-    unsigned long long* o = dst + ((int64_t)b * gridDim.x + blockIdx.x) * k;
-    for (int i = tid; i < k; i += nthr) o[i] = i < npad ? keys[i] : 0ull;
-    return;
+// What the last merge round (select.h sel_merge_kernel) does with the one list left per lane = b * ag + alpha slot: alpha
+// a0 + slot of out_val / out_idx, written exactly as rerank_select_kernel writes it.
+struct RrEmit {
+  const int32_t* cand_offsets;
+  const int32_t* cand_ids;
+  int R, cand_stride, positions, A, a0, ag;
+  float* out_val;
+  int32_t* out_idx;
+  __device__ bool skip() const { return false; }
+  __device__ void operator()(int lane, const unsigned long long* keys, int npad, int k) const {
+    const int b = lane / ag, as = lane % ag;
+    rr_write_topk(keys, npad, k, cand_ids, cand_seg(cand_offsets, b, R, cand_stride).base, positions,
+                  out_val + ((int64_t)b * A + a0 + as) * k, out_idx + ((int64_t)b * A + a0 + as) * k);
   }
-  rr_write_topk(keys, npad, k, cand_ids, cand_seg(cand_offsets, b, R, cand_stride).base, positions,
-                out_val + ((int64_t)b * A + a0 + as) * k, out_idx + ((int64_t)b * A + a0 + as) * k);
-}
-
-static int rr_pow2(int n) {  // sort width: the power of two >= n, at least one wave
-  int p = 64;
-  while (p < n) p <<= 1;
-  return p;
-}
+};
 
 // Workspace of the long-list form: sim[B][max_cand], then the chunk pass's partial lists and the lists a merge round
 // writes (the rounds alternate between the two), both for RR_ASLOTS alphas at k = RR_LONG_MAX_K — the sizing call knows
@@ -368,7 +308,7 @@ static int rerank_impl(const float* q, const void* D, bool bf16, int d, const in
   const int positions = (flags & GDR_RERANK_POSITIONS) ? 1 : 0;
   ProfScope prof(PROF_SELECT, 0.0, stream);
   if (!chunked) {
-    const int npad = rr_pow2(max_cand);
+    const int npad = sel_pow2(max_cand);
     const size_t lds = (size_t)npad * 8 + (size_t)R * 4;
     if (int rc__ = ensure_dyn_lds(reinterpret_cast<const void*>(rerank_select_kernel), 80 * 1024, "rerank")) return rc__;
     hipLaunchKernelGGL(rerank_select_kernel, dim3((unsigned)A, (unsigned)B), dim3(npad >= 2048 ? 1024 : 256), lds, stream, sim,
@@ -382,26 +322,17 @@ static int rerank_impl(const float* q, const void* D, bool bf16, int d, const in
   unsigned char* ws = static_cast<unsigned char*>(workspace);
   unsigned long long* part[2] = {reinterpret_cast<unsigned long long*>(ws + plan.sim_bytes),
                                  reinterpret_cast<unsigned long long*>(ws + plan.sim_bytes + plan.part0_bytes)};
-  if (int rc__ = ensure_dyn_lds(reinterpret_cast<const void*>(rerank_merge_kernel), RR_MAX_CAND * 8, "rerank")) return rc__;
-  const int cpad = rr_pow2(max_cand < RR_LCH ? max_cand : RR_LCH);
-  const int G = RR_MAX_CAND / k;  // >= RR_MIN_GROUP
+  if (int rc__ = ensure_dyn_lds(reinterpret_cast<const void*>(sel_merge_kernel<RrEmit>), RR_MAX_CAND * 8, "rerank")) return rc__;
+  const int cpad = sel_pow2(max_cand < RR_LCH ? max_cand : RR_LCH);
   for (int a0 = 0; a0 < A; a0 += RR_ASLOTS) {  // the scratch holds RR_ASLOTS alphas: the groups follow each other on the stream
     const int ag = A - a0 < RR_ASLOTS ? A - a0 : RR_ASLOTS;
     hipLaunchKernelGGL(rerank_chunk_kernel, dim3((unsigned)(plan.nchunk * ag), (unsigned)B), dim3(cpad >= 2048 ? 1024 : 256),
                        (size_t)cpad * 8 + (size_t)R * 4, stream, sim, cand_offsets, beam_scores, R, alphas + a0, k, cpad, plan.nchunk,
                        max_cand, cand_stride, part[0]);
     GDR_CHECK_LAUNCH("rerank_chunk_kernel");
-    int n = plan.nchunk, from = 0;
-    do {
-      const int n_out = (n + G - 1) / G;
-      const int npad = rr_pow2((n < G ? n : G) * k);
-      hipLaunchKernelGGL(rerank_merge_kernel, dim3((unsigned)(n_out * ag), (unsigned)B), dim3(npad >= 2048 ? 1024 : 256),
-                         (size_t)npad * 8, stream, part[from], n, G, n_out, k, npad, n_out == 1 ? nullptr : part[from ^ 1],
-                         cand_offsets, cand_ids, R, cand_stride, positions, A, a0, out_val, out_idx);
-      GDR_CHECK_LAUNCH("rerank_merge_kernel");
-      n = n_out;
-      from ^= 1;
-    } while (n > 1);
+    // a round merges sel_merge_fan(k) = RR_MAX_CAND / k >= RR_MIN_GROUP lists
+    const RrEmit emit{cand_offsets, cand_ids, R, cand_stride, positions, A, a0, ag, out_val, out_idx};
+    if (int rc__ = sel_merge_rounds(part, plan.nchunk, k, ag, B, emit, "sel_merge_kernel<rerank>", stream)) return rc__;
   }
   return GDR_OK;
 }

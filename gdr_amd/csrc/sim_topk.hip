@@ -19,7 +19,7 @@
 // n_sample ≈ sqrt(k·N) balances list length against survivors.  Small corpora take steps 1, 2, 4 only.
 #include <stdlib.h>
 
-#include "common.h"
+#include "select.h"
 
 namespace gdr {
 
@@ -70,14 +70,7 @@ static SimPlan make_plan(int B, int64_t N, int k, bool exhaustive, double surviv
   return p;
 }
 
-// ---- orderable keys --------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t fkey(float v) {
-  const uint32_t u = __float_as_uint(v);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float fkey_inv(uint32_t k) {
-  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
+// (the orderable keys, their 64-bit pack and the bitonic sorts: select.h)
 
 // Given hist[256] (LDS) find the highest bin b with  sum(hist[b..255]) >= need.
 // Returns b and the count strictly above it through *above.  Every thread of the block calls it (blockDim >= 256).
@@ -113,26 +106,6 @@ __device__ __forceinline__ int find_bin(int* hist, int* scan, int& need, int* ab
   return res[0];
 }
 
-// Bitonic sort of kpad <= 1024 64-bit keys in LDS, descending, by the FIRST WAVE alone: LDS operations of one wave execute
-// in order, so the 28 .. 55 stages need no workgroup barrier (one before, one after — the callers').
-__device__ __forceinline__ void wave0_bitonic_desc(unsigned long long* buf, int kpad) {
-  if (threadIdx.x >= 64) return;
-  const int lane = threadIdx.x;
-  for (int size = 2; size <= kpad; size <<= 1) {
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      for (int t = lane; t < (kpad >> 1); t += 64) {
-        const int lo_i = (t / stride) * (stride << 1) + (t % stride), hi_i = lo_i + stride;
-        const bool desc = ((lo_i & size) == 0);
-        const unsigned long long a = buf[lo_i], b = buf[hi_i];
-        if ((a < b) == desc) buf[lo_i] = b, buf[hi_i] = a;
-      }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    }
-  }
-}
-
 // Block-wide min / max of 32-bit keys (red[] holds 2 * 16 words).  Result broadcast to every thread.
 __device__ __forceinline__ void block_minmax(uint32_t& lo, uint32_t& hi, uint32_t* red) {
 #pragma unroll
@@ -152,26 +125,22 @@ __device__ __forceinline__ void block_minmax(uint32_t& lo, uint32_t& hi, uint32_
 // spreads the live range over 256 bins.  Similarity scores share sign and exponent, so digits taken from the raw
 // float bits spend two full sweeps (and ~10^4 same-address LDS atomics each) without separating anything.
 
-// ---- step 2: per-query threshold = k-th largest of the sample scores ----------------------------
-// sub != null (the bf16 pre-filter below): thr[q] = value - sub[q]
-__global__ __launch_bounds__(1024) void sim_threshold_kernel(const float* __restrict__ cand_val, int64_t cap,
-                                                             int n_slots, int k, float* thr, int32_t* cand_cnt,
-                                                             const float* __restrict__ sub) {
-  __shared__ int hist[256];
-  __shared__ int scan[256];
-  __shared__ int res[2];
-  __shared__ uint32_t red[32];
-  const int q = blockIdx.x;
-  const float* v = cand_val + (int64_t)q * cap;
-  // the sample scores are read ONCE: up to RC keys per thread stay in registers across the digit passes (every pass used to
-  // re-read them from memory — a dependent L2 round trip per sweep); longer lists fall back to re-reading
-  constexpr int RC = 8;
-  const bool cached = n_slots <= RC * (int)blockDim.x;
-  uint32_t rk[RC];
+// The 32-bit key (fkey) of the k-th largest of v[0 .. count), -inf entries aside; fkey(-inf) when there is nothing else.  Every
+// thread of the workgroup calls it: nthr = its size as the caller knows it (a literal where the launch fixes it), hist / scan /
+// res / red the caller's LDS words.  The scores are read ONCE: up to RC keys per thread stay in rk[] across the digit passes
+// (every pass used to re-read them from memory — a dependent L2 round trip per sweep) and are the caller's afterwards — rk[u] is
+// the key of v[tid + u * nthr], 0 for "no entry" (fkey(-inf) = 0x007fffff > 0), all 0 when count > RC * nthr: such lists are
+// re-read on every pass, by loops unrolled UNROLL times (4: sim_threshold_kernel's pragma; 1: what the compiler chose for the
+// pre-filter tail, which had none).  cached says which of the two it was, for a caller that goes on using rk[].
+template <int UNROLL, int RC>
+__device__ __forceinline__ uint32_t radix_kth_key(const float* __restrict__ v, int count, int k, int nthr, uint32_t (&rk)[RC],
+                                                  bool& cached, int* hist, int* scan, int* res, uint32_t* red) {
+  const int tid = threadIdx.x;
+  cached = count <= RC * nthr;
 #pragma unroll
   for (int u = 0; u < RC; ++u) {
-    const int i = threadIdx.x + u * (int)blockDim.x;
-    rk[u] = (cached && i < n_slots) ? fkey(v[i]) : 0u;  // fkey(-inf) = 0x007fffff > 0: 0 marks "no entry"
+    const int i = tid + u * nthr;
+    rk[u] = (cached && i < count) ? fkey(v[i]) : 0u;
   }
   const uint32_t kneg = fkey(-INFINITY);
   uint32_t lo = 0xFFFFFFFFu, hi = 0u;  // range of the real scores; -inf padding slots of a ragged tile stay below it
@@ -180,8 +149,8 @@ __global__ __launch_bounds__(1024) void sim_threshold_kernel(const float* __rest
     for (int u = 0; u < RC; ++u)
       if (rk[u] > kneg) lo = min(lo, rk[u]), hi = max(hi, rk[u]);
   } else {
-#pragma unroll 4
-    for (int i = threadIdx.x; i < n_slots; i += blockDim.x) {
+#pragma unroll UNROLL
+    for (int i = tid; i < count; i += nthr) {
       const float x = v[i];
       if (x > -INFINITY) {
         const uint32_t key = fkey(x);
@@ -190,14 +159,14 @@ __global__ __launch_bounds__(1024) void sim_threshold_kernel(const float* __rest
     }
   }
   block_minmax(lo, hi, red);
-  if (hi < lo) lo = hi = fkey(-INFINITY);  // nothing but padding
+  if (hi < lo) lo = hi = kneg;  // nothing but padding
   const int nbits = hi > lo ? 32 - __clz(hi - lo) : 0;
   const int lsh = 32 - nbits;  // nbits == 0: every key equal, no pass runs
   uint32_t prefix = 0;
   int need = k;
   for (int pass = 0; 8 * pass < nbits; ++pass) {
     const int shift = 24 - 8 * pass;
-    if (threadIdx.x < 256) hist[threadIdx.x] = 0;
+    if (tid < 256) hist[tid] = 0;
     __syncthreads();
     if (cached) {
 #pragma unroll
@@ -208,8 +177,8 @@ __global__ __launch_bounds__(1024) void sim_threshold_kernel(const float* __rest
         if (raw != 0u && match && raw >= lo) atomicAdd(&hist[(key >> shift) & 255u], 1);
       }
     } else {
-#pragma unroll 4
-      for (int i = threadIdx.x; i < n_slots; i += blockDim.x) {
+#pragma unroll UNROLL
+      for (int i = tid; i < count; i += nthr) {
         const uint32_t raw = fkey(v[i]);
         const uint32_t key = (raw - lo) << lsh;
         const bool match = pass == 0 ? true : ((key >> (shift + 8)) == (prefix >> (shift + 8)));
@@ -223,8 +192,24 @@ __global__ __launch_bounds__(1024) void sim_threshold_kernel(const float* __rest
     prefix |= (uint32_t)b << shift;
     __syncthreads();
   }
+  return nbits ? (prefix >> lsh) + lo : lo;
+}
+
+// ---- step 2: per-query threshold = k-th largest of the sample scores ----------------------------
+// sub != null (the bf16 pre-filter below): thr[q] = value - sub[q]
+__global__ __launch_bounds__(1024) void sim_threshold_kernel(const float* __restrict__ cand_val, int64_t cap,
+                                                             int n_slots, int k, float* thr, int32_t* cand_cnt,
+                                                             const float* __restrict__ sub) {
+  __shared__ int hist[256];
+  __shared__ int scan[256];
+  __shared__ int res[2];
+  __shared__ uint32_t red[32];
+  const int q = blockIdx.x;
+  uint32_t rk[8];
+  bool cached;
+  const uint32_t kth = radix_kth_key<4>(cand_val + (int64_t)q * cap, n_slots, k, (int)blockDim.x, rk, cached, hist, scan, res, red);
   if (threadIdx.x == 0) {
-    const float t = fkey_inv(nbits ? (prefix >> lsh) + lo : lo);
+    const float t = fkey_inv(kth);
     thr[q] = sub ? t - sub[q] : t;
     cand_cnt[(int64_t)q * CNT_STRIDE] = n_slots;  // survivors of the filter pass are appended behind the sample block
   }
@@ -280,7 +265,7 @@ __global__ __launch_bounds__(1024) void topk_select_kernel(const float* __restri
     const int64_t a = addr_of(i);
     const int32_t id = idxs[a];
     if (id < 0) return 0ull;
-    return ((unsigned long long)fkey(vals[a]) << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)id);
+    return sel_pack(vals[a], (uint32_t)id);
   };
   unsigned long long rk[RC];
 #pragma unroll
@@ -384,8 +369,8 @@ __global__ __launch_bounds__(1024) void topk_select_kernel(const float* __restri
     float v = -INFINITY;
     int32_t id = -1;
     if (i < want && key != 0ull) {
-      v = fkey_inv((uint32_t)(key >> 32));
-      id = (int32_t)(0xFFFFFFFFu - (uint32_t)(key & 0xFFFFFFFFull)) + idx_offset;
+      v = sel_score(key);
+      id = (int32_t)sel_low(key) + idx_offset;
     }
     out_val[(int64_t)q * k + i] = v;
     out_idx[(int64_t)q * k + i] = id;
@@ -513,10 +498,10 @@ __global__ __launch_bounds__(SL_THREADS) void sim_sliced_select_kernel(const Sli
     if (i < i1) {
       const float x = v[i];
       if (THR) {
-        if (x > -INFINITY) raw = ((unsigned long long)fkey(x) << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)i);
+        if (x > -INFINITY) raw = sel_pack(x, (uint32_t)i);
       } else {
         const int32_t id = ix[i];
-        if (id >= 0) raw = ((unsigned long long)fkey(x) << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)id);
+        if (id >= 0) raw = sel_pack(x, (uint32_t)id);
       }
     }
     rk[u] = raw;
@@ -569,7 +554,7 @@ __global__ __launch_bounds__(SL_THREADS) void sim_sliced_select_kernel(const Sli
       const unsigned long long* w4 = reinterpret_cast<const unsigned long long*>(L.hist);
       unsigned long long mm = w4[0];
       for (int i = 1; i < SL_THREADS / 64; ++i) mm = w4[i] < mm ? w4[i] : mm;
-      const float t = want > 0 ? fkey_inv((uint32_t)(mm >> 32)) : -INFINITY;
+      const float t = want > 0 ? sel_score(mm) : -INFINITY;
       a.thr[q] = a.sub ? t - a.sub[q] : t;
       a.cnt[(int64_t)q * CNT_STRIDE] = a.n_slots;  // survivors of the filter pass are appended behind the sample block
       a.cnt[(int64_t)q * CNT_STRIDE + 1] = 0;      // both tickets ready for their next use (the select form's: this call)
@@ -584,8 +569,8 @@ __global__ __launch_bounds__(SL_THREADS) void sim_sliced_select_kernel(const Sli
     float val = -INFINITY;
     int32_t id = -1;
     if (i < want && key != 0ull) {
-      val = fkey_inv((uint32_t)(key >> 32));
-      id = (int32_t)(0xFFFFFFFFu - (uint32_t)(key & 0xFFFFFFFFull)) + a.idx_offset;
+      val = sel_score(key);
+      id = (int32_t)sel_low(key) + a.idx_offset;
     }
     a.out_val[(int64_t)q * a.k + i] = val;
     a.out_idx[(int64_t)q * a.k + i] = id;
@@ -607,12 +592,6 @@ static int sliced_ns(int64_t len, int kpad) {
   if (ns > SL_NS_MAX) ns = SL_NS_MAX;
   while ((int64_t)ns * kpad > SL_RC * SL_THREADS) --ns;  // the merge holds NS x kpad keys in registers
   return ns >= need ? ns : 0;
-}
-
-static int next_pow2(int x) {
-  int p = 1;
-  while (p < x) p <<= 1;
-  return p;
 }
 
 }  // namespace gdr
@@ -707,7 +686,7 @@ int gdr::sim_topk_impl(const void* Q, int B, const void* D, int64_t N, int d, in
   int rc = stream_mode ? launch_sim_stream(D, N, Q, B, d, ep, bf16, stream) : launch_sim_gemm(D, N, Q, B, d, ep, bf16, stream);
   if (rc) return rc;
   const int sel_threads = 1024;  // 1024 lanes per query: measured faster than 512 with twice the entries per lane (26.7 vs 37.7 us at 32 queries)
-  const int kpad = next_pow2(k);
+  const int kpad = sel_pow2(k, 1);
   static const bool sliced_on = [] {
     const char* e = getenv("GDR_SIM_SLICED");  // A/B knob: 0 = one workgroup per query for the threshold / select tails (the r05 form)
     return e ? atoi(e) != 0 : true;
@@ -832,62 +811,10 @@ __global__ __launch_bounds__(1024) void prefilter_tail_kernel(const float* __res
   const int c_all = cand_cnt[(int64_t)q * CNT_STRIDE], count = c_all < (int)cap ? c_all : (int)cap;
   const float* v = cand_val + (int64_t)q * cap;
   const int32_t* ix = cand_idx + (int64_t)q * cap;
-  const bool cached = count <= RC * 1024;
+  bool cached;
   uint32_t rk[RC];
-#pragma unroll
-  for (int u = 0; u < RC; ++u) {
-    const int i = tid + u * 1024;
-    rk[u] = (cached && i < count) ? fkey(v[i]) : 0u;  // fkey(-inf) = 0x007fffff > 0: 0 marks "no entry"
-  }
   const uint32_t kneg = fkey(-INFINITY);
-  uint32_t lo = 0xFFFFFFFFu, hi = 0u;
-  if (cached) {
-#pragma unroll
-    for (int u = 0; u < RC; ++u)
-      if (rk[u] > kneg) lo = min(lo, rk[u]), hi = max(hi, rk[u]);
-  } else {
-    for (int i = tid; i < count; i += 1024) {
-      const float x = v[i];
-      if (x > -INFINITY) {
-        const uint32_t key = fkey(x);
-        lo = min(lo, key), hi = max(hi, key);
-      }
-    }
-  }
-  block_minmax(lo, hi, red);
-  if (hi < lo) lo = hi = fkey(-INFINITY);
-  const int nbits = hi > lo ? 32 - __clz(hi - lo) : 0;
-  const int lsh = 32 - nbits;
-  uint32_t prefix = 0;
-  int need = k;
-  for (int pass = 0; 8 * pass < nbits; ++pass) {
-    const int shift = 24 - 8 * pass;
-    if (tid < 256) hist[tid] = 0;
-    __syncthreads();
-    if (cached) {
-#pragma unroll
-      for (int u = 0; u < RC; ++u) {
-        const uint32_t raw = rk[u];
-        const uint32_t key = (raw - lo) << lsh;
-        const bool match = pass == 0 ? true : ((key >> (shift + 8)) == (prefix >> (shift + 8)));
-        if (raw != 0u && match && raw >= lo) atomicAdd(&hist[(key >> shift) & 255u], 1);
-      }
-    } else {
-      for (int i = tid; i < count; i += 1024) {
-        const uint32_t raw = fkey(v[i]);
-        const uint32_t key = (raw - lo) << lsh;
-        const bool match = pass == 0 ? true : ((key >> (shift + 8)) == (prefix >> (shift + 8)));
-        if (match && raw >= lo) atomicAdd(&hist[(key >> shift) & 255u], 1);
-      }
-    }
-    __syncthreads();
-    int above;
-    const int b = find_bin(hist, scan, need, &above, res);
-    need -= above;
-    prefix |= (uint32_t)b << shift;
-    __syncthreads();
-  }
-  const float band = fkey_inv(nbits ? (prefix >> lsh) + lo : lo) - eps2[q];  // t~_k - 2 eps_q
+  const float band = fkey_inv(radix_kth_key<1>(v, count, k, 1024, rk, cached, hist, scan, res, red)) - eps2[q];  // t~_k - 2 eps_q
   // ---- b. the band's ids
   int32_t* ids = reinterpret_cast<int32_t*>(pkeys + cap2p / 2);  // [cap2p] ints in the upper half of the key array
   if (tid == 0) n_sh = 0;
@@ -956,7 +883,7 @@ __global__ __launch_bounds__(1024) void prefilter_tail_kernel(const float* __res
     for (int u = 0; u < 4; ++u) {
       const int i = tid + u * 1024;
       mykey[u] = 0ull;
-      if (i < n2) mykey[u] = ((unsigned long long)fkey(vals[i]) << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)ids[i]);
+      if (i < n2) mykey[u] = sel_pack(vals[i], (uint32_t)ids[i]);
     }
     __syncthreads();
 #pragma unroll
@@ -966,14 +893,10 @@ __global__ __launch_bounds__(1024) void prefilter_tail_kernel(const float* __res
     }
     __syncthreads();
   }
+  // select.h's network with a workgroup barrier behind every stage: bitonic_desc (wave-local stages) costs this kernel registers
   for (int size = 2; size <= cap2p; size <<= 1) {
     for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      for (int t = tid; t < (cap2p >> 1); t += 1024) {
-        const int lo_i = (t / stride) * (stride << 1) + (t % stride), hi_i = lo_i + stride;
-        const bool desc = ((lo_i & size) == 0);
-        const unsigned long long a = pkeys[lo_i], b = pkeys[hi_i];
-        if ((a < b) == desc) pkeys[lo_i] = b, pkeys[hi_i] = a;
-      }
+      for (int t = tid; t < (cap2p >> 1); t += 1024) sel_cmpx(pkeys, t, stride, size);
       __syncthreads();
     }
   }
@@ -982,8 +905,8 @@ __global__ __launch_bounds__(1024) void prefilter_tail_kernel(const float* __res
     float val = -INFINITY;
     int32_t id = -1;
     if (i < n2 && key != 0ull) {
-      val = fkey_inv((uint32_t)(key >> 32));
-      id = (int32_t)(0xFFFFFFFFu - (uint32_t)(key & 0xFFFFFFFFull)) + idx_offset;
+      val = sel_score(key);
+      id = (int32_t)sel_low(key) + idx_offset;
     }
     out_val[(int64_t)q * k + i] = val;
     out_idx[(int64_t)q * k + i] = id;
@@ -991,9 +914,7 @@ __global__ __launch_bounds__(1024) void prefilter_tail_kernel(const float* __res
 }
 
 static int prefilter_cap2(int k) {
-  int c = 1024;
-  while (c < 4 * k) c <<= 1;
-  return c;
+  return sel_pow2(4 * k, 1024);
 }
 struct PrefilterPlan {
   SimPlan p;
@@ -1104,8 +1025,7 @@ extern "C" int gdr_sim_topk_prefilter(const float* Q, int B, const float* D, con
     if (rc) return rc;
   }
   // the tail in one launch: k-th largest bf16-operand score, the band around it, fp32 scores of the band, exact select
-  int cap2p = 1024;
-  while (cap2p < pp.cap2) cap2p <<= 1;
+  const int cap2p = sel_pow2(pp.cap2, 1024);
   if (int rc__ = ensure_dyn_lds(reinterpret_cast<const void*>(prefilter_tail_kernel<16>), cap2p * 8, "sim_topk_prefilter")) return rc__;
   hipLaunchKernelGGL(prefilter_tail_kernel<16>, dim3(B), dim3(1024), (size_t)cap2p * 8, stream, (const float*)ep.cand_val,
                      (const int32_t*)ep.cand_idx, (const int32_t*)ep.cand_cnt, p.cap, k, pp.cap2, cap2p, (const float*)eps2, Q, D, d,
@@ -1121,7 +1041,7 @@ extern "C" int gdr_topk_merge(const float* vals, const int32_t* idx, int G, int 
   if (B == 0) return GDR_OK;
   GDR_CHECK_ARG(vals && idx && out_val && out_idx, "topk_merge: null pointer");
   GDR_CHECK_ARG(G > 0 && B > 0 && k >= 1 && k <= 1024, "topk_merge: bad shape G=%d B=%d k=%d", G, B, k);
-  const int kpad = next_pow2(k);
+  const int kpad = sel_pow2(k, 1);
   hipLaunchKernelGGL(topk_select_kernel<true>, dim3(B), dim3(SEL_THREADS), kpad * sizeof(unsigned long long), stream,
                      vals, idx, (const int32_t*)nullptr, (int64_t)0, G, B, k, kpad, 0, (const float*)nullptr, out_val, out_idx,
                      (int32_t*)nullptr, k, 1);
@@ -1169,7 +1089,7 @@ extern "C" int gdr_topk_merge_packed(const void* pairs, int G, int B, int k, flo
   if (B == 0) return GDR_OK;
   GDR_CHECK_ARG(pairs && out_val && out_idx, "topk_merge_packed: null pointer");
   GDR_CHECK_ARG(G > 0 && B > 0 && k >= 1 && k <= 1024, "topk_merge_packed: bad shape G=%d B=%d k=%d", G, B, k);
-  const int kpad = next_pow2(k);
+  const int kpad = sel_pow2(k, 1);
   const float* vals = static_cast<const float*>(pairs);
   const int32_t* idx = static_cast<const int32_t*>(pairs) + 1;
   hipLaunchKernelGGL(topk_select_kernel<true>, dim3(B), dim3(SEL_THREADS), kpad * sizeof(unsigned long long), stream,

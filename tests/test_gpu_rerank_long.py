@@ -172,7 +172,7 @@ def test_8_shards_chunked_and_merged_equal_the_unsharded_one_sort_list(dev, shor
 # ---------------------------------------------------------------------------------------------------------------------
 def _orderable(v):
     u = v.view(np.uint32).astype(np.int64)
-    return np.where(u & 0x80000000, 0xFFFFFFFF - u, u | 0x80000000)                    # csrc/rerank.hip rr_fkey
+    return np.where(u & 0x80000000, 0xFFFFFFFF - u, u | 0x80000000)                    # csrc/select.h fkey
 
 
 def _expected_from_one_sort(Q, D, segs, beam, alphas, k, dev):
