@@ -221,7 +221,12 @@ __global__ __launch_bounds__(1024) void sim_threshold_kernel(const float* __rest
 // MERGE = true : entries vals/idx[((g*B + q)*rs + j)*es], i = g*k + j < G*k.  rs = entries per (shard, query) row (k, or
 //                k+1 when a trailing status entry rides along), es = element stride (2 when vals/idx interleave as
 //                {score, id} pairs).  With rs > k and `status`, status[q] = OR over shards of the trailing entry's id.
-template <bool MERGE>
+// DEEP = false: k <= 1024 — the first wave alone sorts the kpad selected keys (no workgroup barrier inside the sort).
+// DEEP = true : 1024 < k <= SEL_SORT_MAX — the same passes pick the keys, the whole workgroup sorts kpad = 2048 .. 8192 of them
+//                with select.h's network (16 .. 64 KiB of dynamic LDS: the launcher raises the limit).  The gather keeps its one
+//                same-address LDS atomic per selected key: a per-wave ballot / prefix compaction (one atomic per wave and sweep)
+//                measured the same or 1 - 2 % slower per call at k = 8192, so it was not kept.
+template <bool MERGE, bool DEEP = false>
 __global__ __launch_bounds__(1024) void topk_select_kernel(const float* __restrict__ vals,
                                                            const int32_t* __restrict__ idxs,
                                                            const int32_t* __restrict__ cnt, int64_t cap, int G, int B,
@@ -362,8 +367,12 @@ __global__ __launch_bounds__(1024) void topk_select_kernel(const float* __restri
     }
   }
   __syncthreads();
-  wave0_bitonic_desc(sortbuf, kpad);  // descending; the first wave alone, no workgroup barriers inside
-  __syncthreads();
+  if (DEEP) {
+    bitonic_desc(sortbuf, kpad);  // descending; every wave (kpad >= 2048 is a multiple of 2 x 16 waves), ends with a barrier
+  } else {
+    wave0_bitonic_desc(sortbuf, kpad);  // descending; the first wave alone, no workgroup barriers inside
+    __syncthreads();
+  }
   for (int i = threadIdx.x; i < k; i += blockDim.x) {
     const unsigned long long key = sortbuf[i];
     float v = -INFINITY;
@@ -594,12 +603,57 @@ static int sliced_ns(int64_t len, int kpad) {
   return ns >= need ? ns : 0;
 }
 
+// ---- k beyond 1024 ------------------------------------------------------------------------------------------------------------
+// gdr_sim_topk[_bf16], gdr_topk_merge, gdr_topk_pack and gdr_topk_merge_packed take k up to one LDS sort (select.h SEL_SORT_MAX); the
+// pre-filter stops where its one-workgroup tail does (it sorts 4k band keys in LDS and rescores them in fp32).
+constexpr int SIM_TOPK_MAX_K = SEL_SORT_MAX, SIM_ONE_WAVE_MAX_K = 1024, PREFILTER_MAX_K = 1024;
+
+// topk_select_kernel<MERGE, DEEP = true> for 1024 < k <= SIM_TOPK_MAX_K: kpad = 2048 .. 8192 keys of dynamic LDS, one workgroup of
+// DEEP_THREADS per query.  The merge form runs 256 threads at k <= 1024; here 1024 won: 0.056 / 0.106 / 0.187 ms at 1024 / 512 / 256
+// threads for (G, B, k) = (8, 64, 2048), 0.303 / 0.413 / 0.757 ms at k = 8192 (16 384 keys fit 1024 threads' register cache, and the
+// sort has 16 waves).  kpad is a multiple of 2 x 16 waves, as bitonic_desc asks.
+constexpr int DEEP_THREADS = 1024;
+template <bool MERGE>
+static int launch_select_deep(const float* vals, const int32_t* idxs, const int32_t* cnt, int64_t cap, int G, int B, int k,
+                              int32_t idx_offset, const float* thr, float* out_val, int32_t* out_idx, int32_t* status, int rs, int es,
+                              const char* what, hipStream_t stream) {
+  const int kpad = sel_pow2(k, 2048);
+  auto* kern = topk_select_kernel<MERGE, true>;
+  if (int rc = ensure_dyn_lds(reinterpret_cast<const void*>(kern), SEL_SORT_MAX * 8, what)) return rc;
+  hipLaunchKernelGGL(kern, dim3(B), dim3(DEEP_THREADS), (size_t)kpad * sizeof(unsigned long long), stream, vals, idxs, cnt, cap, G, B, k,
+                     kpad, idx_offset, thr, out_val, out_idx, status, rs, es);
+  GDR_CHECK_LAUNCH(what);
+  return GDR_OK;
+}
+
 }  // namespace gdr
 
+// The size a caller is told: the largest plan of any k' <= k, so that the answer never shrinks when k grows and a buffer sized for
+// the deepest list of a caller serves its shallower ones.  make_plan itself — what a call of depth k lays out and checks its
+// workspace against — is not monotone: each time a larger k lowers the sample stride by one the sample block grows by a step while
+// the survivor term 4 k N / n_sample shrinks, and the sum dips by 1 - 2 %.  With the sample tile count ts fixed the plan only grows
+// with k, so the maximum sits at the last k of one of the ts values up to k's: k' ~ (128 ts)^2 / N (or 128 ts once k' > N), looked
+// at with its two neighbours, since the boundary comes out of a rounded square root.
 extern "C" size_t gdr_sim_topk_workspace_bytes(int B, int64_t N, int d, int k, int flags) {
   (void)d;
   if (B <= 0 || N <= 0 || k <= 0) return 0;
-  return gdr::make_plan(B, N, k, (flags & GDR_SIM_EXHAUSTIVE) != 0).total;
+  const bool exhaustive = (flags & GDR_SIM_EXHAUSTIVE) != 0;
+  size_t best = gdr::make_plan(B, N, k, exhaustive).total;
+  if (exhaustive) return best;  // stride 1 whatever k: the plan does not depend on k
+  double target = sqrt((double)k * (double)N);
+  if (target < k) target = k;
+  const int64_t ts_k = (int64_t)((target + gdr::TILE - 1) / gdr::TILE);
+  for (int64_t ts = 1; ts <= ts_k; ++ts) {
+    const double edge = (double)(ts * gdr::TILE);
+    const int64_t ends[2] = {(int64_t)(edge * edge / (double)N), ts * gdr::TILE};
+    for (const int64_t e : ends)
+      for (int64_t kk = e - 1; kk <= e + 1; ++kk)
+        if (kk >= 1 && kk < k) {
+          const size_t t = gdr::make_plan(B, N, (int)kk, false).total;
+          if (t > best) best = t;
+        }
+  }
+  return best;
 }
 
 namespace gdr {
@@ -659,7 +713,7 @@ int gdr::sim_topk_impl(const void* Q, int B, const void* D, int64_t N, int d, in
   GDR_CHECK_ARG(Q && D && out_val && out_idx && workspace, "sim_topk: null pointer");
   GDR_CHECK_ARG(B > 0 && N > 0 && d > 0 && d % (bf16 ? 8 : 4) == 0, "sim_topk: bad shape B=%d N=%lld d=%d", B,
                 (long long)N, d);
-  GDR_CHECK_ARG(k >= 1 && k <= 1024 && k <= N, "sim_topk: k=%d must be in [1, min(1024, N)]", k);
+  GDR_CHECK_ARG(k >= 1 && k <= SIM_TOPK_MAX_K && k <= N, "sim_topk: k=%d must be in [1, min(%d, N)]", k, SIM_TOPK_MAX_K);
   GDR_CHECK_ARG(N < 0x7fffffffLL - 256, "sim_topk: shard too large for int32 doc ids");
   GDR_CHECK_ARG((int64_t)idx_offset + N <= 0x7fffffffLL,
                 "sim_topk: idx_offset=%d + N=%lld leaves int32 doc ids (the largest id, idx_offset + N - 1, must be < 2^31 - 1)", (int)idx_offset,
@@ -720,6 +774,9 @@ int gdr::sim_topk_impl(const void* Q, int B, const void* D, int64_t N, int d, in
     GDR_CHECK_LAUNCH("sim_sliced_select_kernel(select)");
     return GDR_OK;
   }
+  if (k > SIM_ONE_WAVE_MAX_K)
+    return launch_select_deep<false>(ep.cand_val, ep.cand_idx, ep.cand_cnt, p.cap, 1, B, k, idx_offset, thr, out_val, out_idx,
+                                     status, 0, 1, "topk_select_kernel<deep>", stream);
   hipLaunchKernelGGL(topk_select_kernel<false>, dim3(B), dim3(sel_threads), kpad * sizeof(unsigned long long), stream,
                      ep.cand_val, ep.cand_idx, ep.cand_cnt, p.cap, 1, B, k, kpad, idx_offset, (const float*)thr, out_val,
                      out_idx, status, 0, 1);
@@ -960,7 +1017,11 @@ static PrefilterPlan make_prefilter_plan(int B, int64_t N, int d, int k) {
 
 extern "C" size_t gdr_sim_topk_prefilter_workspace_bytes(int B, int64_t N, int d, int k) {
   if (B <= 0 || N <= 0 || k <= 0 || d <= 0) return 0;
-  return gdr::make_prefilter_plan(B, N, d, k).total;
+  // never below what gdr_sim_topk is told for the same call (its answer is the largest plan up to k, see there) plus the bf16 queries
+  // and the bands this entry point keeps beside the list
+  const size_t own = gdr::make_prefilter_plan(B, N, d, k).total;
+  const size_t plain = gdr_sim_topk_workspace_bytes(B, N, d, k, 0) + gdr::align_up((size_t)B * d * 2, 256) + gdr::align_up((size_t)B * 4, 256);
+  return own > plain ? own : plain;
 }
 
 extern "C" int gdr_row_norm2_max(const float* D, int64_t N, int d, float* out_dev, void* stream_) {
@@ -987,7 +1048,7 @@ extern "C" int gdr_sim_topk_prefilter(const float* Q, int B, const float* D, con
   GDR_CHECK_ARG(Q && D && D_bf16 && out_val && out_idx && workspace, "sim_topk_prefilter: null pointer");
   GDR_CHECK_ARG(B > 0 && N > 0 && d > 0 && d % 8 == 0 && d <= 1024, "sim_topk_prefilter: bad shape B=%d N=%lld d=%d (d %% 8 == 0, d <= 1024)", B,
                 (long long)N, d);
-  GDR_CHECK_ARG(k >= 1 && k <= 1024 && k <= N, "sim_topk_prefilter: k=%d must be in [1, min(1024, N)]", k);
+  GDR_CHECK_ARG(k >= 1 && k <= PREFILTER_MAX_K && k <= N, "sim_topk_prefilter: k=%d must be in [1, min(1024, N)]", k);
   GDR_CHECK_ARG(N < 0x7fffffffLL - 256, "sim_topk_prefilter: shard too large for int32 doc ids");
   GDR_CHECK_ARG((int64_t)idx_offset + N <= 0x7fffffffLL,
                 "sim_topk_prefilter: idx_offset=%d + N=%lld leaves int32 doc ids (the largest id, idx_offset + N - 1, must be < 2^31 - 1)",
@@ -1040,7 +1101,11 @@ extern "C" int gdr_topk_merge(const float* vals, const int32_t* idx, int G, int 
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   if (B == 0) return GDR_OK;
   GDR_CHECK_ARG(vals && idx && out_val && out_idx, "topk_merge: null pointer");
-  GDR_CHECK_ARG(G > 0 && B > 0 && k >= 1 && k <= 1024, "topk_merge: bad shape G=%d B=%d k=%d", G, B, k);
+  GDR_CHECK_ARG(G > 0 && B > 0 && k >= 1 && k <= SIM_TOPK_MAX_K && (int64_t)G * k <= 0x7fffffffLL,
+                "topk_merge: bad shape G=%d B=%d k=%d (k in [1, %d], G * k < 2^31)", G, B, k, SIM_TOPK_MAX_K);
+  if (k > SIM_ONE_WAVE_MAX_K)
+    return launch_select_deep<true>(vals, idx, nullptr, 0, G, B, k, 0, nullptr, out_val, out_idx, nullptr, k, 1,
+                                    "topk_select_kernel<merge, deep>", stream);
   const int kpad = sel_pow2(k, 1);
   hipLaunchKernelGGL(topk_select_kernel<true>, dim3(B), dim3(SEL_THREADS), kpad * sizeof(unsigned long long), stream,
                      vals, idx, (const int32_t*)nullptr, (int64_t)0, G, B, k, kpad, 0, (const float*)nullptr, out_val, out_idx,
@@ -1074,7 +1139,7 @@ extern "C" int gdr_topk_pack(const float* vals, const int32_t* idx, const int32_
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   if (B == 0) return GDR_OK;
   GDR_CHECK_ARG(vals && idx && pairs, "topk_pack: null pointer");
-  GDR_CHECK_ARG(B > 0 && k >= 1 && k <= 1024, "topk_pack: bad shape B=%d k=%d", B, k);
+  GDR_CHECK_ARG(B > 0 && k >= 1 && k <= SIM_TOPK_MAX_K, "topk_pack: bad shape B=%d k=%d (k in [1, %d])", B, k, SIM_TOPK_MAX_K);
   const int64_t n = (int64_t)B * (k + 1);
   hipLaunchKernelGGL(topk_pack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, vals, idx, status, B, k,
                      static_cast<int2*>(pairs));
@@ -1088,10 +1153,14 @@ extern "C" int gdr_topk_merge_packed(const void* pairs, int G, int B, int k, flo
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   if (B == 0) return GDR_OK;
   GDR_CHECK_ARG(pairs && out_val && out_idx, "topk_merge_packed: null pointer");
-  GDR_CHECK_ARG(G > 0 && B > 0 && k >= 1 && k <= 1024, "topk_merge_packed: bad shape G=%d B=%d k=%d", G, B, k);
-  const int kpad = sel_pow2(k, 1);
+  GDR_CHECK_ARG(G > 0 && B > 0 && k >= 1 && k <= SIM_TOPK_MAX_K && (int64_t)G * k <= 0x7fffffffLL,
+                "topk_merge_packed: bad shape G=%d B=%d k=%d (k in [1, %d], G * k < 2^31)", G, B, k, SIM_TOPK_MAX_K);
   const float* vals = static_cast<const float*>(pairs);
   const int32_t* idx = static_cast<const int32_t*>(pairs) + 1;
+  if (k > SIM_ONE_WAVE_MAX_K)
+    return launch_select_deep<true>(vals, idx, nullptr, 0, G, B, k, 0, nullptr, out_val, out_idx, out_status, k + 1, 2,
+                                    "topk_select_kernel<merge packed, deep>", stream);
+  const int kpad = sel_pow2(k, 1);
   hipLaunchKernelGGL(topk_select_kernel<true>, dim3(B), dim3(SEL_THREADS), kpad * sizeof(unsigned long long), stream,
                      vals, idx, (const int32_t*)nullptr, (int64_t)0, G, B, k, kpad, 0, (const float*)nullptr, out_val, out_idx,
                      out_status, k + 1, 2);

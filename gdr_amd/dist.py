@@ -109,7 +109,8 @@ class ShardedIndex:
 
     def search(self, q_all, k, return_status=False):
         """q_all [B,d] identical on every rank -> (values [B,k], global doc ids int32 [B,k][, status]), identical on
-        every rank.  ONE all-gather of the packed per-shard lists."""
+        every rank.  ONE all-gather of the packed per-shard lists.  k <= ops.SIM_TOPK_MAX_K (8192), and k <= the rows of the
+        smallest shard (a shard returns k of its own docs); the wire row int64[B, k+1] grows with k, nothing else changes."""
         v, i, st = self.local_topk(q_all, self.D, k, self.lo)
         if not self.distributed:
             return self._ret(v, i, st, return_status)
@@ -129,7 +130,7 @@ class ShardedIndex:
     def search_own(self, q_all, k, return_status=False):
         """q_all [B,d] identical on every rank (rank-major blocks of B/world queries) -> top-k of THIS rank's query block:
         (values [B/world,k], global doc ids int32 [B/world,k][, status]).  Same lists as search()[rank block].
-        ONE all-to-all of the packed per-shard lists."""
+        ONE all-to-all of the packed per-shard lists.  k as in search()."""
         v, i, st = self.local_topk(q_all, self.D, k, self.lo)
         if not self.distributed:
             return self._ret(v, i, st, return_status)
@@ -141,7 +142,7 @@ class ShardedIndex:
     def search_own_async(self, q_all, k):
         """search_own with pack + all-to-all + merge issued on a side stream: returns a handle whose wait() yields
         (values, ids, status) and makes the caller's current stream wait for them.  Between the call and wait() the
-        caller's stream is free — bench.py runs the next batch's encoder there, hiding the exchange."""
+        caller's stream is free — bench.py runs the next batch's encoder there, hiding the exchange.  k as in search()."""
         v, i, st = self.local_topk(q_all, self.D, k, self.lo)
         if not self.distributed:
             return _Pending((v, i, st), None)

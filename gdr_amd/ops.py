@@ -154,6 +154,10 @@ def to_bf16(x):
     return out
 
 
+SIM_TOPK_MAX_K = 8192            # gdr_sim_topk[_bf16], gdr_topk_merge, gdr_topk_pack, gdr_topk_merge_packed: one LDS sort of the list
+PREFILTER_MAX_K = 1024           # gdr_sim_topk_prefilter: its one-workgroup tail sorts 4k band keys and rescores them in fp32
+
+
 def _sim_topk_raw(Q, D, k, idx_offset, workspace, flags):
     B, d = Q.shape
     N = D.shape[0]
@@ -169,7 +173,10 @@ def _sim_topk_raw(Q, D, k, idx_offset, workspace, flags):
 
 
 def sim_topk(Q, D, k, idx_offset=0, workspace=None, return_status=False, exact_on_overflow=True, flags=0):
-    """Fused Q·Dᵀ + per-row top-k — gdr_sim_topk.  Returns (values fp32[B,k], indices int32[B,k]).
+    """Fused Q·Dᵀ + per-row top-k — gdr_sim_topk.  Returns (values fp32[B,k], indices int32[B,k]), 1 <= k <= min(SIM_TOPK_MAX_K, N).
+    D may be an fp32 or bf16 tensor, or a PrefilteredCorpus: the pre-filter serves k <= PREFILTER_MAX_K, a deeper list is the
+    plain fp32 call over its rows (the same answer: both return the top-k of the fp32 scores for every input).
+    The scratch grows with k (gdr_sim_topk_workspace_bytes; at N = 320 000: 0.7 MiB per query at k = 1024, 2.0 MiB at k = 8192).
     exact_on_overflow=True (the default) reads the per-query status back (one host sync per call) and recomputes any
     query whose candidate list overflowed (degenerate corpora with tens of thousands of tied docs) exhaustively, so the
     result is exact for every input.  Latency-critical callers pass exact_on_overflow=False, return_status=True: no sync,
@@ -177,7 +184,7 @@ def sim_topk(Q, D, k, idx_offset=0, workspace=None, return_status=False, exact_o
     prefilter = isinstance(D, PrefilteredCorpus)
     if prefilter:
         P, D = D, D.D
-        if (Q.shape[0] < PREFILTER_MIN_BATCH or D.shape[1] % 8 or D.shape[1] > 1024 or (flags & _ffi.SIM_EXHAUSTIVE)
+        if (Q.shape[0] < PREFILTER_MIN_BATCH or D.shape[1] % 8 or D.shape[1] > 1024 or (flags & _ffi.SIM_EXHAUSTIVE) or k > PREFILTER_MAX_K
                 or not P.dnorm_max > 0.0):                               # an all-zero corpus has no band: the fp32 path serves it
             prefilter = False
     _need_cuda(Q, D)
@@ -250,7 +257,7 @@ def _sim_topk_prefilter_raw(Q, P, k, idx_offset, workspace):
 
 
 def topk_merge(vals, idx):
-    """[G,B,k] per-shard lists -> [B,k] — gdr_topk_merge."""
+    """[G,B,k] per-shard lists -> [B,k] — gdr_topk_merge.  k <= SIM_TOPK_MAX_K."""
     _need_cuda(vals, idx)
     vals, idx = _f32c(vals), idx.contiguous()
     G, B, k = vals.shape
@@ -261,7 +268,7 @@ def topk_merge(vals, idx):
 
 
 def topk_pack(vals, idx, status=None):
-    """(values fp32[B,k], ids int32[B,k][, status int32[B]]) -> int64[B,k+1] wire form — gdr_topk_pack."""
+    """(values fp32[B,k], ids int32[B,k][, status int32[B]]) -> int64[B,k+1] wire form — gdr_topk_pack.  k <= SIM_TOPK_MAX_K."""
     _need_cuda(vals, idx, status)
     vals, idx = _f32c(vals), idx.contiguous()
     B, k = vals.shape
@@ -271,7 +278,8 @@ def topk_pack(vals, idx, status=None):
 
 
 def topk_merge_packed(pairs, return_status=False):
-    """int64[G,B,k+1] per-shard wire lists -> (values [B,k], ids int32 [B,k][, status int32 [B]]) — gdr_topk_merge_packed."""
+    """int64[G,B,k+1] per-shard wire lists -> (values [B,k], ids int32 [B,k][, status int32 [B]]) — gdr_topk_merge_packed.
+    k <= SIM_TOPK_MAX_K."""
     _need_cuda(pairs)
     pairs = pairs.contiguous()
     G, B, k1 = pairs.shape

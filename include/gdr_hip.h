@@ -254,7 +254,15 @@ int gdr_t5_encoder_forward_bf16(const GdrT5EncoderWeights* w, const int64_t* ids
  *   workspace B*N*8 bytes) is exact for any input.  The C entry point never synchronises, so the re-run is the
  *   caller's job: gdr_amd.ops.sim_topk does it by default (exact_on_overflow=True: one status read-back per call);
  *   latency-critical callers pass exact_on_overflow=False and receive the device status tensor instead.
- * d % 4 == 0, 1 <= k <= 1024, k <= N.
+ * d % 4 == 0, 1 <= k <= 8192, k <= N (gdr_sim_topk_bf16 likewise; gdr_sim_topk_prefilter stops at k <= 1024).  Up to k = 1024 the first
+ *   wave of the select's workgroup sorts the list; from 1025 on the same radix passes pick the k keys and the whole workgroup sorts
+ *   them in one LDS sort of 2048 .. 8192 keys — the same list by the same rule, one workgroup per query either way.
+ *   Workspace (gdr_sim_topk_workspace_bytes): a candidate list of 8 bytes per entry and query, sample block + 4 x the expected
+ *   survivors + 4096, beside 132 bytes per query.  At N = 320 000: k = 1024 -> sample stride 17, 92 288 entries, 360.6 MiB at 512 queries;
+ *   k = 8192 -> sample stride 6, 253 952 entries: 77.5 MiB at 40 queries, 992 MiB at 512.  The answer is the largest list of any
+ *   k' <= k (one call's list dips by 1 - 2 % where a larger k lowers the sample stride by one, and shrinks where the whole corpus
+ *   becomes the sample), so it never shrinks when k grows: a buffer sized for the deepest k of a caller serves its shallower ones.
+ *   gdr_sim_topk_prefilter_workspace_bytes is never below it (plus its bf16 queries and bands).
  * ---------------------------------------------------------------------------------------------- */
 #define GDR_SIM_EXHAUSTIVE 1
 #define GDR_SIM_NO_STREAM 2   /* force the tiled GEMM core even at B <= 32 (A/B testing of the latency-mode kernel) */
@@ -277,7 +285,8 @@ int gdr_sim_topk_bf16(const void* Q, int B, const void* D, int64_t N, int d, int
  * that band provably contains the fp32 top-k including every doc tied at the cut (derivation: csrc/sim_topk.hip), so out_val / out_idx
  * are the top-k of the fp32 scores for every input, ties as in gdr_sim_topk (higher score, then lower id); the values are fp32 dot
  * products of the same operands in another summation order.  dnorm_max: the largest ||D[r]||_2 (sqrt of gdr_row_norm2_max's result).
- * status as in gdr_sim_topk (1 = an overflowed list: re-run that query with gdr_sim_topk).  d % 8 == 0, d <= 1024.
+ * status as in gdr_sim_topk (1 = an overflowed list: re-run that query with gdr_sim_topk).  d % 8 == 0, d <= 1024, 1 <= k <= 1024 (the
+ * tail sorts 4k band keys in one workgroup's LDS and rescores them in fp32; a deeper list is gdr_sim_topk's: the same answer).
  * The workspace depends on d beyond the bf16 queries it holds: the filter pass keeps every doc above the sample threshold MINUS 2 eps_q,
  * and 2 eps_q measured in deviations of a query's scores grows like sqrt(d), so the candidate list is sized for that lowered threshold
  * (never smaller than gdr_sim_topk's list for the same B, N, k; non-decreasing in d).  The sizing is an expectation for scores that are
@@ -292,7 +301,7 @@ int gdr_row_norm2_max(const float* D, int64_t N, int d, float* out_dev, void* st
 int gdr_cast_f32_bf16(const float* in, void* out_bf16, int64_t n, void* stream);
 
 /* Merge of per-shard top-k lists after the RCCL all-gather (no reference analogue):
- * vals/idx [G,B,k] (shard-major) -> [B,k]; same tie rule (higher score in total order — +0.0 above -0.0 —, then lower id), so
+ * vals/idx [G,B,k] (shard-major) -> [B,k], 1 <= k <= 8192, any G with G * k < 2^31; same tie rule (higher score in total order — +0.0 above -0.0 —, then lower id), so
  * every rank computes identical output. */
 int gdr_topk_merge(const float* vals, const int32_t* idx, int G, int B, int k, float* out_val, int32_t* out_idx,
                    void* stream);
@@ -300,7 +309,7 @@ int gdr_topk_merge(const float* vals, const int32_t* idx, int G, int B, int k, f
  * 8 bytes, entry j < k = {fp32 score, int32 id}, entry k = {0, status[q]} (status may be NULL = 0).
  * gdr_topk_pack writes pairs[B, k+1]; gdr_topk_merge_packed merges pairs[G, B, k+1] (shard-major, as an all-gather /
  * all-to-all lays them out) into out_val/out_idx [B,k] with gdr_topk_merge's tie rule and, when out_status is given,
- * out_status[q] = 1 if any shard flagged query q (its list was the top-k of a subset, see gdr_sim_topk). */
+ * out_status[q] = 1 if any shard flagged query q (its list was the top-k of a subset, see gdr_sim_topk).  1 <= k <= 8192 in both. */
 int gdr_topk_pack(const float* vals, const int32_t* idx, const int32_t* status, int B, int k, void* pairs, void* stream);
 int gdr_topk_merge_packed(const void* pairs, int G, int B, int k, float* out_val, int32_t* out_idx,
                           int32_t* out_status, void* stream);
