@@ -907,6 +907,82 @@ __global__ __launch_bounds__(256) void beam_finalize_kernel(BeamBufs bb, BeamDim
   }
 }
 
+// ---- num_beams = 1: the reference's _generate_no_beam_search (generation_utils.py:553-627) --------------------------------------
+// One row per query and no hypotheses: `unfinished` is !done[b], `sent_len` is out_len[b], and the tokens go straight into out_ids.
+// greedy_init_kernel leaves out_ids = START, PAD, PAD, ... and out_len = max_length, so a finished row — and a step the early exit
+// never runs — has nothing left to write: padding is what is already there.
+__global__ void greedy_init_kernel(BeamBufs bb, BeamDims bd, int64_t* __restrict__ out_ids, int32_t* __restrict__ out_len,
+                                   double* __restrict__ out_scores) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b < bd.B) {
+    bb.cur_tok[b] = START_ID;
+    bb.kv_rows[b] = b;      // step 0: stride 1, position 0
+    bb.node[0][b] = 0;      // trie root (prefix-table mode)
+    bb.done[b] = 0;         // :553 unfinished_sents = 1
+    out_len[b] = bd.maxlen; // :554 sent_lengths = max_length
+    out_scores[b] = 0.0;    // the reference keeps no score
+    for (int t = 0; t < bd.maxlen; ++t) out_ids[(size_t)b * bd.maxlen + t] = t == 0 ? START_ID : PAD_ID;
+  }
+  if (b == 0) *bb.n_done = 0, *bb.live = 1;
+}
+
+// One decode step's select and bookkeeping at num_beams = 1, a wave per query (:596-619).  next = argmax over the full decode
+// vocabulary: the V+1 live columns are ranked here, every other column is exactly -1e9 after select_valid_embedding and loses to
+// any logit a model produces.  torch.argmax takes the LOWEST token id among equal maxima; EOS (token 1) sits in the LAST live
+// column, so lanes compare (logit, token id) pairs, never columns.  pos = the position just computed (cur_len = pos + 1 before the
+// token is added); the cache row of position p of query b is p*B + b at every step, so the step only re-lays kv_rows for the next
+// stride.
+__global__ __launch_bounds__(256) void greedy_step_kernel(BeamBufs bb, BeamDims bd, int pos, int cur, int64_t* __restrict__ out_ids,
+                                                          int32_t* __restrict__ out_len) {
+  // every query finished at an earlier step: nothing reads what this step would write (see beam_update_kernel)
+  if (bb.live_gate && *bb.live_gate == 0) return;
+  const int b = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (b >= bd.B) return;
+  const int V = bd.V, V1 = V + 1, stride = pos + 2;
+  for (int p = lane; p < stride; p += 64) bb.kv_rows[(size_t)b * stride + p] = p * bd.B + b;
+  if (bb.done[b]) {  // :601 a finished row adds PAD — already in out_ids — and feeds PAD to the next step
+    if (lane == 0) {
+      bb.cur_tok[b] = PAD_ID;
+      bb.node[cur ^ 1][b] = -1;
+    }
+    return;
+  }
+  const float* lg = bb.logits + (size_t)b * V1;
+  float best = -INFINITY;
+  int btok = INT32_MAX;
+  for (int c = lane; c < V1; c += 64) {
+    const float v = lg[c];
+    const int tok = c < V ? pos * V + 2 + c : EOS_ID;
+    if (v > best || (v == best && tok < btok)) best = v, btok = tok;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {  // the pairs are totally ordered: after the butterfly every lane holds the same one
+    const float ov = __shfl_xor(best, o);
+    const int ot = __shfl_xor(btok, o);
+    if (ov > best || (ov == best && ot < btok)) best = ov, btok = ot;
+  }
+  if (lane != 0) return;
+  if (btok == INT32_MAX) btok = EOS_ID;  // a row of NaNs ranks nothing: end it rather than index the tables with a non-token
+  bb.cur_tok[b] = btok;
+  out_ids[(size_t)b * bd.maxlen + pos + 1] = btok;
+  if (bd.trie_child) {
+    const int nd = bb.node[cur][b], c = btok - (pos * V + 2);
+    int nx = (nd >= 0 && c >= 0 && c < V) ? bd.trie_child[(size_t)nd * V + c] : -1;
+    if (nx >= bd.trie_nodes) nx = -1;  // a malformed table must not send later lookups out of bounds
+    bb.node[cur ^ 1][b] = nx;
+  }
+  if (btok != EOS_ID) return;
+  out_len[b] = pos + 2;  // :613 sent_lengths = cur_len after the increment: START and EOS both count
+  bb.done[b] = 1;        // :615
+  if (atomicAdd(bb.n_done, 1) + 1 == bd.B) {  // :618-619 `if unfinished_sents.max() == 0: break` — the words beam_update_kernel raises
+    *bb.live = 0;
+    if (bb.all_done_host) {
+      __hip_atomic_store(bb.all_done_host + 64, pos + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      __hip_atomic_store(bb.all_done_host, bb.done_epoch, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+  }
+}
+
 // ------------------------------------------------------------------------------------------ driver pieces
 // dynamic LDS of the two kernels that hold a query's hypothesis heap
 static size_t beam_update_lds(const BeamDims& bd) {
@@ -934,6 +1010,31 @@ static int check_beam_dims(const BeamDims& bd, int max_length) {
   GDR_CHECK_ARG(heap + 64 <= (size_t)BEAM_LDS_LIMIT,
                 "beam: num_beams=%d at max_length=%d needs %zu B of LDS for a query's hypothesis heap (limit %d): fewer beams or a shorter max_length",
                 bd.R, max_length, heap + 64, BEAM_LDS_LIMIT);
+  return GDR_OK;
+}
+
+// num_beams = 1 (gdr_t5_generate only: gdr_beam_search_table keeps check_beam_dims' range).  No candidate list and no hypothesis
+// heap, so none of the select's or the LDS limits apply; length_penalty is accepted and unused, as in the reference.
+static int check_greedy_dims(const BeamDims& bd, int max_length) {
+  GDR_CHECK_ARG(bd.B > 0, "generate: B=%d must be positive", bd.B);
+  GDR_CHECK_ARG(max_length >= 2 && max_length <= MAXLEN_CAP, "generate: max_length=%d must be in [2,%d]", max_length, MAXLEN_CAP);
+  GDR_CHECK_ARG(bd.V >= 1 && bd.Vd >= bd.V * (max_length - 1) + 2, "generate: decode vocab %d too small for V=%d, max_length=%d",
+                bd.Vd, bd.V, max_length);
+  return GDR_OK;
+}
+
+static int greedy_begin(const BeamBufs& bb, const BeamDims& bd, int64_t* out_ids, int32_t* out_len, double* out_scores,
+                        hipStream_t stream) {
+  hipLaunchKernelGGL(greedy_init_kernel, dim3((bd.B + 255) / 256), dim3(256), 0, stream, bb, bd, out_ids, out_len, out_scores);
+  GDR_CHECK_LAUNCH("greedy_init_kernel");
+  return GDR_OK;
+}
+
+// One decode step's select and bookkeeping at num_beams = 1 after bb.logits holds the step's unmasked-column logits.
+static int greedy_step(const BeamBufs& bb, const BeamDims& bd, int pos, int cur, int64_t* out_ids, int32_t* out_len,
+                       hipStream_t stream) {
+  hipLaunchKernelGGL(greedy_step_kernel, dim3((bd.B + 3) / 4), dim3(256), 0, stream, bb, bd, pos, cur, out_ids, out_len);
+  GDR_CHECK_LAUNCH("greedy_step_kernel");
   return GDR_OK;
 }
 
@@ -1267,6 +1368,16 @@ static int generate_impl(const GdrT5DecoderWeights* w, const float* enc_hidden, 
                          size_t workspace_bytes, bool bf16, hipStream_t stream) {
   GDR_CHECK_ARG(w && enc_hidden && enc_mask && out_ids && out_len && out_scores && workspace, "generate: null pointer");
   const GdrT5Dims& dm = w->dims;
+  // num_beams = 1 is the reference's non-beam branch (greedy_step_kernel): one sequence per query, and neither the trie constraint nor
+  // the top-2R trace, which exist for the beam search only — refused here, before anything behind those pointers is looked at
+  const bool greedy = num_beams == 1;
+  if (greedy) {
+    GDR_CHECK_ARG(num_return_sequences == 1, "generate: num_return_sequences=%d must be 1 at num_beams=1 (greedy decoding gives one sequence per query)",
+                  num_return_sequences);
+    GDR_CHECK_ARG(!trie, "generate: trie must be NULL at num_beams=1 (the constraint belongs to the beam search)");
+    GDR_CHECK_ARG(!step_scores, "generate: step_scores must be NULL at num_beams=1 (the top-2R trace belongs to the beam search)");
+    GDR_CHECK_ARG(!step_tokens, "generate: step_tokens must be NULL at num_beams=1 (the top-2R trace belongs to the beam search)");
+  }
   GDR_CHECK_ARG(!trie || (trie->child && trie->eos_ok && trie->n_nodes > 0), "generate: bad trie");
   GDR_CHECK_ARG(!trie || trie->V == w->out_vocab, "generate: trie built for V=%d but the head has output_vocab_size=%d",
                 trie ? trie->V : 0, w->out_vocab);
@@ -1294,7 +1405,7 @@ static int generate_impl(const GdrT5DecoderWeights* w, const float* enc_hidden, 
   BeamDims bd{B, num_beams, w->out_vocab, dm.vocab_size, max_length, num_return_sequences, length_penalty,
               trie ? trie->child : (ptab ? ptab->child : nullptr), trie ? trie->eos_ok : nullptr,
               trie ? trie->n_nodes : (ptab ? ptab->n_nodes : 0)};
-  int rc = check_beam_dims(bd, max_length);
+  int rc = greedy ? check_greedy_dims(bd, max_length) : check_beam_dims(bd, max_length);
   if (rc) return rc;
   GDR_CHECK_ARG(L >= 1 && L <= T5_MAX_LEN, "generate: L=%d must be in [1,%d]", L, T5_MAX_LEN);
   GDR_CHECK_ARG(max_length <= w->max_out_len, "generate: max_length=%d > max_output_length=%d of the head", max_length,
@@ -1358,7 +1469,8 @@ static int generate_impl(const GdrT5DecoderWeights* w, const float* enc_hidden, 
     const char* e = getenv("GDR_DECODE_DEDUP0");  // exact A/B knob: 0 = run step 0 on all B*R (identical) beam rows
     return e ? atoi(e) != 0 : true;
   }();
-  GDR_TRY(beam_begin(bb, bd, stream, dedup0));
+  if (greedy) GDR_TRY(greedy_begin(bb, bd, out_ids, out_len, out_scores, stream));
+  else GDR_TRY(beam_begin(bb, bd, stream, dedup0));
   // stream-K hand-off scratch of the two chains' big linears (gemm_f32.hip) inside their split-K regions — a launch uses one
   // or the other; both flag blocks are zeroed here, on the caller's stream, before the adaptor stream is first forked
   StreamK sk1{skw, reinterpret_cast<int32_t*>(base + g.splitk + STREAMK_PART_BYTES), 0};
@@ -1618,9 +1730,11 @@ static int generate_impl(const GdrT5DecoderWeights* w, const float* enc_hidden, 
                          partial);
       GDR_CHECK_LAUNCH("head_logits_table_kernel");
     }
-    GDR_TRY(beam_step(bb, bd, s, cur, step_scores, step_tokens, stream, s == 0 && dedup0));
+    if (greedy) GDR_TRY(greedy_step(bb, bd, s, cur, out_ids, out_len, stream));
+    else GDR_TRY(beam_step(bb, bd, s, cur, step_scores, step_tokens, stream, s == 0 && dedup0));
     cur ^= 1;
   }
+  if (greedy) return GDR_OK;  // greedy_step_kernel wrote out_ids / out_len as it went
   return beam_end(bb, bd, max_length, cur, out_ids, out_len, out_scores, stream);
 #undef GDR_TRY
 }

@@ -116,7 +116,9 @@ class GDRModel:
                  **model_kwargs):
         """Same kwargs / return shape as the vendored generate(): returns `(output, encoder_outputs | None)` where
         output is `(LongTensor[B*nret, <=max_length], list[float])` with output_scores=True, else the LongTensor
-        (generation_utils.py:524-527, 918-921).  Unknown kwargs (decode_tree, decoder_index, cluster_constraint,
+        (generation_utils.py:524-527, 918-921).  num_beams=1 (the reference's default) is its greedy branch
+        (_generate_no_beam_search, :553-627): output is the bare LongTensor[B, width] also with output_scores=True, width =
+        the length at which the last row emitted EOS (or max_length).  Unknown kwargs (decode_tree, decoder_index, cluster_constraint,
         decoder_attention_mask, ...) are accepted and ignored exactly as the reference swallows them
         (modeling_t5.py:1755)."""
         cfg = self.config
@@ -136,7 +138,10 @@ class GDRModel:
         if do_sample:
             raise NotImplementedError("sampling is outside the GDR hot path (gen_method='greedy', main.py:299)")
         if num_beams == 1:
-            raise NotImplementedError("GDR always decodes with num_beams = num_return_sequences > 1 (infer.sh:10-15)")
+            # no_beam_search greedy generation conditions (generation_utils.py:341-346)
+            assert num_return_sequences == 1, \
+                "Greedy decoding will always produce the same output for num_beams == 1 and num_return_sequences > 1. " \
+                "Please set num_return_sequences = 1"
         assert num_return_sequences <= num_beams, "num_return_sequences has to be <= num_beams for greedy beam search"
         if decode_vocab_size is not None:
             assert decode_vocab_size == cfg.decode_vocab_size, "decode_vocab_size does not match the loaded head"
@@ -145,8 +150,12 @@ class GDRModel:
             attention_mask = torch.ones_like(input_ids)
         enc_h, ids, lens, scores = self._generate_launch(input_ids, attention_mask, num_beams, max_length, length_penalty,
                                                           num_return_sequences)
-        decoded, score_list = ops.finish_generate_output(ids, lens, scores, max_length)
-        output = (decoded, score_list) if output_scores else decoded
+        if num_beams == 1:
+            # _generate_no_beam_search returns input_ids alone (generation_utils.py:627): no scores, whatever output_scores says
+            output = ops.finish_greedy_output(ids, lens)
+        else:
+            decoded, score_list = ops.finish_generate_output(ids, lens, scores, max_length)
+            output = (decoded, score_list) if output_scores else decoded
         if output_encoder_embedding:
             # the reference hands back the states already expanded per beam (generation_utils.py:459-461);
             # callers stride them with [::num_beams] (main_models.py:1466)
@@ -331,6 +340,12 @@ class GDRRetriever:
     beam-decode cluster ids -> id_mapping lookup -> tanh(q·d) over the candidates -> + alpha*softmax(beam scores)
     per cluster -> top-k, for every alpha in score_rate."""
 
+    @staticmethod
+    def _need_beams(args):
+        if getattr(args, "num_return_sequences", None) == 1:
+            raise _ffi.GdrError("GDRRetriever needs num_return_sequences >= 2: with one sequence generate() takes the greedy branch, "
+                                "which returns no scores for validation_step_i to unpack (main_models.py:1400)")
+
     def __init__(self, model: GDRModel, doc_embed, cluster_index: codec.ClusterIndex, args, doc_tower=None,
                  doc_tokens=None, device_candidates=True, sharded=None):
         """doc_embed: fp32 (or, in the C5 precision mode, bf16) [N, d] resident on the GPU (the reference's `self.doc_embed`).
@@ -344,6 +359,7 @@ class GDRRetriever:
         all-gather of the queries + candidate blocks, per-shard scoring, one all-to-all, merge: the lists are bit-identical
         to the unsharded rerank.  Every rank must call validation_step_i the same number of times with the same batch size
         (the collectives are fixed-size); `cluster_index` is the index of the WHOLE corpus on every rank."""
+        self._need_beams(args)
         self.model, self.args, self.index = model, args, cluster_index
         self.doc_embed = doc_embed if doc_embed is not None or sharded is None else sharded.D
         self.sharded = sharded
@@ -500,6 +516,7 @@ class GDRRetriever:
 
     def _step_launch(self, batch):
         a = self.args
+        self._need_beams(a)
         R = a.num_return_sequences
         mask = batch["source_mask"] if batch.get("source_mask") is not None else torch.ones_like(batch["source_ids"])
         enc_h, ids, lens, scores = self.model._generate_launch(batch["source_ids"], mask, R, a.max_output_length,

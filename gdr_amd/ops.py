@@ -1086,6 +1086,8 @@ class T5DecoderHandle:
     def generate(self, enc_hidden, enc_mask, num_beams, max_length, length_penalty, num_return_sequences, trace=False,
                  trie=None, prefix_table=None, graph=False):
         """Returns (out_ids int64[B*nret,max_length], out_len int32[B*nret], out_scores float64[B*nret][, trace]).
+        num_beams=1: greedy decode (include/gdr_hip.h) — nret must be 1, no trie and no trace; out_len counts START and EOS
+        (max_length for a row without EOS) and out_scores is 0.
         graph=True: the ~1 400 kernel launches of one call are captured once per (B, L, beams, max_length, nret) into a HIP
         graph (gdr_t5_generate contains no host synchronisation and forks / joins its side stream with events, i.e. it is
         capturable as is) and replayed on later calls — at small batches (one query x 100 beams, infer.sh's setting) the
@@ -1250,6 +1252,14 @@ def beam_search_table(table, out_vocab, num_beams, max_length, length_penalty, n
                                       ptr(ids), ptr(lens), ptr(scores), ptr(ws), ws.numel(), stream_ptr()),
           "gdr_beam_search_table")
     return ids, lens, scores
+
+
+def finish_greedy_output(ids, lens):
+    """Host tail of a num_beams = 1 call: _generate_no_beam_search returns input_ids as they stood when its loop ended
+    (generation_utils.py:618-627), i.e. width = max(sent_lengths), which is what gdr_t5_generate leaves in out_len."""
+    out = ids[:, :int(lens.max().item())].contiguous()
+    _ffi.check_device_fault("generate")                      # the host has just synchronised: a faulted launch must not pass
+    return out
 
 
 def finish_generate_output(ids, lens, scores, max_length):

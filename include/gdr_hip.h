@@ -664,7 +664,23 @@ size_t gdr_t5_generate_workspace_bytes(const GdrT5DecoderWeights* w, int B, int 
  *   its partial lists; a call that stays in the one-sort form needs what it always needed).
  *   A query's hypothesis heap (num_beams + 1 entries of max_length tokens) and, at the end, its open beam rows live in one
  *   workgroup's LDS (160 KiB): roughly num_beams * (8 * max_length + 32) bytes.  1024 beams fit up to max_length = 13, 512 beams
- *   up to 32; a combination that does not fit is refused with GDR_EINVAL naming num_beams and max_length before any launch. */
+ *   up to 32; a combination that does not fit is refused with GDR_EINVAL naming num_beams and max_length before any launch.
+ * num_beams == 1 selects the reference's non-beam branch instead (_generate_no_beam_search, generation_utils.py:553-627), the call
+ * its generate() makes by default: one row per query, next token = argmax of the step's logits over the whole decode vocabulary
+ * (of the logits, not a log-softmax; equal maxima: the lowest token id as torch.argmax on the CPU gives, so EOS = 1 wins a tie
+ * against any digit token; masked columns are exactly -1e9 and never win), PAD after a row's EOS, the loop ends when every row has
+ * emitted EOS (the same early exit as below; the step reported is width - 1) or at max_length.  The decoder chain, adaptor chain,
+ * head, prefix table and both cross-attention forms are the beam path's launches over B rows; the select and bookkeeping are one
+ * launch per step.  Contract:
+ *   num_return_sequences must be 1 (the reference asserts it, :341-346); trie, step_scores and step_tokens must be NULL (the
+ *   constraint and the top-2R trace exist for the beam search only) — any violation is GDR_EINVAL naming the argument, before any
+ *   launch; length_penalty is accepted and unused; prefix_table is allowed;
+ *   out_ids int64[B, max_length] = START, the tokens, then PAD after EOS; out_len int32[B] = the reference's sent_lengths: START
+ *   and EOS both count, max_length for a row that never emitted EOS (so generate()'s result is out_ids[:, :max(out_len)]);
+ *   out_scores[b] = 0.0 (the reference keeps none);
+ *   gdr_t5_generate_workspace_bytes(w, B, L, 1, max_length) is what this form needs: the beam form's layout at one row per query,
+ *   non-zero and never more than the answer for num_beams = 2.
+ * gdr_beam_search_table has no such form: it keeps refusing num_beams = 1. */
 int gdr_t5_generate(const GdrT5DecoderWeights* w, const float* enc_hidden, const int64_t* enc_mask, int B, int L,
                     int num_beams, int max_length, double length_penalty, int num_return_sequences,
                     const GdrTrie* trie, const GdrPrefixTable* prefix_table /* NULL: compute every row */, int64_t* out_ids,
