@@ -47,6 +47,25 @@ def peaked_t5(sd, cfg, s, rb, hs):
     return out
 
 
+STEEP_RAISE = 110.0   # > ln(FLT_MAX) = 88.7: exp(score - m) against a maximum that misses such a key overflows fp32
+
+
+def steep_t5(sd, cfg):
+    """A new state dict whose encoder position bias makes the row maximum climb or fall by STEEP_RAISE between key blocks: in block 0's
+    relative_attention_bias the last bucket of the "key after query" direction (num_buckets - 1) of heads 0 and 1, and the last bucket of
+    the "key before query" direction (num_buckets / 2 - 1) of heads 2 and 3, are set to (column maximum + STEEP_RAISE).  A key that far
+    behind (in front of) the query then outweighs every near one: for an early query the maximum lies in a late key block, for a late
+    query in an early one."""
+    key = "encoder.block.0.layer.0.SelfAttention.relative_attention_bias.weight"
+    nb = cfg.relative_attention_num_buckets
+    w = sd[key].clone()
+    for h in (0, 1):
+        w[nb - 1, h] = sd[key][:, h].max() + STEEP_RAISE
+    for h in (2, 3):
+        w[nb // 2 - 1, h] = sd[key][:, h].max() + STEEP_RAISE
+    return dict(sd, **{key: w})
+
+
 def peaked_bert(sd, s):
     return {k: (v * s if "attention.self.query." in k else v) for k, v in sd.items()}
 
@@ -61,6 +80,34 @@ def score_stats(scores):
     sc = scores.double()
     rows = (sc > -1e8).sum(-1) >= 2
     return float(sc[sc > -1e8].abs().max()), float(torch.softmax(sc, -1).max(-1).values[rows].mean())
+
+
+KEY_BLOCK = 64        # ops.ATTN_LONG_KEY_BLOCK: the key-block forms of csrc/attention_long.hip walk K / V in blocks of this many keys
+
+
+def block_walk_stats(scores, mask, min_len=129):
+    """What an online softmax over KEY_BLOCK-key blocks meets on `scores` [B, H, L, L] (additive mask included), over the live query
+    rows of the sequences with at least `min_len` live keys.  Returns (climb, fall, after0), each [rows, H] with rows = those query
+    rows concatenated: climb = (row maximum) - (maximum over keys 0..63), fall = (row maximum) - (maximum over the last key block that
+    holds a live key of the sequence), both over live keys only (0 where that block holds no live key), and after0 = whether the row
+    maximum lies behind key block 0."""
+    sc = scores.double()
+    sc = sc.masked_fill(sc < -1e8, float("-inf"))
+    mask = torch.as_tensor(mask)
+    climb, fall, after0 = [], [], []
+    for b in range(sc.shape[0]):
+        live = mask[b].nonzero().flatten()
+        if len(live) < min_len:
+            continue
+        rows = sc[b][:, live, :]                                    # [H, live queries, L]
+        top = rows.max(-1)
+        first = rows[..., :KEY_BLOCK].max(-1).values
+        lb = int(live[-1]) // KEY_BLOCK * KEY_BLOCK
+        last = rows[..., lb:lb + KEY_BLOCK].max(-1).values
+        climb.append(torch.where(torch.isfinite(first), top.values - first, torch.zeros_like(first)).T)
+        fall.append(torch.where(torch.isfinite(last), top.values - last, torch.zeros_like(last)).T)
+        after0.append((top.indices >= KEY_BLOCK).T)
+    return torch.cat(climb).numpy(), torch.cat(fall).numpy(), torch.cat(after0).numpy()
 
 
 def t5_block0_scores(sd, cfg, ids, mask):
@@ -176,23 +223,110 @@ GENERATE_CASES = {
 }
 GEN_BF16 = dict(case="gen-64", s=6.0, noise=(7.3e-3, 8.3e-4))
 
+# ---- more than 128 keys: the key-block forms of csrc/attention_long.hip (64 keys x 128 queries) and attention_kernel<8>.  The GPU
+# comparisons of these tables are tests/test_gpu_peaked_long.py's.  holes: L -> {row: (first, last + 1) of a run of masked keys}
+ENCODER_LONG_CASES = {
+    # d_kv 64: attention_long_f32_kernel<LONG_T5_SELF>.  L = 512 adds a left-padded row (keys 0..199 masked: three whole key blocks in
+    # front of the first live one) and a row with a hole (keys 130..389: whole key blocks between live ones)
+    "enc-long": dict(cfg=CFG64, seed=331, shapes={200: (200, 129, 131, 17), 512: (512, 385, 140, 1, 512, 512)},
+                     holes={512: {4: (0, 200), 5: (130, 390)}}, g=dict(moderate=1.64e-5, strong=4.57e-5)),
+    # d_kv 16: attention_kernel<8>
+    "enc-long-generic": dict(cfg={}, seed=332, shapes={300: (300, 129, 17, 1)}, g=dict(moderate=8.40e-6, strong=1.81e-5)),
+}
+# enc-long-steep: the L = 512 batch of enc-long at STRONG under steep_t5 — the row maximum climbs (heads 0, 1) or falls (heads 2, 3)
+# by more than ln(FLT_MAX) between key blocks.  min_share: of the live rows of the sequences longer than 128, per direction
+ENC_LONG_STEEP = dict(case="enc-long", L=512, setting="strong", step=100.0, min_share=0.10, g=3.87e-5)
+
+BERT_LONG_CASES = {
+    # 2 heads of 64, L = 384: attention_long_f32_kernel<LONG_PLAIN>
+    "bert-long": dict(bc=dict(max_pos=512), seed=341, L=384, lens=(384, 129, 200, 17, 1), g=dict(moderate=1.74e-5, strong=9.14e-5)),
+}
+# bert-long-bf16: attention_long_bf16_kernel, kept rows, the rule of BERT_BF16
+BERT_LONG_BF16 = dict(case="bert-long", s=6.0, noise=(2.37e-2, 1.10e-3), p99=7.1e-3, over=8.3e-3)
+
+_WIDE_LENS = (129, 128, 65, 64, 17, 1, 129, 100, 33, 129, 2, 90)
+GENERATE_LONG_CASES = {
+    # attention_long_f32_kernel<LONG_T5_CROSS>: step 0's single row, then a 6-row tile with slab-sourced q.  d_model = 256: decode.hip
+    # hands the q projection's split-K slabs to the attention kernel only where linear_f32_small_splits (gemm_small.hip) splits K,
+    # S <= (d_model / 32) / 4 — 2 slabs here, never at CFG64's d_model = 128.  token_seed: the first from 1 on with no tied beam row
+    "gen-long": dict(cfg=dict(CFG64, d_model=256), seed=351, token_seed=1, shape=(3, 6, 300), lens=(300, 129, 200),
+                     g=dict(moderate=8.65e-6, strong=8.44e-5)),
+    # 12 x 130 = 1 560 beam rows in two query blocks (128 + 2 beam rows) per (query, head); L = 129: key blocks of 64 + 64 + 1.  q rows
+    # come finished (d_model = 128: the projection is not split at any row count), so this case adds the two-query-block walk alone.  12 docid symbols: 144 candidates, so all 130 beams are live from step 1 on.  token_seed: the first from 1 on whose
+    # float64 search leaves <= 5 % of the beam rows inside the tie window (3.2 %).  At STRONG no token seed from 1 to 50 does (9.0 % ..
+    # 23 %: g is 2e-4 .. 5e-4 there, and 130 beams lie within 9 units of score), so STRONG takes the smaller beam of gen-long-wide-64
+    "gen-long-wide": dict(cfg=dict(CFG64, output_vocab_size=12, decode_vocab_size=12 * 5 + 2), seed=352, token_seed=1,
+                          shape=(12, 130, 129), lens=_WIDE_LENS, settings=("moderate",), g=dict(moderate=3.55e-5)),
+    # STRONG: 24 x 64 = 1 536 beam rows, finished q rows as above, one query block; token_seed: the first from 1 on with a tie share <= 5 % (4.5 %)
+    "gen-long-wide-64": dict(cfg=dict(CFG64, output_vocab_size=12, decode_vocab_size=12 * 5 + 2), seed=352, token_seed=5,
+                             shape=(24, 64, 129), lens=_WIDE_LENS * 2, settings=("strong",), g=dict(strong=1.94e-4)),
+}
+
+# ---- template instantiations under 128 keys that no case above reaches
+ENCODER_TILE_CASES = {
+    # attention_mfma16_kernel<1>, <4>, <5>, <6>, <7>
+    "enc-mfma-tiles": dict(cfg=CFG64, seed=361, shapes={16: (1, 16), 64: (1, 16, 17, 64), 65: (1, 16, 17, 65), 96: (1, 16, 17, 96),
+                                                        112: (1, 16, 17, 112)}, g=dict(moderate=9.20e-6, strong=1.72e-5)),
+    # the ENC_BF16 setting, padded: attention_mfma_bf16_kernel<1> and <8>.  seed: the first from 362 on at which both shapes meet the
+    # premise of enc-bf16 (mean top probability >= 0.5, max |score| >= 15) with a tenth to spare (>= 0.55, >= 16.5)
+    "enc-bf16-tiles": dict(cfg=CFG64, seed=367, shapes={16: (1, 16), 128: (1, 16, 17, 128)}),
+}
+ENC_BF16_TILES = dict(case="enc-bf16-tiles", s=3.0, noise=(1.24e-2, 4.9e-4), p99=4.1e-3, over=6.9e-4)
+GENERATE_TILE_CASES = {
+    # the gen-cross-mfma shape at L = 16 and L = 128: attention_cross_mfma16_kernel<1> and <8>
+    "gen-cross-16": dict(cfg=CFG64, seed=371, shape=(80, 20, 16), g=dict(moderate=2.58e-5, strong=1.66e-4)),
+    "gen-cross-128": dict(cfg=CFG64, seed=372, shape=(80, 20, 128), g=dict(moderate=3.32e-5, strong=2.73e-4)),
+    # gen-heads4 with 17 output positions: the steps that see 13 .. 16 keys — attention_decode_heads4_kernel<16>.  tied: at STRONG the
+    # float64 search leaves more than the generate cases' 5 % of the beam rows inside the tie window (5.7 % .. 14 % for every model seed
+    # from 324 to 335: 32 beams over 16 steps rank their tail 1e-3 apart).  The case keeps gen-heads4's seed and records its share; the
+    # host test re-asserts it, so the part of the ids that is compared by position (87 %) cannot shrink unnoticed
+    "gen-heads4-16": dict(cfg=dict(CFG64, max_output_length=17, decode_vocab_size=6 * 17 + 2), seed=324, shape=(128, 32, 12),
+                          g=dict(moderate=1.59e-5, strong=1.49e-4), tied=dict(strong=0.128)),
+}
+_ENCODER_TABLES = (ENCODER_CASES, ENCODER_LONG_CASES, ENCODER_TILE_CASES)
+_BERT_TABLES = (BERT_CASES, BERT_LONG_CASES)
+_GENERATE_TABLES = (GENERATE_CASES, GENERATE_LONG_CASES, GENERATE_TILE_CASES)
+
+
+def case_row(name, tables):
+    for t in tables:
+        if name in t:
+            return t[name]
+    raise KeyError(name)
+
+
+def generate_row(name):
+    return case_row(name, _GENERATE_TABLES)
+
+
+def case_settings(table):
+    """[(case name, setting name)] of a table: both settings unless the row names its own."""
+    return [(name, sname) for name, row in table.items() for sname in row.get("settings", ("moderate", "strong"))]
+
 
 # ------------------------------------------------------------------------------------------------------------ encoder
 @functools.lru_cache(maxsize=None)
 def encoder_case(name, setting):
     """(cfg, peaked fp32 state dict, {L: (ids, mask)})."""
-    c = ENCODER_CASES[name]
+    c = case_row(name, _ENCODER_TABLES)
     cfg = GDRConfig.tiny(**c["cfg"])
     sd = peaked_t5(synth.make_state_dict(cfg, seed=c["seed"], with_decoder=False), cfg, setting.s, setting.rb, setting.hs)
     inputs = {L: tokens_with_lengths(lens, L, cfg.vocab_size, c["seed"] * 1000 + L) for L, lens in c["shapes"].items()}
+    for L, rows in c.get("holes", {}).items():
+        for b, (lo, hi) in rows.items():
+            inputs[L][1][b, lo:hi] = 0
     return cfg, sd, inputs
 
 
 @functools.lru_cache(maxsize=None)
 def encoder_oracle(name, setting, f64, bf16=False):
     """{L: hidden states ndarray[B, L, d]} of the oracle: fp32 or float64 sums, optionally the bf16 mode's rounding points."""
-    from oracle import t5_ref
     cfg, sd, inputs = encoder_case(name, setting)
+    return _encoder_oracle(cfg, sd, inputs, f64, bf16)
+
+
+def _encoder_oracle(cfg, sd, inputs, f64, bf16=False):
+    from oracle import t5_ref
     sd = as_float64(sd) if f64 else sd
     out = {}
     for L, (ids, mask) in inputs.items():
@@ -206,6 +340,19 @@ def encoder_oracle(name, setting, f64, bf16=False):
     return out
 
 
+@functools.lru_cache(maxsize=None)
+def steep_case():
+    """(cfg, steep_t5 state dict in fp32, ids, mask) of enc-long-steep."""
+    cfg, sd, inputs = encoder_case(ENC_LONG_STEEP["case"], SETTINGS[ENC_LONG_STEEP["setting"]])
+    return (cfg, steep_t5(sd, cfg)) + inputs[ENC_LONG_STEEP["L"]]
+
+
+@functools.lru_cache(maxsize=None)
+def steep_oracle(f64):
+    cfg, sd, ids, mask = steep_case()
+    return _encoder_oracle(cfg, sd, {0: (ids, mask)}, f64)[0]
+
+
 def bf16_setting(table):
     return MODERATE._replace(s=table["s"], bert_s=table["s"])
 
@@ -213,7 +360,7 @@ def bf16_setting(table):
 # ------------------------------------------------------------------------------------------------------------ doc tower
 @functools.lru_cache(maxsize=None)
 def bert_case(name, setting):
-    c = BERT_CASES[name]
+    c = case_row(name, _BERT_TABLES)
     bc = dict(synth.bert_config(True), **c["bc"])
     sd = peaked_bert(synth.make_bert_state_dict(bc, seed=c["seed"]), setting.bert_s)
     return bc, sd, tokens_with_lengths(c["lens"], c["L"], bc["vocab_size"], c["seed"] * 1000)
@@ -231,11 +378,15 @@ def bert_oracle(name, setting, f64, bf16=False):
 # ------------------------------------------------------------------------------------------------------------ generate
 @functools.lru_cache(maxsize=None)
 def generate_case(name, setting):
-    c = GENERATE_CASES[name]
+    c = generate_row(name)
     cfg = GDRConfig.tiny(**c["cfg"])
     sd = peaked_t5(synth.make_state_dict(cfg, seed=c["seed"]), cfg, setting.s, setting.rb, setting.hs)
     B, R, L = c["shape"]
-    ids, mask = synth.make_tokens(B, L=L, vocab_hi=cfg.vocab_size, seed=c["seed"], min_len=2)
+    if "lens" in c:
+        ids, mask = tokens_with_lengths(c["lens"], L, cfg.vocab_size, c.get("token_seed", c["seed"]))
+    else:
+        ids, mask = synth.make_tokens(B, L=L, vocab_hi=cfg.vocab_size, seed=c["seed"], min_len=2)
+    assert ids.shape == (B, L)
     return cfg, sd, ids, mask, R
 
 
@@ -302,3 +453,61 @@ def shared_score_gaps(lists_a, scores_a, lists_b, scores_b):
         where = {x: i for i, x in enumerate(lb)}
         gaps += [abs(sa[p] - sb[where[x]]) for p, x in enumerate(la) if x in where]
     return np.array(gaps, np.float64)
+
+
+# ------------------------------------------------------------------------------------------------------------ how the seeds were picked
+def _clear_caches():
+    for f in (encoder_case, encoder_oracle, generate_case, generate_oracle):
+        f.cache_clear()
+
+
+def scan_generate_seeds(name, key, seeds):
+    """Yields (seed, {setting name: (g, tied share)}) of a generate case with row[key] (`seed` or `token_seed`) replaced by each seed
+    in turn: the figures the `token_seed` comments of the tables quote (first seed with every tied share <= 0.05)."""
+    row = generate_row(name)
+    kept = row.get(key, row["seed"])
+    try:
+        for seed in seeds:
+            row[key] = seed
+            _clear_caches()
+            out = {}
+            for _, sname in case_settings({name: row}):
+                st = SETTINGS[sname]
+                s32, s64 = generate_oracle(name, st, False)[1], generate_oracle(name, st, True)[1]
+                g = float(np.abs(s32 - s64).max())
+                out[sname] = (g, tied_row_share(s64, fp32_bound(g)))
+            yield seed, out
+    finally:
+        row[key] = kept
+        _clear_caches()
+
+
+def scan_bf16_tile_seeds(seeds):
+    """Yields (seed, [(L, max |score|, mean top probability)]) of enc-bf16-tiles under each model seed."""
+    row = ENCODER_TILE_CASES[ENC_BF16_TILES["case"]]
+    kept = row["seed"]
+    try:
+        for seed in seeds:
+            row["seed"] = seed
+            _clear_caches()
+            cfg, sd, inputs = encoder_case(ENC_BF16_TILES["case"], bf16_setting(ENC_BF16_TILES))
+            yield seed, [(L,) + score_stats(t5_block0_scores(sd, cfg, i, m)) for L, (i, m) in inputs.items()]
+    finally:
+        row["seed"] = kept
+        _clear_caches()
+
+
+if __name__ == "__main__":
+    # from the repository root, with PYTHONPATH=. :
+    #   python tests/peaked.py gen-long-wide token_seed 1 50 [strong]   |   python tests/peaked.py enc-bf16-tiles seed 362 370
+    import sys
+    torch.set_grad_enabled(False)
+    case, key, lo, hi = sys.argv[1], sys.argv[2], int(sys.argv[3]), int(sys.argv[4])
+    if case == ENC_BF16_TILES["case"]:
+        for seed, stats in scan_bf16_tile_seeds(range(lo, hi + 1)):
+            print(seed, " ".join(f"L={L}: max |score| {top:.1f}, top probability {prob:.2f};" for L, top, prob in stats), flush=True)
+    else:
+        if len(sys.argv) > 5:
+            generate_row(case)["settings"] = tuple(sys.argv[5:])
+        for seed, figures in scan_generate_seeds(case, key, range(lo, hi + 1)):
+            print(seed, " ".join(f"{sn}: g {g:.2e}, tied {100 * t:.1f} %;" for sn, (g, t) in figures.items()), flush=True)

@@ -15,33 +15,17 @@ import torch
 import peaked as P
 from conftest import beam_cut_explains_absence, hypothesis_lists_match
 from gdr_amd import synth
+from peaked_gpu import FP32_SETTINGS, close as _close, generate_vs_oracle as _generate_vs_oracle, noise_close as _noise_close
+from peaked_gpu import statistics_close as _statistics_close, to_dev as _dev, tower as _tower
 
 pytestmark = pytest.mark.gpu
 torch.set_grad_enabled(False)
-FP32_SETTINGS = [pytest.param(P.MODERATE, id="moderate"), pytest.param(P.STRONG, id="strong")]
 
 
 @pytest.fixture(scope="module")
 def dev():
     assert torch.cuda.is_available()
     return torch.device("cuda:0")
-
-
-def _close(got, want, bound, what):
-    got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
-    print(f"{what}: max |gpu - float64 oracle| {np.abs(got - want).max():.2e} (bound {bound:.1e})")
-    np.testing.assert_allclose(got, want, rtol=bound, atol=bound, err_msg=what)
-
-
-def _noise_close(got, want, table, what):
-    d = np.abs(np.asarray(got, np.float64) - want)
-    print(f"{what}: |gpu - bf16 emulation with float64 sums| max {d.max():.3e} mean {d.mean():.3e} "
-          f"(bounds {4 * table['noise'][0]:.1e} / {4 * table['noise'][1]:.1e})")
-    assert d.max() <= 4 * table["noise"][0] and d.mean() <= 4 * table["noise"][1], what
-
-
-def _dev(a, dev):
-    return torch.from_numpy(a).to(dev)
 
 
 # ------------------------------------------------------------------------------------------------------------ T5 encoder
@@ -105,11 +89,6 @@ def test_peaked_encoder_bf16_mode_vs_float64_emulation(dev):
 
 
 # ------------------------------------------------------------------------------------------------------------ doc tower
-def _tower(bc, sd, dev, **kw):
-    from gdr_amd.modeling import EncoderModel
-    return EncoderModel.from_state_dict(bc, sd, dev, **kw)
-
-
 @pytest.mark.parametrize("st", FP32_SETTINGS)
 @pytest.mark.parametrize("name", ["bert-64", "bert-16"])
 def test_peaked_doc_tower_vs_float64_oracle(dev, name, st):
@@ -144,42 +123,17 @@ def test_peaked_doc_tower_bf16_mode_vs_float64_emulation(dev):
     ref = P.bert_oracle(P.BERT_BF16["case"], st, True, True)
     hid, pooled = _tower(bc, sd, dev, dtype=torch.bfloat16).bert.forward(_dev(ids, dev), _dev(mask, dev))
     got, keep = hid.cpu().numpy(), mask != 0
-    _noise_close(got[keep], ref[keep], P.BERT_BF16, "bert-bf16 hidden (kept rows)")
-    d = np.abs(got[keep] - ref[keep])
-    print(f"bert-bf16: 99th percentile {np.quantile(d, 0.99):.3e} (bound {4 * P.BERT_BF16['p99']:.1e}), share of elements over 3e-2 "
-          f"{(d > 3e-2).mean():.2e} (bound {P.BERT_BF16['over']:.1e})")
-    assert np.quantile(d, 0.99) <= 4 * P.BERT_BF16["p99"] and (d > 3e-2).mean() <= P.BERT_BF16["over"]
+    _statistics_close(got[keep], ref[keep], P.BERT_BF16, "bert-bf16 hidden (kept rows)")
     assert np.abs(pooled.cpu().numpy() - ref[:, 0]).max() <= 4 * P.BERT_BF16["noise"][0]
     assert not got[~keep].any()
 
 
 # ------------------------------------------------------------------------------------------------------------ generate
-def _generate_vs_oracle(dev, name, st, what, **model_kw):
-    from gdr_amd.modeling import GDRModel
-    cfg, sd, ids, mask, R = P.generate_case(name, st)
-    B = ids.shape[0]
-    bound = P.fp32_bound(P.GENERATE_CASES[name]["g"][st.name])
-    ref, ref_sc, trace, ptrace = P.generate_oracle(name, st, True)
-    (dec, sc), _ = GDRModel(cfg, sd, dev, **model_kw).generate(_dev(ids, dev), attention_mask=_dev(mask, dev),
-                                                               max_length=cfg.max_output_length, num_beams=R, length_penalty=0.8,
-                                                               num_return_sequences=R, output_scores=True)
-    sc = np.array(sc, np.float64).reshape(B, R)
-    _close(sc, ref_sc, bound, f"{what} {st.name} beam scores ({B} x {R})")
-    got = P.hypothesis_lists(dec.cpu().numpy(), B, R)
-    moved = foreign = 0
-    for b in range(B):
-        def explain(hyp, b=b):         # a hypothesis the oracle's list lacks must have fallen at a cut of ITS search by a tie
-            return beam_cut_explains_absence(trace, ptrace, b, R, cfg.decode_vocab_size, list(hyp), bound, final_cut=ref_sc[b, -1])
-        m, f, _ = hypothesis_lists_match(ref[b], ref_sc[b], got[b], bound, explain_foreign=explain)
-        moved, foreign = moved + m, foreign + f
-    print(f"{what} {st.name}: of {B * R} hypotheses {moved} moved inside a tie group, {foreign} crossed a cut by a tie")
-
-
 @pytest.mark.parametrize("st", FP32_SETTINGS)
 @pytest.mark.parametrize("name", list(P.GENERATE_CASES))
 def test_peaked_generate_vs_float64_oracle(dev, name, st):
     """gen-generic (d_kv 16; 5 x 6 beams, L = 9): attention_decode_short_kernel<16>, the generic kernel for the cross-attention.
-    gen-64 (8 x 6, L = 20): decode-short; generic cross-attention with slab-sourced q (< 1 536 beam rows).
+    gen-64 (8 x 6, L = 20): decode-short; generic cross-attention (finished q rows: d_model = 128 is never split into K slabs).
     gen-cross-mfma (80 x 20 = 1 600 beam rows, L = 23): attention_cross_mfma16_kernel<2>.
     gen-heads4 (128 x 32 = 4 096 rows x 4 heads, 9 steps): attention_decode_heads4_kernel<4>, <8>, <12>.
     gen-rows (19 output positions): 17 and 18 keys in the last steps — attention_decode_rows_kernel, for the decoder (d_kv 64) and the
