@@ -30,10 +30,24 @@ class GDRConfig:
     adaptor_nhead: int = 8            # nn.TransformerDecoderLayer(nhead=8)
     adaptor_ff: int = 2048            # torch default dim_feedforward
     adaptor_ln_eps: float = 1e-5      # torch default layer_norm_eps
+    # the decode head (modeling_t5.py:1245-1249): 1/1 = the "efficient adaptor" head (:1615-1639); 0/0 = no adaptor at all, the
+    # head is lm_head(sequence_output) (:1640-1641).  The two mixed settings are other models (`unsupported_variant`).
+    adaptor_decode: int = 1
+    adaptor_efficient: int = 1
+
+    def __post_init__(self):
+        if bool(self.adaptor_decode) != bool(self.adaptor_efficient):
+            raise ValueError(f"GDRConfig: adaptor_decode={self.adaptor_decode} with adaptor_efficient={self.adaptor_efficient} is not "
+                             "implemented: both 1 (the efficient adaptor head) or both 0 (the plain lm_head head)")
 
     @property
     def inner_dim(self) -> int:
         return self.num_heads * self.d_kv
+
+    @property
+    def has_adaptor(self) -> bool:
+        """False: the adaptor-free model — no adaptor* weights, the docid head is lm_head alone."""
+        return bool(self.adaptor_decode) and bool(self.adaptor_efficient)
 
     def to_dict(self):
         return asdict(self)
@@ -66,16 +80,23 @@ class GDRConfig:
                          num_decoder_layers=args.num_decoder_layers,
                          output_vocab_size=V, max_output_length=L,
                          decode_vocab_size=V * L + 2,
-                         adaptor_layer_num=args.adaptor_layer_num)
+                         adaptor_layer_num=args.adaptor_layer_num,
+                         adaptor_decode=getattr(args, "adaptor_decode", 1),
+                         adaptor_efficient=getattr(args, "adaptor_efficient", 1))
 
 
 # Reference model variants selected by flags that main.py forwards into T5Config (main_models.py:748-780) and that change
 # the arithmetic of the decode branch (modeling_t5.py:1578-1640) or of the validation step (main_models.py:1350-1397).
-# The kernels implement exactly ONE of them — the shipped infer.sh / train.sh setting.  Anything else must fail loudly:
+# The kernels implement exactly ONE of them — the shipped infer.sh / train.sh setting — with one exception: the PAIR
+# --adaptor_decode 0 --adaptor_efficient 0 (no adaptor is built, modeling_t5.py:1245-1249; the head is lm_head(sequence_output),
+# :1640-1641) is implemented too (_PLAIN_PAIR below).  Anything else must fail loudly:
 # (flag, the value the kernels implement, what the reference would compute instead)
 _ONLY = [
-    ("adaptor_decode", 1, "without the adaptor the head is the plain lm_head (modeling_t5.py:1640-1644)"),
-    ("adaptor_efficient", 1, "adaptor_efficient=0 runs the per-position adaptor of modeling_t5.py:1578-1600"),
+    # each of these two at 0 ALONE is another model; both at 0 is the supported adaptor-free model
+    ("adaptor_decode", 1, "adaptor_decode=0 alone keeps building the adaptor but decodes through the plain lm_head "
+                          "(modeling_t5.py:1640-1644); supported: both 1, or the pair --adaptor_decode 0 --adaptor_efficient 0"),
+    ("adaptor_efficient", 1, "adaptor_efficient=0 alone runs the per-position T5Stack adaptor of modeling_t5.py:1578-1600; "
+                             "supported: both 1, or the pair --adaptor_decode 0 --adaptor_efficient 0"),
     ("decode_embedding", 2, "decode_embedding 0/1 decodes over the T5 vocabulary / a shared docid table "
                             "(main_models.py:1357-1374, modeling_t5.py:1266-1272)"),
     ("hierarchic_decode", 0, "hierarchic_decode=1 shares one V-column head over all positions (main_models.py:741,554)"),
@@ -89,10 +110,16 @@ _ONLY = [
 ]
 
 
+_PLAIN_PAIR = ("adaptor_decode", "adaptor_efficient")   # both 0: the adaptor-free model (GDRConfig.has_adaptor is False)
+
+
 def unsupported_variant(args):
     """None when `args` selects the model variant the HIP path implements, else one sentence naming the first flag that
     does not (reference: main_models.py:748-780 forwards these into T5Config; modeling_t5.py:1578-1640 branches on them)."""
+    plain = all(hasattr(args, n) and getattr(args, n) == 0 for n in _PLAIN_PAIR)
     for name, only, what in _ONLY:
+        if plain and name in _PLAIN_PAIR:
+            continue
         if hasattr(args, name) and getattr(args, name) != only:
             return (f"--{name} {getattr(args, name)!r} selects a reference model variant this build does not implement "
                     f"(implemented: {only!r}; {what})")

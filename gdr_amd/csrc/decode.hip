@@ -197,6 +197,79 @@ __global__ __launch_bounds__(256) void head_logits_kernel(const float* __restric
   if (lane == 0) logits[item] = acc;
 }
 
+// The head of a model WITHOUT the adaptor (GdrT5DecoderWeights' plain form; modeling_t5.py:1640-1641 lm_head(sequence_output)):
+//   logits[r][c] = sum_i (h[r][i] * d^-0.5) * E[c][i]
+// Per (row, column) this is head_logits_kernel's arithmetic with A == 0 — lane l walks the float4 pieces l, l + 64, ... in .x .y .z .w
+// order, then wave_sum; 0 + e == e exactly — so an adaptor model whose adaptor_linear is zero gives the same bits.  A wave serves one
+// row: it reads (and scales) the row once, NP pieces per lane in registers (d / 4 <= 64 * NP; NP = 0: any width, the row is read again
+// for every column), and loops over the V + 1 columns; lane c % 64 keeps column c's sum and every 64 columns are stored in one go.
+template <int NP>
+__global__ __launch_bounds__(256) void head_plain_kernel(const float* __restrict__ h, const float* __restrict__ E, int rows, int V1,
+                                                         int d, float scale, float* __restrict__ logits,
+                                                         const int32_t* __restrict__ live) {
+  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= rows) return;
+  if (live && *live == 0) return;  // every query is done: these logits are never ranked
+  const int lane = threadIdx.x & 63, n4 = d >> 2;
+  const float4* h4 = reinterpret_cast<const float4*>(h + (size_t)r * d);
+  float4 hs[NP > 0 ? NP : 1];
+#pragma unroll
+  for (int k = 0; k < NP; ++k) {
+    const int i = lane + 64 * k;
+    const float4 hv = i < n4 ? h4[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+    hs[k] = make_float4(hv.x * scale, hv.y * scale, hv.z * scale, hv.w * scale);
+  }
+  float* out = logits + (size_t)r * V1;
+  float mine = 0.f;
+  for (int c = 0; c < V1; ++c) {
+    const float4* e4 = reinterpret_cast<const float4*>(E + (size_t)c * d);
+    float acc = 0.f;
+    if (NP > 0) {
+#pragma unroll
+      for (int k = 0; k < NP; ++k) {
+        const int i = lane + 64 * k;
+        if (i < n4) {
+          const float4 ev = e4[i];
+          acc = fmaf(hs[k].x, ev.x, acc);
+          acc = fmaf(hs[k].y, ev.y, acc);
+          acc = fmaf(hs[k].z, ev.z, acc);
+          acc = fmaf(hs[k].w, ev.w, acc);
+        }
+      }
+    } else {
+      for (int i = lane; i < n4; i += 64) {
+        const float4 hv = h4[i], ev = e4[i];
+        acc = fmaf(hv.x * scale, ev.x, acc);
+        acc = fmaf(hv.y * scale, ev.y, acc);
+        acc = fmaf(hv.z * scale, ev.z, acc);
+        acc = fmaf(hv.w * scale, ev.w, acc);
+      }
+    }
+    acc = wave_sum(acc);
+    if ((c & 63) == lane) mine = acc;
+    if ((c & 63) == 63 || c + 1 == V1) {
+      const int c0 = c & ~63;
+      if (c0 + lane <= c) out[c0 + lane] = mine;
+    }
+  }
+}
+
+static int launch_head_plain(const float* h, const float* E, int rows, int V1, int d, float* logits, const int32_t* live,
+                             hipStream_t stream) {
+  const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
+  const float scale = 1.0f / sqrtf((float)d);
+  const int n4 = d / 4;
+#define GDR_HEAD_PLAIN(NP) hipLaunchKernelGGL(head_plain_kernel<NP>, grid, block, 0, stream, h, E, rows, V1, d, scale, logits, live)
+  if (n4 <= 64) GDR_HEAD_PLAIN(1);
+  else if (n4 <= 128) GDR_HEAD_PLAIN(2);
+  else if (n4 <= 192) GDR_HEAD_PLAIN(3);
+  else if (n4 <= 256) GDR_HEAD_PLAIN(4);
+  else GDR_HEAD_PLAIN(0);
+#undef GDR_HEAD_PLAIN
+  GDR_CHECK_LAUNCH("head_plain_kernel");
+  return GDR_OK;
+}
+
 // Prefix-table form of the same dot: a row whose prefix is a table node reads its finished head matrix
 // W[node][c][i] = A + E (built at load); any other row reads the A computed this step for its compacted slot.
 __global__ __launch_bounds__(256) void head_logits_table_kernel(const float* __restrict__ h, const float* __restrict__ A_c,
@@ -1312,40 +1385,47 @@ struct GenWs {
   size_t beam, dcache, acache, crosskv, xd, xa, nx, ctx, qc, ff, tmp, A, hl, splitk, ctx2, ff2, splitk2, qkv_c, abf, abf2, img1, img2, c16a, c16b, f16a, f16b, total;
 };
 
+// The plain form of GdrT5DecoderWeights (include/gdr_hip.h): no adaptor, the head is lm_head's rows alone.
+static bool plain_head(const GdrT5DecoderWeights& w) { return w.adaptor_layers == 0 && !w.alayers && !w.head_w; }
+
 static GenWs gen_ws(const GdrT5DecoderWeights& w, const BeamDims& bd, int L) {
   GenWs g{};
+  // plain head: no adaptor chain — its K/V cache, its activations and their bf16 images, and the head-matrix buffer A take no
+  // bytes (adaptor_ff is ignored); the side stream's split-K region and bf16 operand stay, the cross K/V projections use them
+  const bool plain = plain_head(w);
+  const size_t ad = plain ? 0 : 1, aff = plain ? 0 : (size_t)w.adaptor_ff;
   const GdrT5Dims& dm = w.dims;
   const size_t rows = (size_t)bd.B * bd.R, d = dm.d_model, inner = (size_t)dm.num_heads * dm.d_kv;
   const size_t tmax = bd.maxlen;
   size_t o = 0;
   g.beam = carve(o, beam_layout(bd, nullptr, nullptr));
   g.dcache = carve(o, 4 * (size_t)dm.num_layers * tmax * rows * 3 * inner);
-  g.acache = carve(o, 4 * (size_t)w.adaptor_layers * tmax * rows * 3 * d);
+  g.acache = carve(o, ad * 4 * (size_t)w.adaptor_layers * tmax * rows * 3 * d);
   g.crosskv = carve(o, 4 * (size_t)dm.num_layers * bd.B * L * 2 * inner);
   g.xd = carve(o, 4 * rows * d);
-  g.xa = carve(o, 4 * rows * d);
+  g.xa = carve(o, ad * 4 * rows * d);
   g.nx = carve(o, 4 * rows * d);
   g.ctx = carve(o, 4 * rows * (inner > d ? inner : d));
   g.qc = carve(o, 4 * rows * inner);
-  const size_t ffw = (size_t)(dm.d_ff > w.adaptor_ff ? dm.d_ff : w.adaptor_ff);
+  const size_t ffw = (size_t)dm.d_ff > aff ? (size_t)dm.d_ff : aff;
   g.ff = carve(o, 4 * rows * ffw);
-  g.tmp = carve(o, 4 * rows * d);
-  g.A = carve(o, 4 * rows * (size_t)(bd.V + 1) * d);
+  g.tmp = carve(o, ad * 4 * rows * d);
+  g.A = carve(o, ad * 4 * rows * (size_t)(bd.V + 1) * d);
   g.hl = carve(o, 4 * rows * d);
   g.splitk = carve(o, SPLITK_WS_BYTES);
-  g.ctx2 = carve(o, 4 * rows * d);                       // adaptor chain runs on a side stream: own scratch
-  g.ff2 = carve(o, 4 * rows * (size_t)w.adaptor_ff);
+  g.ctx2 = carve(o, ad * 4 * rows * d);                     // adaptor chain runs on a side stream: own scratch
+  g.ff2 = carve(o, 4 * rows * aff);
   g.splitk2 = carve(o, SPLITK_WS_BYTES);
-  g.qkv_c = carve(o, 4 * rows * 3 * d);                 // prefix-table mode: (q,k,v) of the compacted rows
+  g.qkv_c = carve(o, ad * 4 * rows * 3 * d);               // prefix-table mode: (q,k,v) of the compacted rows
   const size_t abf_main = rows * ffw > (size_t)bd.B * L * d ? rows * ffw : (size_t)bd.B * L * d;
   g.abf = carve(o, 2 * abf_main);                       // bf16 mode: the rounded activation operand of a linear (main stream)
   g.abf2 = carve(o, 2 * abf_main);                      //            ... of the side stream (adaptor chain, cross K/V projections)
   g.img1 = carve(o, 2 * rows * d);                      // bf16 mode: the bf16 image of the last normed rows of either chain (Bf16Image)
-  g.img2 = carve(o, 2 * rows * d);
+  g.img2 = carve(o, ad * 2 * rows * d);
   g.c16a = carve(o, 2 * rows * (inner > d ? inner : d));   // bf16 mode: attention contexts / ReLU outputs emitted as bf16 by their
-  g.c16b = carve(o, 2 * rows * d);                         // producers (a: decoder chain, b: adaptor chain) — the operand of
+  g.c16b = carve(o, ad * 2 * rows * d);                       // producers (a: decoder chain, b: adaptor chain) — the operand of
   g.f16a = carve(o, 2 * rows * ffw);                       // the linear behind them, which then needs no cast launch
-  g.f16b = carve(o, 2 * rows * (size_t)w.adaptor_ff);
+  g.f16b = carve(o, 2 * rows * aff);
   g.total = o;
   return g;
 }
@@ -1378,6 +1458,16 @@ static int generate_impl(const GdrT5DecoderWeights* w, const float* enc_hidden, 
     GDR_CHECK_ARG(!step_scores, "generate: step_scores must be NULL at num_beams=1 (the top-2R trace belongs to the beam search)");
     GDR_CHECK_ARG(!step_tokens, "generate: step_tokens must be NULL at num_beams=1 (the top-2R trace belongs to the beam search)");
   }
+  // the head: either the adaptor (layers > 0 with alayers and head_w) or the plain form (none of the three) — never a mixture
+  GDR_CHECK_ARG(w->adaptor_layers >= 0, "generate: adaptor_layers=%d must be >= 0", w->adaptor_layers);
+  GDR_CHECK_ARG(w->adaptor_layers == 0 || w->alayers, "generate: alayers is NULL at adaptor_layers=%d", w->adaptor_layers);
+  GDR_CHECK_ARG(w->adaptor_layers == 0 || w->head_w, "generate: head_w is NULL at adaptor_layers=%d", w->adaptor_layers);
+  GDR_CHECK_ARG(w->adaptor_layers > 0 || !w->alayers, "generate: alayers must be NULL at adaptor_layers=0 (the plain lm_head form)");
+  GDR_CHECK_ARG(w->adaptor_layers > 0 || !w->head_w, "generate: head_w must be NULL at adaptor_layers=0 (the plain lm_head form)");
+  const bool plain = plain_head(*w);
+  GDR_CHECK_ARG(!plain || !ptab,
+                "generate: prefix_table must be NULL with plain-head weights (the table stores adaptor results; lm_head alone has "
+                "nothing query-independent to store)");
   GDR_CHECK_ARG(!trie || (trie->child && trie->eos_ok && trie->n_nodes > 0), "generate: bad trie");
   GDR_CHECK_ARG(!trie || trie->V == w->out_vocab, "generate: trie built for V=%d but the head has output_vocab_size=%d",
                 trie ? trie->V : 0, w->out_vocab);
@@ -1410,11 +1500,11 @@ static int generate_impl(const GdrT5DecoderWeights* w, const float* enc_hidden, 
   GDR_CHECK_ARG(L >= 1 && L <= T5_MAX_LEN, "generate: L=%d must be in [1,%d]", L, T5_MAX_LEN);
   GDR_CHECK_ARG(max_length <= w->max_out_len, "generate: max_length=%d > max_output_length=%d of the head", max_length,
                 w->max_out_len);
-  GDR_CHECK_ARG(dm.d_model % 4 == 0 && dm.d_kv % 4 == 0 && dm.d_model % w->adaptor_nhead == 0 &&
-                    (dm.d_model / w->adaptor_nhead) % 4 == 0,
+  GDR_CHECK_ARG(dm.d_model % 4 == 0 && dm.d_kv % 4 == 0, "generate: unsupported dims");
+  // the adaptor's head width; the plain form ignores adaptor_nhead / adaptor_ff / adaptor_eps
+  GDR_CHECK_ARG(plain || (w->adaptor_nhead > 0 && dm.d_model % w->adaptor_nhead == 0 && (dm.d_model / w->adaptor_nhead) % 4 == 0),
                 "generate: unsupported dims");
-  GDR_CHECK_ARG(w->dec_embed && w->self_rel_bias && w->cross_rel_bias && w->final_ln && w->layers && w->alayers &&
-                    w->head_w && w->head_e,
+  GDR_CHECK_ARG(w->dec_embed && w->self_rel_bias && w->cross_rel_bias && w->final_ln && w->layers && w->head_e,
                 "generate: null weight pointer");
   const GenWs g = gen_ws(*w, bd, L);
   if (workspace_bytes < g.total) {
@@ -1439,11 +1529,11 @@ static int generate_impl(const GdrT5DecoderWeights* w, const float* enc_hidden, 
     else at_.out = fp32_ctx;
     at_.live = bb.live_gate;  // a step behind the last query's end: the attention launch exits at once
   };
-  GDR_CHECK_ARG(!bf16 || (dm.d_model % 8 == 0 && dm.d_ff % 8 == 0 && (dm.num_heads * dm.d_kv) % 8 == 0 && w->adaptor_ff % 8 == 0),
+  GDR_CHECK_ARG(!bf16 || (dm.d_model % 8 == 0 && dm.d_ff % 8 == 0 && (dm.num_heads * dm.d_kv) % 8 == 0 && (plain || w->adaptor_ff % 8 == 0)),
                 "generate(bf16): dims must be multiples of 8");
   const int d = dm.d_model, H = dm.num_heads, dk = dm.d_kv, inner = H * dk;
   const int rows = B * num_beams, V1 = bd.V + 1;
-  const int aH = w->adaptor_nhead, ahd = d / aH, aff = w->adaptor_ff;
+  const int aH = w->adaptor_nhead, ahd = plain ? 0 : d / aH, aff = w->adaptor_ff;
   const size_t dslab = (size_t)rows * 3 * inner;  // one position of one decoder layer's cache
   const size_t aslab = (size_t)rows * 3 * d;
   const size_t dlayer = (size_t)max_length * dslab, alayer = (size_t)max_length * aslab;
@@ -1549,13 +1639,15 @@ static int generate_impl(const GdrT5DecoderWeights* w, const float* enc_hidden, 
     hipLaunchKernelGGL(embed_rmsnorm_kernel, dim3((unsigned)((rows_s + 3) / 4)), dim3(256), 0, stream, w->dec_embed, bb.cur_tok, rows_s,
                        d / 4, dm.vocab_size, w->layers[0].ln_self, dm.eps, xd, nx, sk1.live);
     GDR_CHECK_LAUNCH("embed_rmsnorm_kernel");
-    if (ss.ok) {
+    // plain head: no second chain — nothing is forked or joined per step (the cross K/V projections above are joined through
+    // their own per-layer events at step 0)
+    if (ss.ok && !plain) {
       if (hipEventRecord(ss.fork, stream) != hipSuccess || hipStreamWaitEvent(ss.s, ss.fork, 0) != hipSuccess) {
         set_error("generate: fork to the adaptor stream failed");
         return GDR_EHIP;
       }
     }
-    if (!ptab) {
+    if (!ptab && !plain) {
       GDR_TRY(launch_embed(w->dec_embed, bb.cur_tok, rows_s, d, dm.vocab_size, xa, as));
     }
     // prefix-table mode, steps at which every possible prefix is a table node (step 0: the root; deeper while the trie's
@@ -1686,20 +1778,22 @@ static int generate_impl(const GdrT5DecoderWeights* w, const float* enc_hidden, 
     if (ptab && !adaptor_idle && !fuse_head)  // the head GEMM of the compacted rows belongs to the adaptor chain (it needs nothing from the decoder stack)
       GDR_TRY(side.linear(xa, d, w_at(w->head_w, (size_t)s * V1 * d * d, bf16), d, A, (int64_t)V1 * d, rows_s, nm, V1 * d, d, GDR_EPI_NONE,
                           nullptr, nullptr, 0));
-    if (ss.ok) {
+    if (ss.ok && !plain) {
       if (hipEventRecord(ss.join, ss.s) != hipSuccess) {
         set_error("generate: adaptor stream join failed");
         return GDR_EHIP;
       }
     }
-    if (ss.ok && hipStreamWaitEvent(stream, ss.join, 0) != hipSuccess) {
+    if (ss.ok && !plain && hipStreamWaitEvent(stream, ss.join, 0) != hipSuccess) {
       set_error("generate: adaptor stream join failed");
       return GDR_EHIP;
     }
     // ---------------- head: last position, unmasked columns only (modeling_t5.py:1634-1646)
-    const float* hw = w_at(w->head_w, (size_t)s * V1 * d * d, bf16);
     const float* he = w->head_e + (size_t)s * V1 * d;
-    if (!ptab) {
+    const float* hw = plain ? nullptr : w_at(w->head_w, (size_t)s * V1 * d * d, bf16);
+    if (plain) {  // lm_head(sequence_output) alone (modeling_t5.py:1640-1641): one launch, fp32 in both modes
+      GDR_TRY(launch_head_plain(hl, he, rows_s, V1, d, bb.logits, bb.live_gate, stream));
+    } else if (!ptab) {
       GDR_TRY(main.linear(xa, d, hw, d, A, (int64_t)V1 * d, rows_s, nullptr, V1 * d, d, GDR_EPI_NONE, nullptr, nullptr, 0));
       const int64_t items = (int64_t)rows_s * V1;
       hipLaunchKernelGGL(head_logits_kernel, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, stream, hl, A, he, rows_s, V1, d,
@@ -1794,7 +1888,7 @@ static TabWs tab_ws(const GdrT5DecoderWeights& w, int max_level_nodes) {
 }  // namespace gdr
 
 extern "C" size_t gdr_t5_prefix_table_workspace_bytes(const GdrT5DecoderWeights* w, int max_level_nodes) {
-  if (!w || max_level_nodes <= 0) return 0;
+  if (!w || max_level_nodes <= 0 || gdr::plain_head(*w)) return 0;  // plain head: there is no table to build
   return gdr::tab_ws(*w, max_level_nodes).total;
 }
 
@@ -1802,7 +1896,11 @@ namespace gdr {
 static int table_build_impl(const GdrT5DecoderWeights* w, int n_levels, const int32_t* level_off, const int64_t* node_tok,
                             const int32_t* node_anc, float* kv, float* W, void* workspace, size_t workspace_bytes, bool bf16,
                             hipStream_t stream) {
-  GDR_CHECK_ARG(w && level_off && node_tok && node_anc && kv && W && workspace, "prefix_table_build: null pointer");
+  GDR_CHECK_ARG(w, "prefix_table_build: null pointer");
+  GDR_CHECK_ARG(!plain_head(*w), "prefix_table_build: plain-head weights (adaptor_layers=0) have no adaptor results to store");
+  GDR_CHECK_ARG(w->adaptor_layers > 0 && w->alayers && w->head_w && w->head_e && w->adaptor_nhead > 0,
+                "prefix_table_build: adaptor_layers / alayers / head_w / head_e do not describe an adaptor head");
+  GDR_CHECK_ARG(level_off && node_tok && node_anc && kv && W && workspace, "prefix_table_build: null pointer");
   const GdrT5Dims& dm = w->dims;
   GDR_CHECK_ARG(n_levels >= 1 && n_levels <= w->max_out_len - 1 && n_levels <= MAXLEN_CAP,
                 "prefix_table_build: n_levels=%d must be in [1, max_output_length - 1 = %d]", n_levels, w->max_out_len - 1);

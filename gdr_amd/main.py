@@ -375,6 +375,9 @@ def main(argv=None):
         why = unsupported_variant(args)                      # before any rank is started: a variant the kernels lack
         if why:
             raise SystemExit("gdr_amd: " + why)
+        if args.adaptor_decode == 0 and args.adaptor_efficient == 0 and args.prefix_table:
+            raise SystemExit("gdr_amd: --prefix_table 1 cannot be combined with --adaptor_decode 0 --adaptor_efficient 0: the prefix "
+                             "table stores the adaptor's results and the adaptor-free model has none — pass --prefix_table 0")
         if args.expand_index and args.n_gpu > 1:
             raise SystemExit("gdr_amd: --expand_index 1 runs on one GPU: it cannot be combined with --n_gpu > 1")
         if args.n_gpu > 1 and not launch.under_launcher():

@@ -57,7 +57,8 @@ class _Encoder:
 
 
 class GDRModel:
-    """T5ForConditionalGeneration of the reference (GDR config: decode_embedding=2, adaptor_efficient),
+    """T5ForConditionalGeneration of the reference (GDR config: decode_embedding=2, adaptor_efficient — or, with
+    GDRConfig(adaptor_decode=0, adaptor_efficient=0), the adaptor-free model whose docid head is the plain lm_head),
     inference only.  Construct from a reference-style state_dict (SURVEY Appendix C key names)."""
 
     def __init__(self, cfg: GDRConfig, state_dict, device="cuda:0", with_decoder=True, trie=None, ragged=False,
@@ -71,7 +72,8 @@ class GDRModel:
         prefix_trie: optional codec.Trie over the corpus' docids — builds the device prefix table (ops.PrefixTable) at
         load: beams whose prefix is a node of that trie read the query-independent adaptor/head results from it instead of
         recomputing them (modeling_t5.py:1618-1639); other beams are computed as before.  Same logits up to fp32
-        summation order.  When `trie` (the constraint) is given too it must be the same trie.
+        summation order.  When `trie` (the constraint) is given too it must be the same trie.  Refused (GdrError) for an
+        adaptor-free config (cfg.has_adaptor False: the head is lm_head alone, there is nothing to tabulate); trie= works there.
         dtype=torch.bfloat16: BASELINE config C5's precision mode (the reference has none: precision=32) — every linear of
         encoder, decoder, adaptor and head takes bf16 operands with fp32 accumulate; all other arithmetic stays fp32.
         graph: replay the decode (gdr_t5_generate) of a repeated call shape as one captured HIP graph instead of ~1 400
@@ -80,6 +82,10 @@ class GDRModel:
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise _ffi.GdrError("GDRModel needs a CUDA (ROCm) device; there is no CPU path")
+        if prefix_trie is not None and not cfg.has_adaptor:       # before any weight is moved to the device
+            raise _ffi.GdrError("prefix_trie= needs the adaptor head: the prefix table stores the adaptor's query-independent "
+                                "results, and an adaptor-free model (adaptor_decode=0, adaptor_efficient=0) has none — pass "
+                                "trie= for the constraint alone")
         sd = strip_lightning_prefix(state_dict)
         self.dtype = dtype
         self.enc = ops.T5EncoderHandle(cfg, sd, self.device, dtype=dtype)

@@ -994,7 +994,11 @@ class T5DecoderHandle:
       * q,k,v of self-attention row-concatenated; k,v of cross-attention row-concatenated;
       * adaptor_linear.weight [d*Vd, d] (= [i, c, k], modeling_t5.py:1634-1636) sliced per decode position into
         head_w[p][c'][i][k] for the V+1 columns that survive the positional mask (modeling_t5.py:1553-1557);
-      * the adaptor's cross-attention over its single learned key folded into cross_const (softmax of one key = 1)."""
+      * the adaptor's cross-attention over its single learned key folded into cross_const (softmax of one key = 1).
+    An adaptor-free config (cfg.has_adaptor False: --adaptor_decode 0 --adaptor_efficient 0) builds the plain form of
+    GdrT5DecoderWeights: no adaptor* key is read, head_w is None and only head_e (lm_head's rows per position) is resident.
+    The state dict must match the config either way — adaptor weights under an adaptor-free config, or none under an adaptor
+    config, raise GdrError naming the key: a different model is never run silently."""
 
     def __init__(self, cfg, sd, device, dtype=torch.float32):
         """dtype=torch.bfloat16: the C5 precision mode — every linear weight (decoder, adaptor, head slices) is rounded to
@@ -1018,7 +1022,19 @@ class T5DecoderHandle:
             return t
 
         d, V, Vd, ml = cfg.d_model, cfg.output_vocab_size, cfg.decode_vocab_size, cfg.max_output_length
-        nl, na = cfg.num_decoder_layers, cfg.adaptor_layer_num
+        nl, na = cfg.num_decoder_layers, (cfg.adaptor_layer_num if cfg.has_adaptor else 0)
+        if cfg.has_adaptor:
+            need = ["adaptor_embeddings", "adaptor_linear.weight"] + [f"adaptor.layers.{i}.self_attn.in_proj_weight" for i in range(na)]
+            for k in need:
+                if k not in sd:
+                    raise _ffi.GdrError(f"T5DecoderHandle: the state dict has no {k!r} but the config has the adaptor head "
+                                        "(adaptor_decode=1, adaptor_efficient=1); an adaptor-free checkpoint needs "
+                                        "GDRConfig(adaptor_decode=0, adaptor_efficient=0)")
+        else:
+            for k in sd:
+                if k.startswith(("adaptor_linear.", "adaptor.layers.", "adaptor_embeddings")):
+                    raise _ffi.GdrError(f"T5DecoderHandle: the state dict holds {k!r} but the config is adaptor-free "
+                                        "(adaptor_decode=0, adaptor_efficient=0): refusing to drop trained adaptor weights")
         self.dec_embed = dev(sd["decode_embeddings.weight"])
         self.self_rel = dev(sd["decoder.block.0.layer.0.SelfAttention.relative_attention_bias.weight"])
         self.cross_rel = dev(sd["decoder.block.0.layer.1.EncDecAttention.relative_attention_bias.weight"])
@@ -1039,8 +1055,8 @@ class T5DecoderHandle:
             L.ln_ff = dev(sd[p + "2.layer_norm.weight"]).data_ptr()
             L.wi = lin(sd[p + "2.DenseReluDense.wi.weight"]).data_ptr()
             L.wo_ff = lin(sd[p + "2.DenseReluDense.wo.weight"]).data_ptr()
-        mem = dev(sd["adaptor_embeddings"]).view(1, d)
-        self._alayers = (_ffi.GdrAdaptorLayer * na)()
+        mem = dev(sd["adaptor_embeddings"]).view(1, d) if na else None
+        self._alayers = (_ffi.GdrAdaptorLayer * na)() if na else None
         aff = None
         for i in range(na):
             p = f"adaptor.layers.{i}."
@@ -1066,21 +1082,24 @@ class T5DecoderHandle:
         # head slices
         P = ml - 1
         cols = torch.tensor([[p * V + 2 + c for c in range(V)] + [1] for p in range(P)], dtype=torch.long, device=device)
-        Wfull = sd["adaptor_linear.weight"].detach().to(device=device, dtype=torch.float32)
-        W = Wfull.view(d, Vd, d)
-        self.head_w = torch.empty((P, V + 1, d, d), dtype=dtype, device=device)
-        for p in range(P):                                   # per position: bounded temporaries
-            sl = W[:, cols[p], :].permute(1, 0, 2).contiguous()
-            self.head_w[p] = to_bf16(sl) if dtype == torch.bfloat16 else sl
-        del W, Wfull                                         # only the slices stay resident
+        self.head_w = None                                   # adaptor-free: the head is head_e alone (head_plain_kernel)
+        if na:
+            Wfull = sd["adaptor_linear.weight"].detach().to(device=device, dtype=torch.float32)
+            W = Wfull.view(d, Vd, d)
+            self.head_w = torch.empty((P, V + 1, d, d), dtype=dtype, device=device)
+            for p in range(P):                                   # per position: bounded temporaries
+                sl = W[:, cols[p], :].permute(1, 0, 2).contiguous()
+                self.head_w[p] = to_bf16(sl) if dtype == torch.bfloat16 else sl
+            del W, Wfull                                         # only the slices stay resident
         self.head_e = dev(sd["lm_head.weight"])[cols].contiguous()            # [P, V+1, d]
         self._keep = keep
         self.dims = _ffi.GdrT5Dims(Vd, d, cfg.d_kv, cfg.d_ff, cfg.num_heads, nl, cfg.relative_attention_num_buckets,
                                    cfg.relative_attention_max_distance, cfg.layer_norm_epsilon)
-        self.struct = _ffi.GdrT5DecoderWeights(self.dims, V, ml, na, cfg.adaptor_nhead, aff, cfg.adaptor_ln_eps,
+        self.struct = _ffi.GdrT5DecoderWeights(self.dims, V, ml, na, cfg.adaptor_nhead if na else 0, aff or 0,
+                                               cfg.adaptor_ln_eps if na else 0.0,
                                                self.dec_embed.data_ptr(), self.self_rel.data_ptr(),
                                                self.cross_rel.data_ptr(), self.final_ln.data_ptr(), self._layers,
-                                               self._alayers, self.head_w.data_ptr(), self.head_e.data_ptr())
+                                               self._alayers, self.head_w.data_ptr() if na else None, self.head_e.data_ptr())
         self.ws = Workspace(device)
 
     def generate(self, enc_hidden, enc_mask, num_beams, max_length, length_penalty, num_return_sequences, trace=False,
@@ -1093,6 +1112,8 @@ class T5DecoderHandle:
         capturable as is) and replayed on later calls — at small batches (one query x 100 beams, infer.sh's setting) the
         call is otherwise bound by the host's launch rate, not by the GPU."""
         _need_cuda(enc_hidden, enc_mask)
+        if prefix_table is not None and self.head_w is None:
+            raise _ffi.GdrError("generate: a prefix table cannot be used with an adaptor-free model (it stores adaptor results)")
         enc_hidden = _f32c(enc_hidden)
         mask = enc_mask.to(torch.int64).contiguous()
         B, L, _ = enc_hidden.shape
@@ -1181,8 +1202,11 @@ class PrefixTable:
         kv, W (optional): caller-provided table storage, fp32 [adaptor_layers, n_table, 3d] and [n_table, V+1, d]; workspace
         (optional): an object whose get(nbytes) returns the build's scratch (ops.Workspace).  Defaults: allocated here."""
         import numpy as np
-        bfs, level_off, parent, tok = trie.breadth_first()
         cfg = dec.cfg
+        if not cfg.has_adaptor:
+            raise _ffi.GdrError("PrefixTable: the model has no adaptor (adaptor_decode=0, adaptor_efficient=0) — the table stores the "
+                                "adaptor's query-independent results and the plain lm_head head has none")
+        bfs, level_off, parent, tok = trie.breadth_first()
         n_levels = min(len(level_off) - 1, cfg.max_output_length - 1, max_levels or (1 << 30))
         per_node = (cfg.adaptor_layer_num * 3 * cfg.d_model + (cfg.output_vocab_size + 1) * cfg.d_model) * 4
         if max_bytes is None:

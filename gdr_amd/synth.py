@@ -24,7 +24,8 @@ def make_state_dict(cfg: GDRConfig, seed: int = 1234, with_decoder: bool = True,
                     ln_jitter: float = 0.1):
     """state_dict of the reference's ``T5ForConditionalGeneration`` (keys of SURVEY Appendix C,
     without the Lightning ``model.`` prefix).  ``ln_jitter`` perturbs norm weights away from 1.0
-    so that a kernel ignoring them fails parity."""
+    so that a kernel ignoring them fails parity.  An adaptor-free config (``cfg.has_adaptor`` False) gives the same draws
+    without the ``adaptor*`` keys: the adaptor is drawn last, so every other weight of a seed is the same tensor."""
     g = np.random.Generator(np.random.PCG64(seed))
     d, dk, H, ff = cfg.d_model, cfg.d_kv, cfg.num_heads, cfg.d_ff
     inner = H * dk
@@ -72,6 +73,8 @@ def make_state_dict(cfg: GDRConfig, seed: int = 1234, with_decoder: bool = True,
         sd[p + ".layer.2.DenseReluDense.wo.weight"] = normal((d, ff), ff ** -0.5)
         sd[p + ".layer.2.layer_norm.weight"] = ln(d)
     sd["decoder.final_layer_norm.weight"] = ln(d)
+    if not cfg.has_adaptor:
+        return sd
 
     aff = cfg.adaptor_ff
 

@@ -582,6 +582,13 @@ typedef struct {          /* one torch.nn.TransformerDecoderLayer (post-LN, ReLU
   const float *ln3_w, *ln3_b;
 } GdrAdaptorLayer;
 
+/* Two forms of the docid head, chosen by the weights themselves:
+ *   adaptor head  adaptor_layers > 0 with alayers and head_w set: the "efficient adaptor" of --adaptor_decode 1 --adaptor_efficient 1
+ *                 (modeling_t5.py:1615-1639): logits = h * d^-0.5 . (adaptor_linear(adaptor(prefix)) + lm_head).
+ *   plain head    adaptor_layers == 0 && alayers == NULL && head_w == NULL: the adaptor-free model of --adaptor_decode 0
+ *                 --adaptor_efficient 0 (no adaptor is built, modeling_t5.py:1245-1249): logits = lm_head(h * d^-0.5) (:1640-1641).
+ *                 head_e is still required; adaptor_nhead / adaptor_ff / adaptor_eps are ignored.
+ * Any mixture (layers > 0 with a NULL alayers or head_w; layers == 0 with either of them set) is GDR_EINVAL naming the field. */
 typedef struct {
   GdrT5Dims dims;                  /* num_layers = num_decoder_layers; vocab_size = decode_vocab_size (Vd) */
   int32_t out_vocab;               /* V  (--output_vocab_size / --kary)                                     */
@@ -593,11 +600,11 @@ typedef struct {
   const float* cross_rel_bias;     /* [buckets,H] decoder.block.0.layer.1.EncDecAttention.relative_attention_bias */
   const float* final_ln;           /* [d]       decoder.final_layer_norm.weight                              */
   const GdrT5DecLayer* layers;     /* host array [num_layers]                                                */
-  const GdrAdaptorLayer* alayers;  /* host array [adaptor_layers]                                            */
+  const GdrAdaptorLayer* alayers;  /* host array [adaptor_layers]; NULL for the plain head                   */
   /* head slices: position p in [0, max_out_len-1), local column c in [0, V] (c < V: token p*V+2+c; c == V: EOS=1)
    *   head_w[p][c][i][k] = adaptor_linear.weight[i*Vd + token(p,c), k]      (modeling_t5.py:1634-1636)
    *   head_e[p][c][i]    = lm_head.weight[token(p,c), i]                                                    */
-  const float* head_w;             /* [(max_out_len-1), V+1, d, d] */
+  const float* head_w;             /* [(max_out_len-1), V+1, d, d]; NULL for the plain head */
   const float* head_e;             /* [(max_out_len-1), V+1, d]    */
 } GdrT5DecoderWeights;
 
@@ -636,6 +643,7 @@ typedef struct {
                             * a value larger than the truth gives WRONG logits for the rows that do miss)                    */
 } GdrPrefixTable;
 
+/* Plain-head weights have no table: gdr_t5_prefix_table_workspace_bytes answers 0 and the builders GDR_EINVAL. */
 size_t gdr_t5_prefix_table_workspace_bytes(const GdrT5DecoderWeights* w, int max_level_nodes);
 /* level_off: HOST int32 [n_levels+1], node range of each depth (level 0 = the root alone);
  * node_tok: device int64 [n_table], the token that leads to the node (root: START = 0);
@@ -680,7 +688,16 @@ size_t gdr_t5_generate_workspace_bytes(const GdrT5DecoderWeights* w, int B, int 
  *   out_scores[b] = 0.0 (the reference keeps none);
  *   gdr_t5_generate_workspace_bytes(w, B, L, 1, max_length) is what this form needs: the beam form's layout at one row per query,
  *   non-zero and never more than the answer for num_beams = 2.
- * gdr_beam_search_table has no such form: it keeps refusing num_beams = 1. */
+ * gdr_beam_search_table has no such form: it keeps refusing num_beams = 1.
+ * Plain-head weights (see GdrT5DecoderWeights): the decoder chain is the one above; no adaptor chain is enqueued and nothing is forked
+ * to or joined from the side stream per step (the side stream still projects the cross-attention K/V at step 0); the head of a step
+ * is ONE launch, head_plain_kernel — logits[r][c] = sum_i (h[r][i] * d^-0.5) * head_e[s][c][i] over the V+1 live columns, per (row,
+ * column) in the adaptor head's order with a zero head matrix, so an adaptor model whose adaptor_linear is zero gives the same bits;
+ * fp32 in both precision modes — followed by the unchanged beam / greedy step.  Beams 2 .. 1024 (chunked select), num_beams == 1,
+ * the trie constraint, the trace, the early exit and its counters, L up to 512 and stream capture all apply.  prefix_table must be
+ * NULL (GDR_EINVAL naming it: the table stores adaptor results, and lm_head alone has nothing query-independent to store).
+ * gdr_t5_generate_workspace_bytes leaves out the adaptor K/V cache, the adaptor activations and the rows x (V+1) x d head-matrix
+ * buffer for such weights. */
 int gdr_t5_generate(const GdrT5DecoderWeights* w, const float* enc_hidden, const int64_t* enc_mask, int B, int L,
                     int num_beams, int max_length, double length_penalty, int num_return_sequences,
                     const GdrTrie* trie, const GdrPrefixTable* prefix_table /* NULL: compute every row */, int64_t* out_ids,
