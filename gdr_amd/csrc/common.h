@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdarg.h>
+#include <stdlib.h>
 
 #include "../../include/gdr_hip.h"
 
@@ -31,9 +32,22 @@ void count_launch();
     }                                                                            \
   } while (0)
 
+// a step of a launcher that hands its status (GDR_OK = 0) on
+#define GDR_TRY(x)                    \
+  do {                                \
+    if (int rc__ = (x)) return rc__;  \
+  } while (0)
+
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
-// Most beams per query of the two-stage path: the beam decode (decode.hip: check_beam_dims) produces up to this many rows per
+// An on/off environment switch (the A/B knobs): unset = dflt, otherwise atoi(value) != 0.  A call site keeps the answer in a
+// function-local `static const bool`, so every switch is read once per process.
+static inline bool env_flag(const char* name, bool dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) != 0 : dflt;
+}
+
+// Most beams per query of the two-stage path: the beam decode (beam.hip: check_beam_dims) produces up to this many rows per
 // query and the stage behind it (rerank.hip: RR_MAX_BEAMS, k of the long-list select) takes as many.
 constexpr int GDR_MAX_BEAMS = 1024;
 

@@ -1,5 +1,5 @@
 // Ranking by sorted 64-bit keys, shared by the similarity top-k (sim_topk.hip), the in-cluster rerank (rerank.hip) and the
-// beam step's top-2R (decode.hip).  One recipe: a float score becomes an order-preserving 32-bit key, packed as
+// beam step's top-2R (beam.hip).  One recipe: a float score becomes an order-preserving 32-bit key, packed as
 // key << 32 | ~low word (a position, a doc id, a flat beam * vocab index) — distinct keys, so their order is total: higher
 // score first, then the lower low word — the keys are bitonic-sorted in LDS, descending, and the first k unpacked.  Key 0 is
 // "no entry": it sorts behind every live key (fkey(-inf) = 0x007fffff > 0).

@@ -1,4 +1,4 @@
-"""The host side of the wide beam decode (up to 1024 beams, up to 2^17 candidates per query and step; csrc/decode.hip
+"""The host side of the wide beam decode (up to 1024 beams, up to 2^17 candidates per query and step; csrc/beam.hip
 check_beam_dims / beam_layout): the two workspace size functions and the argument checks, which come before any launch and
 before any pointer is dereferenced — no GPU needed.  The switch GDR_DECODE_BEAM_CHUNKED is read once per process, so its
 effect on the sizes is looked at in a child process."""
@@ -199,6 +199,6 @@ def test_the_beam_ceiling_is_the_rerank_s():
     src = lambda n: open(os.path.join(ROOT, "gdr_amd", "csrc", n)).read()          # noqa: E731
     assert int(re.search(r"constexpr int GDR_MAX_BEAMS = (\d+);", src("common.h")).group(1)) == MAX_BEAMS
     assert re.search(r"constexpr int RR_MAX_BEAMS = GDR_MAX_BEAMS;", src("rerank.hip"))
-    assert re.search(r"bd\.R <= GDR_MAX_BEAMS", src("decode.hip"))
+    assert re.search(r"bd\.R <= GDR_MAX_BEAMS", src("beam.hip"))
     head = open(os.path.join(ROOT, "include", "gdr_hip.h")).read()
     assert "2 <= num_beams <= 1024" in head and "131072" in head and "GDR_DECODE_BEAM_CHUNKED" in head

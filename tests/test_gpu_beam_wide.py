@@ -1,4 +1,4 @@
-"""The beam decode beyond 256 beams and beyond 8192 candidates per query and step (csrc/decode.hip: beam_topk_kernel up to 8192
+"""The beam decode beyond 256 beams and beyond 8192 candidates per query and step (csrc/beam.hip: beam_topk_kernel up to 8192
 keys, above that beam_norm_kernel / beam_chunk_kernel / sel_merge_kernel — the same top-2R list bit for bit), up to 1024 beams,
 through gdr_beam_search_table, gdr_t5_generate and the two-stage retriever.  Semantics: generation_utils.py:629-921.
 

@@ -1,5 +1,5 @@
 """GPU parity of generate() at num_beams = 1 — the reference's default call, its non-beam branch `_generate_no_beam_search`
-(generation_utils.py:553-627) — through gdr_t5_generate / gdr_t5_generate_bf16 (csrc/decode.hip greedy_step_kernel): against what the
+(generation_utils.py:553-627) — through gdr_t5_generate / gdr_t5_generate_bf16 (csrc/beam.hip greedy_step_kernel): against what the
 reference itself returned (g18), against the restatement tests/greedy_ref.py over the CPU oracle, and on crafted weights whose logits
 are a small-integer table, where EOS, padding, the early exit and exact ties are all decided by construction.  Ids are compared with
 torch.equal unless a test says otherwise."""

@@ -1,4 +1,4 @@
-"""The host side of generate() at num_beams = 1 (greedy decode, csrc/decode.hip greedy_step_kernel): the restatement of the reference's
+"""The host side of generate() at num_beams = 1 (greedy decode, csrc/beam.hip greedy_step_kernel): the restatement of the reference's
 non-beam loop (tests/greedy_ref.py) against what the reference itself returned (g18), the statements the GPU tests rely on about their
 CPU-chosen seeds and crafted tables, and the argument checks of the C entry points and the Python surface, which come before any launch
 and before any pointer is dereferenced — no GPU needed."""
