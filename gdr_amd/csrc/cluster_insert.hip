@@ -12,6 +12,17 @@
 //     receives at most CI_SORT_LDS documents; each cluster that receives more is rewritten by one ordered pass over all n inputs
 //     (one block per such cluster, the blocks run side by side), so the work bound is O(N + n + n * L) with L <= n / CI_SORT_LDS
 //     the number of those clusters.
+//   gdr_cluster_insert, REMOVAL mode (new_target == NULL, new_ids != NULL, n_new > 0): new_ids is the strictly
+//     ascending list of doc ids to take out of the CSR.  Every cluster keeps its surviving members in their order, a cluster
+//     that loses all of them becomes an empty segment, an id that is a member of no cluster is ignored.  out_members still has
+//     room for n_old entries; the first out_offsets[C] are written, the rest is left untouched; n_old - out_offsets[C] ids were
+//     removed.  Three launches, the shape of hist / scan / copy: one wave per cluster counts its members that are in the list
+//     (membership = binary search in the ascending list, no atomic at all) and stores the NEGATED count where the insert mode
+//     keeps its histogram -> the same one-block scan (new offsets, largest cluster, consistency of the old offsets) -> one wave
+//     per cluster walks its segment in order, RM_TILE members at a time: the ballot rank of a survivor inside its 64-member
+//     chunk plus a running base is its destination.  Integers only; the result is a function of the inputs alone.  The
+//     workspace is the insert mode's (per-cluster counters, nothing sized by n_old), which is why membership is tested twice.
+//     Cost O(n_old log n_new); one huge cluster serialises on one wave, as in insert_copy_kernel.
 #include "common.h"
 
 namespace gdr {
@@ -20,6 +31,8 @@ namespace {
 constexpr int CE_ROWS = 8;          // member rows in flight per wave
 constexpr int CE_MAX_D = 4096;      // 16 slices of 256 columns
 constexpr int CI_SORT_LDS = 4096;   // inserted tails up to this size are sorted in LDS (bitonic); longer ones are compacted in order
+constexpr int RM_CHUNKS = 4;        // removal: 64-member chunks one wave has in flight (their list lookups overlap)
+constexpr int RM_TILE = 64 * RM_CHUNKS;
 
 __global__ __launch_bounds__(256) void centroid_kernel(const float* __restrict__ D, int64_t N, int d4, int S,
                                                        const int32_t* __restrict__ offsets, const int32_t* __restrict__ members,
@@ -92,7 +105,8 @@ __global__ __launch_bounds__(256) void insert_hist_kernel(const int32_t* __restr
   }
 }
 
-// one block: new_off[c] = old_off[c] + sum_{c' < c} hist[c'], the largest new cluster, and the consistency of the old offsets
+// one block: new_off[c] = old_off[c] + sum_{c' < c} hist[c'], the largest new cluster, and the consistency of the old offsets.
+// hist[c] is the number of documents cluster c receives, or (removal mode) minus the number it loses.
 __global__ __launch_bounds__(1024) void insert_scan_kernel(const int32_t* __restrict__ old_off, const int32_t* __restrict__ hist,
                                                            int C, int64_t n_old, int32_t* __restrict__ new_off,
                                                            const int32_t* __restrict__ bad, int32_t* __restrict__ out_max) {
@@ -214,6 +228,70 @@ __global__ __launch_bounds__(256) void insert_sort_kernel(const int32_t* __restr
   }
 }
 
+// removal mode: is `id` in the strictly ascending list ids[0, n)?
+__device__ __forceinline__ bool in_ascending_list(const int32_t* __restrict__ ids, int n, int32_t id) {
+  int lo = 0, hi = n;
+  while (lo < hi) {
+    const int mid = lo + ((hi - lo) >> 1);
+    if (ids[mid] < id) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo < n && ids[lo] == id;
+}
+
+// one wave per cluster: hist[c] = -(members of the cluster that are in the removal list).  No atomics.
+__global__ __launch_bounds__(256) void remove_count_kernel(const int32_t* __restrict__ old_off, const int32_t* __restrict__ old_mem,
+                                                           int C, int64_t n_old, const int32_t* __restrict__ ids, int n,
+                                                           int32_t* __restrict__ hist) {
+  const int c = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (c >= C) return;  // wave-uniform
+  int64_t lo = old_off[c], hi = old_off[c + 1];
+  if (lo < 0 || hi > n_old || hi < lo) lo = hi = 0;  // a malformed segment reads nothing (reported through out_max)
+  int gone = 0;
+  for (int64_t j0 = lo; j0 < hi; j0 += RM_TILE) {
+    int32_t m[RM_CHUNKS];
+#pragma unroll
+    for (int u = 0; u < RM_CHUNKS; ++u) {
+      const int64_t j = j0 + 64 * u + lane;
+      m[u] = j < hi ? old_mem[j] : 0;
+    }
+#pragma unroll
+    for (int u = 0; u < RM_CHUNKS; ++u) gone += (j0 + 64 * u + lane < hi && in_ascending_list(ids, n, m[u])) ? 1 : 0;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) gone += __shfl_xor(gone, o);
+  if (lane == 0) hist[c] = -gone;
+}
+
+// one wave per cluster: the surviving members, in their order, from the start of the cluster's new segment
+__global__ __launch_bounds__(256) void remove_compact_kernel(const int32_t* __restrict__ old_off, const int32_t* __restrict__ old_mem,
+                                                             int C, int64_t n_old, const int32_t* __restrict__ ids, int n,
+                                                             const int32_t* __restrict__ new_off, int32_t* __restrict__ out_mem) {
+  const int c = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (c >= C) return;  // wave-uniform
+  int64_t lo = old_off[c], hi = old_off[c + 1];
+  if (lo < 0 || hi > n_old || hi < lo) lo = hi = 0;
+  int64_t base = new_off[c];  // next free position of the new segment (wave-uniform)
+  for (int64_t j0 = lo; j0 < hi; j0 += RM_TILE) {  // every lane of the wave takes every iteration: the ballots are whole
+    int32_t m[RM_CHUNKS];
+    bool keep[RM_CHUNKS];
+#pragma unroll
+    for (int u = 0; u < RM_CHUNKS; ++u) {
+      const int64_t j = j0 + 64 * u + lane;
+      m[u] = j < hi ? old_mem[j] : 0;
+    }
+#pragma unroll
+    for (int u = 0; u < RM_CHUNKS; ++u) keep[u] = j0 + 64 * u + lane < hi && !in_ascending_list(ids, n, m[u]);
+#pragma unroll
+    for (int u = 0; u < RM_CHUNKS; ++u) {
+      const uint64_t bal = __ballot(keep[u]);
+      const int64_t p = base + __popcll(bal & ((1ull << lane) - 1ull));
+      if (keep[u] && p >= 0 && p < n_old) out_mem[p] = m[u];  // p <= its old position while the offsets are consistent
+      base += __popcll(bal);
+    }
+  }
+}
+
 }  // namespace
 }  // namespace gdr
 
@@ -252,11 +330,14 @@ extern "C" int gdr_cluster_insert(const int32_t* offsets, const int32_t* members
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   GDR_CHECK_ARG(offsets && out_offsets && out_members && out_max, "cluster_insert: null pointer");
   GDR_CHECK_ARG(members || n_old == 0, "cluster_insert: null members with n_old=%lld", (long long)n_old);
-  GDR_CHECK_ARG((new_ids && new_target) || n_new == 0, "cluster_insert: null new_ids / new_target with n_new=%d", n_new);
+  const bool removal = new_ids && !new_target && n_new > 0;  // new_target == NULL: new_ids are the ids to take out
+  GDR_CHECK_ARG((new_ids && new_target) || n_new == 0 || removal, "cluster_insert: null new_ids / new_target with n_new=%d", n_new);
   GDR_CHECK_ARG(n_clusters > 0 && n_old >= 0 && n_new >= 0, "cluster_insert: bad size n_clusters=%d n_old=%lld n_new=%d",
                 n_clusters, (long long)n_old, n_new);
-  GDR_CHECK_ARG(n_old + n_new < ((int64_t)1 << 31), "cluster_insert: n_old + n_new = %lld does not fit int32 doc ids",
-                (long long)(n_old + n_new));
+  GDR_CHECK_ARG(n_old + (removal ? 0 : n_new) < ((int64_t)1 << 31),
+                "cluster_insert: n_old + n_new = %lld does not fit int32 doc ids", (long long)(n_old + n_new));
+  GDR_CHECK_ARG(!removal || (target_map == nullptr && n_map == 0),
+                "cluster_insert: removal (new_target == NULL) takes no target_map (n_map=%d)", n_map);
   GDR_CHECK_ARG(target_map == nullptr ? n_map == 0 : n_map > 0, "cluster_insert: target_map / n_map=%d disagree", n_map);
   GDR_CHECK_ARG(workspace, "cluster_insert: null workspace");
   const size_t need = gdr_cluster_insert_workspace_bytes(n_clusters);
@@ -272,6 +353,19 @@ extern "C" int gdr_cluster_insert(const int32_t* offsets, const int32_t* members
   if (hipMemsetAsync(ws, 0, need, stream) != hipSuccess) {
     set_error("cluster_insert: hipMemsetAsync failed");
     return GDR_EHIP;
+  }
+  if (removal) {
+    const dim3 per_cluster((unsigned)((n_clusters + 3) / 4));
+    hipLaunchKernelGGL(remove_count_kernel, per_cluster, dim3(256), 0, stream, offsets, members, n_clusters, n_old, new_ids, n_new,
+                       hist);
+    GDR_CHECK_LAUNCH("remove_count_kernel");
+    hipLaunchKernelGGL(insert_scan_kernel, dim3(1), dim3(1024), 0, stream, offsets, hist, n_clusters, n_old, out_offsets, bad,
+                       out_max);
+    GDR_CHECK_LAUNCH("insert_scan_kernel");
+    hipLaunchKernelGGL(remove_compact_kernel, per_cluster, dim3(256), 0, stream, offsets, members, n_clusters, n_old, new_ids,
+                       n_new, out_offsets, out_members);
+    GDR_CHECK_LAUNCH("remove_compact_kernel");
+    return GDR_OK;
   }
   const unsigned gn = (unsigned)std::min<int64_t>(std::max<int64_t>((n_new + 255) / 256, 1), 2048);
   if (n_new > 0) {

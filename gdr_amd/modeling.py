@@ -341,6 +341,22 @@ def expand_cluster_index(doc_embed, index, rows, centroids=None):
     return index.with_csr(csr[:C_ + 1], csr[C_ + 1:]), fc.cmap[tgt.long()].cpu().numpy()
 
 
+def shrink_cluster_index(index, rows, device=None):
+    """The counterpart of expand_cluster_index: takes the documents `rows` (doc ids, any order, repeats allowed) out of the
+    clusters of `index` (codec.ClusterIndex) through the device call (ops.cluster_remove) — every cluster keeps its other
+    members in their order, a row that is in no cluster is ignored, names unchanged.  Returns the shrunk codec.ClusterIndex."""
+    import numpy as np
+    dev = torch.device(device if device is not None else "cuda")
+    rows = np.asarray(rows).reshape(-1)
+    if rows.size and (not np.issubdtype(rows.dtype, np.integer) or rows.min() < 0 or rows.max() >= 2 ** 31):
+        raise _ffi.GdrError("shrink_cluster_index: rows must be int32 doc ids")
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)   # noqa: E731
+    offs, mem, _mx, _gone = ops.cluster_remove(up(index.offsets), up(index.members), up(np.unique(rows)))
+    csr = torch.cat([offs, mem]).cpu().numpy()                                      # one read-back of the compacted CSR
+    C_ = len(index.names)
+    return index.with_csr(csr[:C_ + 1], csr[C_ + 1:])
+
+
 class GDRRetriever:
     """Two-stage GDR retrieval = `T5FineTuner.validation_step_i` (main_models.py:1337-1642):
     beam-decode cluster ids -> id_mapping lookup -> tanh(q·d) over the candidates -> + alpha*softmax(beam scores)
@@ -398,30 +414,12 @@ class GDRRetriever:
             raise _ffi.GdrError("add_documents needs the fp32 doc_embed (the bf16 precision mode is not supported)")
         dev = self.doc_embed.device
         N, d = self.doc_embed.shape
-        if self.doc_tokens is not None and tokens is None:
-            raise _ffi.GdrError("add_documents: the re-encode path is configured (doc_tokens=): pass tokens= as well")
-        if tokens is not None:
-            tok, msk = (t.to(dev) for t in tokens)
-            if tok.dim() != 2 or msk.shape != tok.shape:
-                raise _ffi.GdrError(f"add_documents: tokens {tuple(tok.shape)} / mask {tuple(msk.shape)} must be [n, Lp]")
-        if embeds is None:
-            if tokens is None:
-                raise _ffi.GdrError("add_documents: pass embeds= or tokens=")
-            if getattr(self.encoder, "bert", None) is None:
-                raise _ffi.GdrError("add_documents(tokens=...) needs the doc tower (doc_tower=)")
-            embeds = self.encoder(passage={"input_ids": tok, "attention_mask": msk})
-        embeds = torch.as_tensor(embeds)
-        if embeds.dtype != torch.float32 or embeds.dim() != 2 or embeds.shape[1] != d:
-            raise _ffi.GdrError(f"add_documents: embeds must be fp32 [n, {d}], got {embeds.dtype} {tuple(embeds.shape)}")
+        embeds, tok, msk = self._document_rows("add_documents", embeds, tokens)
         n = embeds.shape[0]
-        if tokens is not None and tok.shape[0] != n:
-            raise _ffi.GdrError(f"add_documents: {n} embeddings but {tok.shape[0]} token rows")
         if N + n >= 2 ** 31:
             raise _ffi.GdrError("add_documents: doc ids must fit int32")
         embeds = embeds.to(dev).contiguous()
-        if getattr(self, "_centroids", None) is None:
-            self._centroids = ops.FrozenCentroids(self.doc_embed, self.index)          # frozen: the index as built
-        fc = self._centroids
+        fc = self._freeze_centroids()
         tgt = fc.assign(embeds, compact=True)
         # doc_embed: append into a geometrically grown buffer (a 64-doc add does not copy the corpus)
         buf = getattr(self, "_doc_buf", None)
@@ -445,6 +443,153 @@ class GDRRetriever:
         csr = torch.cat([offs, mem]).cpu().numpy()                                  # one read-back of the merged CSR
         self.index = self.index.with_csr(csr[:C_ + 1], csr[C_ + 1:])
         return np.arange(N, N + n, dtype=np.int64), fc.cmap[tgt.long()].cpu().numpy()
+
+    def _document_rows(self, what, embeds, tokens):
+        """The embeds= / tokens= arguments of add_documents and update_documents, validated: (embeds fp32 [n, d] — embedded by
+        the doc tower when only tokens were given —, input_ids, attention_mask on the device or None, None)."""
+        dev = self.doc_embed.device
+        d = self.doc_embed.shape[1]
+        tok = msk = None
+        if self.doc_tokens is not None and tokens is None:
+            raise _ffi.GdrError(f"{what}: the re-encode path is configured (doc_tokens=): pass tokens= as well")
+        if tokens is not None:
+            tok, msk = (t.to(dev) for t in tokens)
+            if tok.dim() != 2 or msk.shape != tok.shape:
+                raise _ffi.GdrError(f"{what}: tokens {tuple(tok.shape)} / mask {tuple(msk.shape)} must be [n, Lp]")
+        if embeds is None:
+            if tokens is None:
+                raise _ffi.GdrError(f"{what}: pass embeds= or tokens=")
+            if getattr(self.encoder, "bert", None) is None:
+                raise _ffi.GdrError(f"{what}(tokens=...) needs the doc tower (doc_tower=)")
+            embeds = self.encoder(passage={"input_ids": tok, "attention_mask": msk})
+        embeds = torch.as_tensor(embeds)
+        if embeds.dtype != torch.float32 or embeds.dim() != 2 or embeds.shape[1] != d:
+            raise _ffi.GdrError(f"{what}: embeds must be fp32 [n, {d}], got {embeds.dtype} {tuple(embeds.shape)}")
+        n = embeds.shape[0]
+        if tokens is not None and tok.shape[0] != n:
+            raise _ffi.GdrError(f"{what}: {n} embeddings but {tok.shape[0]} token rows")
+        return embeds, tok, msk
+
+    def _lifecycle_ids(self, what, ids):
+        """The refusals remove_documents / update_documents share with add_documents, then `ids` as int64 numpy in [0, N)."""
+        import numpy as np
+        if self.sharded is not None:
+            raise _ffi.GdrError(f"{what}: a sharded retriever cannot change its documents (sharded removal is not supported)")
+        if self.doc_embed is None or self.doc_embed.dtype != torch.float32:
+            raise _ffi.GdrError(f"{what} needs the fp32 doc_embed (the bf16 precision mode is not supported)")
+        ids = np.asarray(ids.cpu() if torch.is_tensor(ids) else ids).reshape(-1)
+        if ids.size and not np.issubdtype(ids.dtype, np.integer):
+            raise _ffi.GdrError(f"{what}: ids must be integers, got {ids.dtype}")
+        ids = ids.astype(np.int64)
+        N = self.doc_embed.shape[0]
+        if ids.size and (ids.min() < 0 or ids.max() >= N):
+            raise _ffi.GdrError(f"{what}: doc ids must lie in [0, {N})")
+        return ids
+
+    def _freeze_centroids(self):
+        """The centroids every add / remove / update uses, computed before the first of them touches the index."""
+        if getattr(self, "_centroids", None) is None:
+            self._centroids = ops.FrozenCentroids(self.doc_embed, self.index)          # frozen: the index as built
+        return self._centroids
+
+    def _edit_csr(self, remove, insert=None, targets=None):
+        """Removes the ascending int32 ids `remove` from the member CSR and then, if given, inserts `insert` (ascending) into
+        the compact targets `targets` of the frozen centroids; replaces the device index and the host ClusterIndex (one
+        read-back), as add_documents does.  Returns the number of ids removed."""
+        import numpy as np
+        dev = self.doc_embed.device
+        fc = self._centroids
+        dci = self._device_index()
+        streams = getattr(self, "_streams", ())
+        if dci is not None:
+            gone = dci.remove(remove, streams=streams)
+            if insert is not None:
+                dci.insert(insert, targets, target_map=fc.cmap, streams=streams)
+            offs, mem = dci.offsets, dci.members[:dci.n_members]
+        else:
+            up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)   # noqa: E731
+            offs, mem, _mx, gone = ops.cluster_remove(up(self.index.offsets), up(self.index.members), remove)
+            if insert is not None:
+                offs, mem, _mx = ops.cluster_insert(offs, mem, insert, targets, fc.cmap)
+        C_ = len(self.index.names)
+        csr = torch.cat([offs, mem]).cpu().numpy()                                  # one read-back of the edited CSR
+        self.index = self.index.with_csr(csr[:C_ + 1], csr[C_ + 1:])
+        return gone
+
+    @torch.no_grad()
+    def remove_documents(self, ids):
+        """Withdraws documents from the index: `ids` (any integer array-like, sorted and de-duplicated here, each in [0, N))
+        leave their clusters and are never stage-2 candidates again.  Their rows of doc_embed / doc_tokens stay where they
+        are — doc ids are row numbers and never shift.  An id that is in no cluster (removed earlier) is ignored.  Every
+        cluster keeps its other members in their order; a cluster that loses all of them stays, empty, keeps its frozen
+        centroid and can receive documents again (add_documents / update_documents).  The centroids are frozen from the index
+        as built before the first add / remove / update touches it, so the order of those calls never changes them.  Both the
+        device index and the host ClusterIndex are replaced (one read-back).  Returns the number of documents removed.
+        Must not run while validation_steps() has steps in flight.  Raises GdrError for a sharded retriever, a bf16
+        doc_embed and an id outside [0, N); nothing has changed then."""
+        import numpy as np
+        ids = np.unique(self._lifecycle_ids("remove_documents", ids))
+        self._freeze_centroids()
+        if ids.size == 0:
+            return 0
+        return self._edit_csr(torch.from_numpy(ids.astype(np.int32)).to(self.doc_embed.device))
+
+    @torch.no_grad()
+    def update_documents(self, ids, embeds=None, tokens=None):
+        """Re-writes documents in place: row ids[i] of doc_embed becomes embeds[i] (embeds= / tokens= as in add_documents; with
+        the re-encode path configured the rows of doc_tokens are overwritten too, and doc_tokens is widened once when a new
+        passage is longer than every earlier one), the ids leave the clusters they are in and join the cluster of the
+        nearest frozen centroid, exactly as a document added with that embedding would.  An id that is in no cluster (removed
+        earlier) is thereby restored.  `ids`: distinct doc ids in [0, N), in any order.  Returns the cluster index of each,
+        int32[n], in the order of `ids`.
+        Must not run while validation_steps() has steps in flight.  Raises GdrError for a sharded retriever, a bf16
+        doc_embed, ids that repeat or lie outside [0, N), and embeds / tokens that do not fit; nothing has changed then."""
+        import numpy as np
+        ids = self._lifecycle_ids("update_documents", ids)
+        dev = self.doc_embed.device
+        embeds, tok, msk = self._document_rows("update_documents", embeds, tokens)
+        if embeds.shape[0] != ids.size:
+            raise _ffi.GdrError(f"update_documents: {ids.size} ids but {embeds.shape[0]} embeddings")
+        order = np.argsort(ids, kind="stable")
+        if np.any(np.diff(ids[order]) == 0):
+            raise _ffi.GdrError("update_documents: an id is given twice")
+        fc = self._freeze_centroids()
+        if ids.size == 0:
+            return np.zeros(0, np.int32)
+        sel = torch.from_numpy(order).to(dev)
+        rows = torch.from_numpy(ids[order]).to(dev)                                 # ascending int64
+        embeds = embeds.to(dev).index_select(0, sel).contiguous()
+        tgt = fc.assign(embeds, compact=True)
+        self.doc_embed.index_copy_(0, rows, embeds)
+        if self.doc_tokens is not None:
+            self._overwrite_tokens(rows, tok.index_select(0, sel), msk.index_select(0, sel))
+        ids32 = rows.to(torch.int32)
+        self._edit_csr(ids32, insert=ids32, targets=tgt)
+        out = np.empty(ids.size, np.int32)
+        out[order] = fc.cmap[tgt.long()].cpu().numpy()
+        return out
+
+    def _overwrite_tokens(self, rows, tok, msk):
+        """doc_tokens[rows] = (tok, msk), PAD 0 / mask 0 behind a shorter passage; a longer one widens the buffers first (one
+        copy of the token table, as in _append_tokens)."""
+        old_t, old_m = self.doc_tokens
+        N, L0 = old_t.shape
+        L1 = tok.shape[1]
+        if L1 > L0:
+            bt, bm = getattr(self, "_tok_buf", (None, None))
+            live = bt is not None and bt.data_ptr() == old_t.data_ptr() and bm.data_ptr() == old_m.data_ptr() and bt.shape[1] == L0
+            cap = bt.shape[0] if live else N
+            bt = torch.zeros((cap, L1), dtype=old_t.dtype, device=old_t.device)
+            bm = torch.zeros((cap, L1), dtype=old_m.dtype, device=old_m.device)
+            bt[:N, :L0].copy_(old_t)
+            bm[:N, :L0].copy_(old_m)
+            self._tok_buf = (bt, bm)
+            self.doc_tokens = (bt[:N], bm[:N])
+        dst_t, dst_m = self.doc_tokens
+        W = dst_t.shape[1]
+        pad = lambda x: torch.nn.functional.pad(x, (0, W - L1))                     # noqa: E731
+        dst_t.index_copy_(0, rows, pad(tok.to(dst_t.dtype)))
+        dst_m.index_copy_(0, rows, pad(msk.to(dst_m.dtype)))
 
     def _append_tokens(self, tok, msk):
         """doc_tokens += (tok, msk) in backing buffers grown like doc_embed's: rows geometrically, and once wider when a passage is

@@ -461,6 +461,20 @@ class DeviceClusterIndex:
         self.n_members, self.max_cluster = int(mem.numel()), mx
         self._make_struct()
 
+    def remove(self, ids, streams=()):
+        """Takes documents out of the member CSR on the device (cluster_remove): ids int32[n] strictly ascending; every cluster
+        keeps its surviving members in their order, an id that is in no cluster is ignored.  Swaps in the compacted CSR, updates
+        n_members and max_cluster (which may shrink, and with it the candidate stride of candidates()) and rebuilds `struct`;
+        the old arrays are kept alive on every stream in `streams`, as in insert().  Returns the number of ids removed."""
+        offs, mem, mx, gone = cluster_remove(self.offsets, self.members[:self.n_members], ids)
+        for t in (self.offsets, self.members):
+            for st in streams:
+                t.record_stream(st)
+        self.offsets, self.members = offs, (mem if mem.numel() else torch.zeros(1, dtype=torch.int32, device=mem.device))
+        self.n_members, self.max_cluster = int(mem.numel()), mx
+        self._make_struct()
+        return gone
+
     def candidates(self, out_ids, B, R):
         """out_ids int64[B*R, max_length] (device, untrimmed) -> (cluster_of int32[B*R], cand_offsets int32[B,R+1],
         cand_ids int32[B,stride], stride = R * largest cluster) — the per-query block layout of rerank_topk
@@ -594,6 +608,34 @@ def cluster_insert(offsets, members, new_ids, new_cluster, target_map=None, work
     if mx < 0:
         raise _ffi.GdrError("cluster_insert: a target is out of range or the old offsets are inconsistent")
     return out_off, out_mem[:n_old + n], mx
+
+
+def cluster_remove(offsets, members, remove_ids, workspace=None):
+    """gdr_cluster_insert in its removal mode (new_target == NULL): the member CSR (offsets int32[C+1], members int32[n_old],
+    segments in any order) minus remove_ids int32[n] (STRICTLY ascending; checked here, one read-back) -> (offsets int32[C+1],
+    members int32[n_left], largest cluster, number of ids removed).  Every cluster keeps its surviving members in their order;
+    an id that is in no cluster is ignored.  One more read-back: the largest cluster size and the new total."""
+    for t in (offsets, members, remove_ids):
+        if t.dtype != torch.int32:
+            raise _ffi.GdrError(f"cluster_remove: expected int32, got {t.dtype}")
+    C_ = offsets.numel() - 1
+    n_old, n = members.numel(), remove_ids.numel()
+    if n > 1 and not bool((remove_ids[1:] > remove_ids[:-1]).all()):
+        raise _ffi.GdrError("cluster_remove: remove_ids must be strictly ascending")
+    _need_cuda(offsets, members, remove_ids)
+    offsets, members, remove_ids = (t.contiguous() for t in (offsets, members, remove_ids))
+    dev = offsets.device
+    out_off = torch.empty((C_ + 2,), dtype=torch.int32, device=dev)             # [C+1] = out_max: one read-back for both
+    out_mem = torch.empty((max(n_old, 1),), dtype=torch.int32, device=dev)
+    need = lib().gdr_cluster_insert_workspace_bytes(C_)
+    ws = (workspace or Workspace(dev)).get(need)
+    check(lib().gdr_cluster_insert(ptr(offsets), ptr(members) if n_old else None, C_, n_old, ptr(remove_ids) if n else None,
+                                   None, n, None, 0, ptr(out_off), ptr(out_mem), ptr(out_off[C_ + 1:]), ptr(ws), ws.numel(),
+                                   stream_ptr()), "gdr_cluster_insert")
+    n_left, mx = (int(x) for x in out_off[C_:].tolist())
+    if mx < 0:
+        raise _ffi.GdrError("cluster_remove: the old offsets are inconsistent")
+    return out_off[:C_ + 1], out_mem[:n_left], mx, n_old - n_left
 
 
 KMEANS_MAX_K = 64

@@ -404,7 +404,17 @@ int gdr_cluster_candidates(const GdrClusterIndex* ci, const int64_t* out_ids, in
  *   offsets were inconsistent (offsets[0] != 0, offsets[n_clusters] != n_old, a negative segment): the output is then
  *   invalid.  Deterministic (the result does not depend on atomic order); O(n_old + n_new) while no cluster receives more than
  *   4,096 documents, plus one ordered pass over the n_new inputs for each cluster that does; n_old + n_new < 2^31.
- *   workspace: gdr_cluster_insert_workspace_bytes(n_clusters) bytes. */
+ *   workspace: gdr_cluster_insert_workspace_bytes(n_clusters) bytes.
+ *
+ * Remove is a mode of the same call, selected by new_target == NULL with new_ids != NULL and n_new > 0: new_ids
+ *   int32[n_new] (STRICTLY ASCENDING) are the doc ids to take out of the member CSR.  target_map must be NULL and n_map 0
+ *   (GDR_EINVAL otherwise).  The segments of the CSR may hold their members in any order.  Every cluster keeps its surviving
+ *   members in their order; a cluster that loses all of them becomes an empty segment; an id that is a member of no cluster
+ *   is ignored.  out_members still has room for n_old entries: the first out_offsets[n_clusters] are written, the rest of the
+ *   buffer is left untouched, and n_old - out_offsets[n_clusters] ids were removed.  out_max = the largest cluster afterwards,
+ *   or -1 under the "old offsets inconsistent" conditions above (the output is then invalid).  Integers only, no atomics: the
+ *   result is a function of the inputs alone.  Same workspace; O(n_old log n_new), one wave per cluster (one huge cluster
+ *   serialises on one wave, as the copy of the insert mode does); n_old < 2^31. */
 int gdr_cluster_centroids(const float* D, int64_t N, int d, const int32_t* offsets, const int32_t* members, int64_t n_members,
                           int n_clusters, float* out_centroids, int32_t* out_counts, void* stream);
 size_t gdr_cluster_insert_workspace_bytes(int n_clusters);
