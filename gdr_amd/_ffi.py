@@ -15,6 +15,7 @@ RERANK_POSITIONS = 1
 RERANK_CHUNKED = 2
 SIM_EXHAUSTIVE = 1
 SIM_NO_STREAM = 2
+SIM_LIVE_MASK = 4                # the workspace starts with a live-row bitmap (ops.LiveRows): rank the live rows only
 EPI_NONE, EPI_RESIDUAL, EPI_RELU, EPI_BIAS, EPI_BIAS_RELU, EPI_BIAS_RESIDUAL, EPI_BIAS_GELU = range(7)
 # gdr_linear_f32_form (include/gdr_hip.h GDR_F32_FORM_*): the kernel form of a dense fp32 linear; 0 = a shape the linear refuses
 (F32_FORM_TILES, F32_FORM_PERSISTENT, F32_FORM_SMALL, F32_FORM_SMALL_SPLITK, F32_FORM_SPLITK, F32_FORM_STREAMK_256,

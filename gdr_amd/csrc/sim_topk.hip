@@ -37,7 +37,9 @@ struct SimPlan {
 
 // survivors: by how much the filter pass's threshold admits more docs than the k-th largest sample score would (1 = that score
 // itself; the pre-filter lowers it by 2 eps_q, see prefilter_survivor_factor).
-static SimPlan make_plan(int B, int64_t N, int k, bool exhaustive, double survivors = 1.0) {
+// base: bytes in front of the plan's own scratch (GDR_SIM_LIVE_MASK: the caller's row bitmap, live_mask_bytes) — every offset and
+// the total move by it; 0 for every other call.
+static SimPlan make_plan(int B, int64_t N, int k, bool exhaustive, double survivors = 1.0, size_t base = 0) {
   SimPlan p{};
   p.tiles_m = (N + TILE - 1) / TILE;
   double target = sqrt((double)k * (double)N);
@@ -59,7 +61,7 @@ static SimPlan make_plan(int B, int64_t N, int k, bool exhaustive, double surviv
     p.cap = p.n_slots + (int64_t)(4.0 * expect * survivors) + 4096;
     p.cap = (p.cap + TILE - 1) / TILE * TILE;
   }
-  size_t o = 0;
+  size_t o = base;
   p.off_val = o, o += align_up((size_t)B * p.cap * sizeof(float), 256);
   p.off_idx = o, o += align_up((size_t)B * p.cap * sizeof(int32_t), 256);
   p.off_cnt = o, o += align_up((size_t)B * CNT_STRIDE * sizeof(int32_t), 256);
@@ -626,6 +628,92 @@ static int launch_select_deep(const float* vals, const int32_t* idxs, const int3
   return GDR_OK;
 }
 
+// ---- GDR_SIM_LIVE_MASK: the top-k over the live rows only ---------------------------------------------------------------------
+// The caller's bitmap (bit r % 32 of word r / 32 = row r is live) sits in front of the plan's scratch and is only read.  The mask
+// is applied to the CANDIDATE LISTS between the existing passes, not in the epilogues that fill them: the selects already skip
+// id < 0 and radix_kth_key already ignores -inf scores, so a dead entry rewritten to (-inf, -1) is padding to every kernel behind
+// it.   sample -> mask [0, n_slots) -> threshold -> (fix-up) -> filter -> mask [n_slots, cnt) -> select.
+// The threshold is then the k-th largest LIVE sample score: a lower bound of the k-th largest live score overall, by the argument
+// at the top of this file applied to the live rows.  The filter pass still appends dead rows that reach it; the second mask drops
+// them, and a list they overflow is reported through status like any other.
+static size_t live_mask_bytes(int64_t N) {
+  return align_up((size_t)((N + 31) / 32) * sizeof(uint32_t), 256);
+}
+
+constexpr int MASK_THREADS = 256;
+// Entries [lo, hi) of every query's list (blockIdx.y strides the queries), hi = hi_fixed (the sample block: the counter is not set yet) or, with hi_fixed < 0,
+// min(cnt[q], cap): an entry whose row is dead becomes (-inf, -1).  A thread takes four consecutive entries — lo and cap are
+// multiples of four (of TILE), so a group never leaves the list — loads their ids as one int4, and touches the scores only where
+// a row is dead.  Entries of a group past hi are written back as they were read.  An id outside [0, N) cannot reach the bitmap.
+__global__ __launch_bounds__(MASK_THREADS) void sim_live_mask_kernel(float* __restrict__ cand_val, int32_t* __restrict__ cand_idx,
+                                                                     const int32_t* __restrict__ cnt, int64_t cap, int64_t lo,
+                                                                     int64_t hi_fixed, const uint32_t* __restrict__ live, int64_t N,
+                                                                     int B) {
+  const int64_t step = (int64_t)gridDim.x * MASK_THREADS * 4;
+  for (int64_t q = blockIdx.y; q < B; q += gridDim.y) {
+    int64_t hi = hi_fixed >= 0 ? hi_fixed : (int64_t)cnt[q * CNT_STRIDE];
+    if (hi > cap) hi = cap;
+    float* cv = cand_val + q * cap;
+    int32_t* ci = cand_idx + q * cap;
+    for (int64_t i = lo + ((int64_t)blockIdx.x * MASK_THREADS + threadIdx.x) * 4; i < hi; i += step) {
+      int4 id = *reinterpret_cast<const int4*>(ci + i);
+      auto dead = [&](int32_t r, int j) -> bool {
+        if (i + j >= hi || r < 0) return false;  // past the list / padding already
+        return r >= N || ((live[r >> 5] >> (r & 31)) & 1u) == 0u;
+      };
+      const bool d0 = dead(id.x, 0), d1 = dead(id.y, 1), d2 = dead(id.z, 2), d3 = dead(id.w, 3);
+      if (d0 || d1 || d2 || d3) {
+        float4 v = *reinterpret_cast<const float4*>(cv + i);
+        if (d0) v.x = -INFINITY, id.x = -1;
+        if (d1) v.y = -INFINITY, id.y = -1;
+        if (d2) v.z = -INFINITY, id.z = -1;
+        if (d3) v.w = -INFINITY, id.w = -1;
+        *reinterpret_cast<float4*>(cv + i) = v;
+        *reinterpret_cast<int4*>(ci + i) = id;
+      }
+    }
+  }
+}
+
+// Fewer than k live rows in the sample tiles: radix_kth_key clamps `need` to the entries it counted, so thr[q] came out as the
+// smallest live sample score — no lower bound of anything, and the select would drop every entry below it with status 0.  The
+// live sample count depends on the bitmap and the plan alone (the same for every query): one workgroup counts it and, if it is
+// short, lowers every thr[q] to -inf.  The filter pass then keeps every row: either the whole corpus fits the list (exact), or the
+// list overflows and status[q] = 1 sends the query to the exhaustive re-run, as for any overflow.
+__global__ __launch_bounds__(256) void sim_live_thr_fixup_kernel(const uint32_t* __restrict__ live, int64_t N, int64_t n_sample_tiles,
+                                                                 int stride, int k, float* __restrict__ thr, int B) {
+  __shared__ int red[4];
+  const int64_t n_words = (N + 31) / 32;
+  int c = 0;
+  for (int64_t e = threadIdx.x; e < n_sample_tiles * (TILE / 32); e += 256) {
+    const int64_t w = (e / (TILE / 32)) * stride * (TILE / 32) + e % (TILE / 32);
+    if (w < n_words) {
+      uint32_t bits = live[w];
+      const int64_t rem = N - w * 32;
+      if (rem < 32) bits &= (1u << rem) - 1u;  // bits past N in the last word are ignored
+      c += __popc(bits);
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = c;
+  __syncthreads();
+  if (red[0] + red[1] + red[2] + red[3] >= k) return;
+  for (int q = threadIdx.x; q < B; q += 256) thr[q] = -INFINITY;
+}
+
+static int launch_live_mask(const SimEpilogue& ep, const SimPlan& p, int B, int64_t lo, int64_t hi_fixed, const uint32_t* live, int64_t N,
+                            hipStream_t stream) {
+  const int64_t span = (hi_fixed >= 0 ? hi_fixed : p.cap) - lo;
+  if (span <= 0) return GDR_OK;
+  int64_t gx = (span + MASK_THREADS * 4 - 1) / (MASK_THREADS * 4);
+  if (gx > 64) gx = 64;
+  hipLaunchKernelGGL(sim_live_mask_kernel, dim3((unsigned)gx, (unsigned)(B < 65535 ? B : 65535)), dim3(MASK_THREADS), 0, stream, ep.cand_val,
+                     ep.cand_idx, (const int32_t*)ep.cand_cnt, p.cap, lo, hi_fixed, live, N, B);
+  GDR_CHECK_LAUNCH("sim_live_mask_kernel");
+  return GDR_OK;
+}
+
 }  // namespace gdr
 
 // The size a caller is told: the largest plan of any k' <= k, so that the answer never shrinks when k grows and a buffer sized for
@@ -638,6 +726,8 @@ extern "C" size_t gdr_sim_topk_workspace_bytes(int B, int64_t N, int d, int k, i
   (void)d;
   if (B <= 0 || N <= 0 || k <= 0) return 0;
   const bool exhaustive = (flags & GDR_SIM_EXHAUSTIVE) != 0;
+  if (flags & GDR_SIM_LIVE_MASK)  // the caller's row bitmap in front of the same plan
+    return gdr_sim_topk_workspace_bytes(B, N, d, k, flags & ~GDR_SIM_LIVE_MASK) + gdr::live_mask_bytes(N);
   size_t best = gdr::make_plan(B, N, k, exhaustive).total;
   if (exhaustive) return best;  // stride 1 whatever k: the plan does not depend on k
   double target = sqrt((double)k * (double)N);
@@ -720,12 +810,18 @@ int gdr::sim_topk_impl(const void* Q, int B, const void* D, int64_t N, int d, in
                 (long long)N);
   GDR_CHECK_ARG(((uintptr_t)Q & 15) == 0 && ((uintptr_t)D & 15) == 0 && ((uintptr_t)workspace & 255) == 0,
                 "sim_topk: Q, D must be 16-byte and workspace 256-byte aligned");
-  const SimPlan p = make_plan(B, N, k, (flags & GDR_SIM_EXHAUSTIVE) != 0);
-  if (workspace_bytes < p.total) {
-    set_error("sim_topk: workspace %zu < required %zu", workspace_bytes, p.total);
+  // GDR_SIM_LIVE_MASK: the first live_mask_bytes(N) bytes of the workspace are the caller's row bitmap (read only); the plan sits behind it
+  const bool masked = (flags & GDR_SIM_LIVE_MASK) != 0;
+  const SimPlan p = make_plan(B, N, k, (flags & GDR_SIM_EXHAUSTIVE) != 0, 1.0, masked ? live_mask_bytes(N) : 0);
+  // A masked call is held to the size its caller was told, not to this k's own layout (which may dip below the unflagged answer,
+  // see gdr_sim_topk_workspace_bytes): a buffer sized without the flag — no room reserved for the bitmap — is refused at every shape.
+  const size_t required = masked ? gdr_sim_topk_workspace_bytes(B, N, d, k, flags) : p.total;
+  if (workspace_bytes < required) {
+    set_error("sim_topk: workspace %zu < required %zu", workspace_bytes, required);
     return GDR_ENOSPC;
   }
   char* ws = static_cast<char*>(workspace);
+  const uint32_t* live = masked ? reinterpret_cast<const uint32_t*>(ws) : nullptr;
   SimEpilogue ep{};
   ep.cand_val = reinterpret_cast<float*>(ws + p.off_val);
   ep.cand_idx = reinterpret_cast<int32_t*>(ws + p.off_idx);
@@ -739,6 +835,7 @@ int gdr::sim_topk_impl(const void* Q, int B, const void* D, int64_t N, int d, in
   const bool stream_mode = sim_stream_supported(B, d, bf16) && !(flags & GDR_SIM_NO_STREAM);
   int rc = stream_mode ? launch_sim_stream(D, N, Q, B, d, ep, bf16, stream) : launch_sim_gemm(D, N, Q, B, d, ep, bf16, stream);
   if (rc) return rc;
+  if (masked) GDR_TRY(launch_live_mask(ep, p, B, 0, p.n_slots, live, N, stream));  // the threshold sees live sample scores only
   const int sel_threads = 1024;  // 1024 lanes per query: measured faster than 512 with twice the entries per lane (26.7 vs 37.7 us at 32 queries)
   const int kpad = sel_pow2(k, 1);
   static const bool sliced_on = [] {
@@ -763,9 +860,14 @@ int gdr::sim_topk_impl(const void* Q, int B, const void* D, int64_t N, int d, in
     GDR_CHECK_LAUNCH("sim_threshold_kernel");
   }
   if (p.stride > 1) {
+    if (masked) {  // fewer than k live sample rows: thr[q] = -inf (sim_live_thr_fixup_kernel)
+      hipLaunchKernelGGL(sim_live_thr_fixup_kernel, dim3(1), dim3(256), 0, stream, live, N, p.n_sample_tiles, p.stride, k, thr, B);
+      GDR_CHECK_LAUNCH("sim_live_thr_fixup_kernel");
+    }
     ep.mode = 2;
     rc = stream_mode ? launch_sim_stream(D, N, Q, B, d, ep, bf16, stream) : launch_sim_gemm(D, N, Q, B, d, ep, bf16, stream);
     if (rc) return rc;
+    if (masked) GDR_TRY(launch_live_mask(ep, p, B, p.n_slots, -1, live, N, stream));  // the survivors, dead rows among them
   }
   if (ns_sel) {
     sa.NS = ns_sel;

@@ -274,14 +274,15 @@ class DenseModel:
 
     forward = __call__
 
-    def search(self, q_reps, p_reps, k):
+    def search(self, q_reps, p_reps, k, live=None):
         """compute_similarity + topk(k) fused (never writes the score matrix). Returns (values, int64 indices).
+        live: an ops.LiveRows over the rows of p_reps — rank its live rows only (k <= live.count); ids stay row numbers.
         p_reps: the passage embeddings [N,d] (fp32, or bf16 = the C5 precision mode), or an ops.PrefilteredCorpus built from them once
         (the same fp32 top-k through the bf16 pre-filter, gdr_sim_topk_prefilter).  1 <= k <= min(ops.SIM_TOPK_MAX_K, N); past
         ops.PREFILTER_MAX_K a PrefilteredCorpus is searched on the plain fp32 path (the same list)."""
         if self._ws is None:
             self._ws = ops.Workspace(q_reps.device)
-        v, i = ops.sim_topk(q_reps.contiguous(), p_reps, k, workspace=self._ws, exact_on_overflow=True)
+        v, i = ops.sim_topk(q_reps.contiguous(), p_reps, k, workspace=self._ws, exact_on_overflow=True, live=live)
         return v, i.to(torch.int64)
 
 
@@ -393,6 +394,32 @@ class GDRRetriever:
         # host form (decode_token strings + ClusterIndex.candidates) — same lists, one D2H / H2D round trip more per step
         self.device_candidates = bool(device_candidates)
 
+    @property
+    def live_rows(self):
+        """ops.LiveRows over doc_embed: a row is live iff it is a member of some cluster.  Built on first use from the member CSR
+        and kept current by add_documents / remove_documents / update_documents.  A sharded retriever has none."""
+        if self.sharded is not None:
+            raise _ffi.GdrError("live_rows: a sharded retriever keeps no live-row mask (sharded removal is not supported)")
+        if getattr(self, "_live", None) is None:
+            import numpy as np
+            N = self.doc_embed.shape[0]
+            mem = np.asarray(self.index.members, dtype=np.int64).reshape(-1)
+            live = np.zeros(N, dtype=bool)
+            live[mem[(mem >= 0) & (mem < N)]] = True
+            self._live = ops.LiveRows.from_bool(torch.from_numpy(live).to(self.doc_embed.device))
+        return self._live
+
+    @torch.no_grad()
+    def search(self, q_reps, k):
+        """The dense top-k of q_reps [B, d] over the LIVE documents (DenseModel.search with live_rows): a document withdrawn by
+        remove_documents never comes back, one restored by update_documents does, ids are rows of doc_embed.  Returns (values,
+        int64 ids); k <= the number of live documents.  Raises GdrError for a sharded retriever."""
+        live = self.live_rows
+        if getattr(self, "_search_ws", None) is None:
+            self._search_ws = ops.Workspace(self.doc_embed.device)
+        v, i = ops.sim_topk(q_reps.contiguous(), self.doc_embed, k, workspace=self._search_ws, live=live)
+        return v, i.to(torch.int64)
+
     @torch.no_grad()
     def add_documents(self, embeds=None, tokens=None):
         """Adds n documents to the corpus without retraining the generative model (the GDR paper's scalability claim; the
@@ -442,6 +469,8 @@ class GDRRetriever:
             offs, mem, _mx = ops.cluster_insert(up(self.index.offsets), up(self.index.members), ids, tgt, fc.cmap)
         csr = torch.cat([offs, mem]).cpu().numpy()                                  # one read-back of the merged CSR
         self.index = self.index.with_csr(csr[:C_ + 1], csr[C_ + 1:])
+        if getattr(self, "_live", None) is not None:
+            self._live.grow(N + n).set(ids)
         return np.arange(N, N + n, dtype=np.int64), fc.cmap[tgt.long()].cpu().numpy()
 
     def _document_rows(self, what, embeds, tokens):
@@ -532,7 +561,10 @@ class GDRRetriever:
         self._freeze_centroids()
         if ids.size == 0:
             return 0
-        return self._edit_csr(torch.from_numpy(ids.astype(np.int32)).to(self.doc_embed.device))
+        gone = self._edit_csr(torch.from_numpy(ids.astype(np.int32)).to(self.doc_embed.device))
+        if getattr(self, "_live", None) is not None:
+            self._live.clear(ids)
+        return gone
 
     @torch.no_grad()
     def update_documents(self, ids, embeds=None, tokens=None):
@@ -565,6 +597,8 @@ class GDRRetriever:
             self._overwrite_tokens(rows, tok.index_select(0, sel), msk.index_select(0, sel))
         ids32 = rows.to(torch.int32)
         self._edit_csr(ids32, insert=ids32, targets=tgt)
+        if getattr(self, "_live", None) is not None:
+            self._live.set(rows)
         out = np.empty(ids.size, np.int32)
         out[order] = fc.cmap[tgt.long()].cpu().numpy()
         return out

@@ -158,11 +158,91 @@ SIM_TOPK_MAX_K = 8192            # gdr_sim_topk[_bf16], gdr_topk_merge, gdr_topk
 PREFILTER_MAX_K = 1024           # gdr_sim_topk_prefilter: its one-workgroup tail sorts 4k band keys and rescores them in fp32
 
 
-def _sim_topk_raw(Q, D, k, idx_offset, workspace, flags):
+class LiveRows:
+    """Which rows of a corpus are live, as gdr_sim_topk's GDR_SIM_LIVE_MASK reads it: bit r % 32 of int32 word r // 32 is 1 when
+    row r is live.  The words stay on `device` (any torch device: the packing is torch ops), `count` = the number of live rows is
+    kept on the host.  set / clear change the words on the device and read back ONE number, how many bits flipped; the words
+    themselves are never read back.  New rows (LiveRows(n, device), grow) start dead."""
+
+    def __init__(self, n, device):
+        self.n, self.count = int(n), 0
+        self._words = torch.zeros(max((self.n + 31) // 32, 1), dtype=torch.int32, device=device)
+        self.device = self._words.device
+
+    @property
+    def words(self):
+        """int32 [ceil(n / 32)]: the bitmap (a view of the backing buffer)."""
+        return self._words[:(self.n + 31) // 32]
+
+    @staticmethod
+    def _pack(bits):
+        """bool [32 W] -> int32 [W]; bit 31 enters as -2^31, so every sum is an int32 value"""
+        w = torch.tensor([1 << j for j in range(31)] + [-(1 << 31)], dtype=torch.int64, device=bits.device)
+        return (bits.view(-1, 32).to(torch.int64) * w).sum(1).to(torch.int32)
+
+    @classmethod
+    def from_bool(cls, live):
+        """live: bool [n] (True = live), on the device the bitmap is to stay on."""
+        live = torch.as_tensor(live).to(torch.bool).reshape(-1)
+        out = cls(live.numel(), live.device)
+        if out.n:
+            out._words = cls._pack(torch.nn.functional.pad(live, (0, -out.n % 32)))
+            out.count = int(live.sum().item())
+        return out
+
+    def _flip(self, ids, to):
+        ids = torch.as_tensor(ids).reshape(-1).to(torch.int64)
+        if ids.numel() == 0:
+            return 0
+        if int(ids.min()) < 0 or int(ids.max()) >= self.n:           # where the ids are: no sync for host ids
+            raise _ffi.GdrError(f"LiveRows: row ids must lie in [0, {self.n})")
+        ids = torch.unique(ids.to(self.device))
+        w, b = ids >> 5, ids & 31
+        now = (self._words[w].to(torch.int64) >> b) & 1
+        ch = now != to                                               # distinct bits, all in the other state: adding them is an OR / AND-NOT
+        bit = torch.where(b == 31, torch.full_like(b, -(1 << 31)), torch.ones_like(b) << b).to(torch.int32)
+        self._words.index_add_(0, w[ch], bit[ch] if to else -bit[ch])    # int32 wraps: +-2^31 flips bit 31
+        n = int(ch.sum().item())
+        self.count += n if to else -n
+        return n
+
+    def set(self, ids):
+        """Rows `ids` become live.  Returns how many were dead."""
+        return self._flip(ids, 1)
+
+    def clear(self, ids):
+        """Rows `ids` become dead.  Returns how many were live."""
+        return self._flip(ids, 0)
+
+    def grow(self, n_new):
+        """The corpus now has n_new >= n rows; the new ones are dead until set()."""
+        n_new = int(n_new)
+        if n_new < self.n:
+            raise _ffi.GdrError(f"LiveRows.grow: {n_new} < {self.n} rows")
+        need = (n_new + 31) // 32
+        if need > self._words.numel():
+            buf = torch.zeros(max(need, self._words.numel() * 3 // 2 + 8), dtype=torch.int32, device=self.device)
+            buf[:self._words.numel()].copy_(self._words)
+            self._words = buf
+        self.n = n_new
+        return self
+
+    def to_bool(self):
+        """bool [n] on the device (tests, debugging)."""
+        j = torch.arange(self.n, device=self.device)
+        return ((self._words[j >> 5].to(torch.int64) >> (j & 31)) & 1).to(torch.bool)
+
+
+def _sim_topk_raw(Q, D, k, idx_offset, workspace, flags, live=None):
     B, d = Q.shape
     N = D.shape[0]
+    if live is not None:
+        flags |= _ffi.SIM_LIVE_MASK
     need = lib().gdr_sim_topk_workspace_bytes(B, N, d, k, flags)
     ws = (workspace or Workspace(Q.device)).get(need)
+    if live is not None:                                             # the bitmap is the head of the workspace (stream-ordered copy)
+        words = live.words
+        ws[:words.numel() * 4].view(torch.int32).copy_(words)
     vals = torch.empty((B, k), dtype=torch.float32, device=Q.device)
     idx = torch.empty((B, k), dtype=torch.int32, device=Q.device)
     status = torch.empty((B,), dtype=torch.int32, device=Q.device)
@@ -172,7 +252,7 @@ def _sim_topk_raw(Q, D, k, idx_offset, workspace, flags):
     return vals, idx, status
 
 
-def sim_topk(Q, D, k, idx_offset=0, workspace=None, return_status=False, exact_on_overflow=True, flags=0):
+def sim_topk(Q, D, k, idx_offset=0, workspace=None, return_status=False, exact_on_overflow=True, flags=0, live=None):
     """Fused Q·Dᵀ + per-row top-k — gdr_sim_topk.  Returns (values fp32[B,k], indices int32[B,k]), 1 <= k <= min(SIM_TOPK_MAX_K, N).
     D may be an fp32 or bf16 tensor, or a PrefilteredCorpus: the pre-filter serves k <= PREFILTER_MAX_K, a deeper list is the
     plain fp32 call over its rows (the same answer: both return the top-k of the fp32 scores for every input).
@@ -180,11 +260,14 @@ def sim_topk(Q, D, k, idx_offset=0, workspace=None, return_status=False, exact_o
     exact_on_overflow=True (the default) reads the per-query status back (one host sync per call) and recomputes any
     query whose candidate list overflowed (degenerate corpora with tens of thousands of tied docs) exhaustively, so the
     result is exact for every input.  Latency-critical callers pass exact_on_overflow=False, return_status=True: no sync,
-    and the device status tensor (1 = that row is the top-k of a subset) is theirs to act on.  flags: _ffi.SIM_* bits."""
+    and the device status tensor (1 = that row is the top-k of a subset) is theirs to act on.  flags: _ffi.SIM_* bits.
+    live: a LiveRows over the N rows of D — the top-k over its live rows only (GDR_SIM_LIVE_MASK; k <= live.count): the list the
+    call would return for the matrix of the live rows, with their ids in D.  A PrefilteredCorpus is then searched on the plain fp32
+    path (the pre-filter has no mask; the same answer), and the overflow re-run carries the mask."""
     prefilter = isinstance(D, PrefilteredCorpus)
     if prefilter:
         P, D = D, D.D
-        if (Q.shape[0] < PREFILTER_MIN_BATCH or D.shape[1] % 8 or D.shape[1] > 1024 or (flags & _ffi.SIM_EXHAUSTIVE) or k > PREFILTER_MAX_K
+        if (live is not None or Q.shape[0] < PREFILTER_MIN_BATCH or D.shape[1] % 8 or D.shape[1] > 1024 or (flags & _ffi.SIM_EXHAUSTIVE) or k > PREFILTER_MAX_K
                 or not P.dnorm_max > 0.0):                               # an all-zero corpus has no band: the fp32 path serves it
             prefilter = False
     _need_cuda(Q, D)
@@ -197,10 +280,15 @@ def sim_topk(Q, D, k, idx_offset=0, workspace=None, return_status=False, exact_o
         raise _ffi.GdrError(f"sim_topk: dim mismatch {Q.shape} vs {D.shape}")
     if k > D.shape[0]:
         raise RuntimeError("selected index k out of range")          # torch.topk's message
+    if live is not None:
+        if not isinstance(live, LiveRows) or live.n != D.shape[0] or live.device != D.device:
+            raise _ffi.GdrError(f"sim_topk: live must be an ops.LiveRows over the {D.shape[0]} rows of D, on its device")
+        if k > live.count:
+            raise RuntimeError("selected index k out of range")      # as torch.topk over the live rows would
     if prefilter:
         vals, idx, status = _sim_topk_prefilter_raw(Q, P, k, idx_offset, workspace)
     else:
-        vals, idx, status = _sim_topk_raw(Q, D, k, idx_offset, workspace, flags)
+        vals, idx, status = _sim_topk_raw(Q, D, k, idx_offset, workspace, flags, live)
     if exact_on_overflow:
         bad = torch.nonzero(status).flatten()
         _ffi.check_device_fault("sim_topk")                              # nonzero() synchronised
@@ -208,7 +296,7 @@ def sim_topk(Q, D, k, idx_offset=0, workspace=None, return_status=False, exact_o
             for lo in range(0, bad.numel(), 64):                     # bounded workspace: 64 queries * N * 8 B
                 rows = bad[lo:lo + 64]
                 v2, i2, _ = _sim_topk_raw(Q[rows].contiguous(), D, k, idx_offset, None,
-                                          _ffi.SIM_EXHAUSTIVE | (flags & _ffi.SIM_NO_STREAM))   # the core the caller chose
+                                          _ffi.SIM_EXHAUSTIVE | (flags & _ffi.SIM_NO_STREAM), live)   # the core the caller chose
                 vals[rows], idx[rows] = v2, i2
             status = torch.zeros_like(status)
     return (vals, idx, status) if return_status else (vals, idx)

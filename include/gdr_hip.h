@@ -263,9 +263,22 @@ int gdr_t5_encoder_forward_bf16(const GdrT5EncoderWeights* w, const int64_t* ids
  *   k' <= k (one call's list dips by 1 - 2 % where a larger k lowers the sample stride by one, and shrinks where the whole corpus
  *   becomes the sample), so it never shrinks when k grows: a buffer sized for the deepest k of a caller serves its shallower ones.
  *   gdr_sim_topk_prefilter_workspace_bytes is never below it (plus its bf16 queries and bands).
+ * GDR_SIM_LIVE_MASK (gdr_sim_topk, gdr_sim_topk_bf16): the top-k over the LIVE rows of D only.  The first
+ *   M = align_up(4 * ceil(N / 32), 256) bytes of `workspace` are then an INPUT the caller writes before the call: a bitmap, bit r % 32 of
+ *   int32 word r / 32 set = row r of D is live; bits past N in the last word are ignored.  The library only reads that region, its own
+ *   scratch starts behind it, and gdr_sim_topk_workspace_bytes(.., flags | GDR_SIM_LIVE_MASK) = the unflagged size + M (a smaller
+ *   workspace is GDR_ENOSPC before any launch).  Scores, tie rule, ids (row + idx_offset) and the status contract are those of the
+ *   unflagged call — the list equals the unflagged call over the matrix of the live rows, ids mapped back; with fewer than k live rows
+ *   the tail of a list is -inf / -1.  A dead row's score is still computed: the mask is applied to the candidate lists between the
+ *   passes (three small launches more).  When fewer than k rows of the sampled tiles are live the sample gives no threshold; the
+ *   filter pass then keeps every row and the list either holds the whole corpus (exact) or overflows: status[q] = 1, and the re-run is
+ *   GDR_SIM_EXHAUSTIVE | GDR_SIM_LIVE_MASK.  With the flag clear nothing changes: layout, launches and results are as before.
+ *   gdr_sim_topk_prefilter takes no flags and stays UNMASKED: a masked search over such a corpus is gdr_sim_topk's (the same fp32
+ *   answer by that entry point's own contract).
  * ---------------------------------------------------------------------------------------------- */
 #define GDR_SIM_EXHAUSTIVE 1
 #define GDR_SIM_NO_STREAM 2   /* force the tiled GEMM core even at B <= 32 (A/B testing of the latency-mode kernel) */
+#define GDR_SIM_LIVE_MASK 4   /* workspace starts with a live-row bitmap; rank the live rows only */
 size_t gdr_sim_topk_workspace_bytes(int B, int64_t N, int d, int k, int flags);
 int gdr_sim_topk(const float* Q, int B, const float* D, int64_t N, int d, int k, int32_t idx_offset,
                  float* out_val, int32_t* out_idx, int32_t* status, int flags, void* workspace,
