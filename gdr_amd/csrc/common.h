@@ -98,6 +98,23 @@ struct StreamK {
 constexpr size_t STREAMK_PART_BYTES = (size_t)512 * 128 * 128 * 4;
 constexpr size_t STREAMK_BYTES = STREAMK_PART_BYTES + 4096;
 
+// What a linear's epilogue code (GDR_EPI_* of include/gdr_hip.h) asks of the kernel that applies it.
+enum { ACT_NONE = 0, ACT_RELU = 1, ACT_GELU = 2 };
+struct LinearEpilogue {
+  bool has_bias, has_residual;
+  int act;
+};
+static inline bool decode_epilogue(int epilogue, LinearEpilogue* e) {  // false: not a GDR_EPI_* code
+  if (epilogue < GDR_EPI_NONE || epilogue > GDR_EPI_BIAS_GELU) return false;
+  e->has_bias = epilogue == GDR_EPI_BIAS || epilogue == GDR_EPI_BIAS_RELU || epilogue == GDR_EPI_BIAS_RESIDUAL ||
+                epilogue == GDR_EPI_BIAS_GELU;
+  e->has_residual = epilogue == GDR_EPI_RESIDUAL || epilogue == GDR_EPI_BIAS_RESIDUAL;
+  e->act = (epilogue == GDR_EPI_RELU || epilogue == GDR_EPI_BIAS_RELU) ? ACT_RELU
+           : epilogue == GDR_EPI_BIAS_GELU                             ? ACT_GELU
+                                                                       : ACT_NONE;
+  return true;
+}
+
 int launch_linear_f32(const float* A, int64_t lda, const float* W, int64_t ldw, float* C, int64_t ldc, int64_t M,
                       int N, int K, int epilogue, const float* bias, const float* residual, int64_t ldr,
                       hipStream_t stream);

@@ -944,13 +944,12 @@ extern "C" int gdr_linear_split_bf16(const void* A3, int64_t lda, const void* W3
   GDR_CHECK_ARG(A3 && W3 && C && M >= 0 && N > 0 && K > 0 && (terms == 6 || terms == 3 || terms == 2),
                 "linear_split_bf16: bad arguments (terms: 6 or 3 = bf16 planes, 2 = fp16 x 2)");
   if (M == 0) return GDR_OK;
-  const bool nb = epilogue == GDR_EPI_BIAS || epilogue == GDR_EPI_BIAS_RELU || epilogue == GDR_EPI_BIAS_RESIDUAL || epilogue == GDR_EPI_BIAS_GELU;
-  const bool nr = epilogue == GDR_EPI_RESIDUAL || epilogue == GDR_EPI_BIAS_RESIDUAL;
-  const int act = (epilogue == GDR_EPI_RELU || epilogue == GDR_EPI_BIAS_RELU) ? 1 : epilogue == GDR_EPI_BIAS_GELU ? 2 : 0;
-  GDR_CHECK_ARG((!nb || bias) && (!nr || residual), "linear_split_bf16: the epilogue's bias / residual pointer is null");
+  LinearEpilogue e{};  // a code outside GDR_EPI_* applies nothing
+  decode_epilogue(epilogue, &e);
+  GDR_CHECK_ARG((!e.has_bias || bias) && (!e.has_residual || residual), "linear_split_bf16: the epilogue's bias / residual pointer is null");
   ProfScope prof(PROF_LINEAR, 2.0 * (double)M * (double)N * (double)K, static_cast<hipStream_t>(stream));
-  const int rc = launch_linear_bf16_glds(A3, lda, W3, ldw, C, ldc, M, N, K, nb, nr, act, bias, residual, ldr, 0, static_cast<hipStream_t>(stream),
-                                         nullptr, terms);
+  const int rc = launch_linear_bf16_glds(A3, lda, W3, ldw, C, ldc, M, N, K, e.has_bias, e.has_residual, e.act, bias, residual, ldr, 0,
+                                         static_cast<hipStream_t>(stream), nullptr, terms);
   if (rc > 0) {
     set_error("linear_split_bf16: shape not served (K %% 64 == 0, lda / ldw >= 3 K and multiples of 8, 16-byte aligned operands)");
     return GDR_EINVAL;

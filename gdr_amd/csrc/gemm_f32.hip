@@ -16,6 +16,17 @@
 //     so the sum over k is unchanged.
 //   * 1-D grid with the bijective XCD remap: the blocks that share a row panel (A tile) run on one XCD
 //     back to back, so the panel is fetched from HBM once and re-read from that XCD's L2.
+//
+// Layout of the file
+//   * device pieces that exist once and serve all three kernels: xcd_remap, supertile_mn, the staging registers and their
+//     LDS store (Staged, lds_store_staged), the fragment read and its MFMA group (Frag, lds_read_frag, mfma_frag), the
+//     scheduled fp32 K-step (kstep_f32) and the linear tile epilogue (GDR_LINEAR_TILE_EPILOGUE);
+//   * gemm_nt_f32_kernel (one tile per workgroup: linears, split-K slabs, bf16 operands, the similarity epilogues),
+//     gemm_nt_f32_persistent_kernel (a workgroup walks whole tiles) and gemm_nt_f32_streamk_kernel (tiles or split-K units
+//     dealt by K-step ranges) — the last two differ on purpose: 64-bit against 32-bit operand offsets, a tile counter
+//     against a segment walker;
+//   * host side: linear_f32_route decides the form of every fp32 linear, build_linear_args validates a call and fills the
+//     kernel arguments, launch_streamk / launch_whole_k launch; the four launchers and the C entry points are thin.
 #include <stdlib.h>
 
 #include "common.h"
@@ -23,6 +34,7 @@
 namespace gdr {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 
 constexpr int BM = 128, BN = 128, BK = 32;
@@ -66,9 +78,230 @@ __device__ __forceinline__ int64_t live_rows_padded(const GemmArgs& g) {
 
 
 enum { EPI_LINEAR = 0, EPI_SIM_SAMPLE = 100, EPI_SIM_FILTER = 101 };
-enum { ACT_NONE = 0, ACT_RELU = 1, ACT_GELU = 2 };
 
 __device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
+
+// ---- pieces shared by the three kernels below: each exists once ---------------------------------------------------
+
+// hardware block -> logical block, XCD-aware and bijective for any block count: XCD x (blocks x, x+8, ...) gets a
+// contiguous logical range
+__device__ __forceinline__ unsigned xcd_remap(unsigned bid, unsigned nblk) {
+  const unsigned q = nblk >> 3, r = nblk & 7u, xcd = bid & 7u, j = bid >> 3;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
+}
+
+// tile index -> (row panel, column tile): supertiles of GM row panels x all column tiles, row-panel-fastest inside, so
+// that the 64 tiles an XCD works on at a time are ~8 row panels x 8 column tiles (16 operand panels through its L2)
+// instead of a few row panels x every column tile (N=3072: 27 panels).  GM travels in g.ksplit (unused by the kernels
+// that deal tiles this way).
+__device__ __forceinline__ void supertile_mn(const GemmArgs& g, int tiles_m, int tile, int& mt, int& nt) {
+  const int per = g.ksplit * g.tiles_n;
+  const int grp = tile / per, loc = tile - grp * per;
+  const int gm = min(g.ksplit, tiles_m - grp * g.ksplit);
+  nt = loc / gm;
+  mt = grp * g.ksplit + (loc - nt * gm);
+}
+
+// One K-step of a thread's share of the operands on its way global -> LDS: four 16-byte pieces of A rows and four of W rows.
+struct Staged {
+  f32x4 a0, a1, a2, a3, b0, b1, b2, b3;
+};
+__device__ __forceinline__ void lds_store_staged(float* As, float* Bs, int buf, int st_off, const Staged& s) {
+  float* a_ = As + buf * BM * LDS_STRIDE + st_off;
+  float* b_ = Bs + buf * BN * LDS_STRIDE + st_off;
+  *reinterpret_cast<f32x4*>(a_) = s.a0;
+  *reinterpret_cast<f32x4*>(a_ + 32 * LDS_STRIDE) = s.a1;
+  *reinterpret_cast<f32x4*>(a_ + 64 * LDS_STRIDE) = s.a2;
+  *reinterpret_cast<f32x4*>(a_ + 96 * LDS_STRIDE) = s.a3;
+  *reinterpret_cast<f32x4*>(b_) = s.b0;
+  *reinterpret_cast<f32x4*>(b_ + 32 * LDS_STRIDE) = s.b1;
+  *reinterpret_cast<f32x4*>(b_ + 64 * LDS_STRIDE) = s.b2;
+  *reinterpret_cast<f32x4*>(b_ + 96 * LDS_STRIDE) = s.b3;
+}
+
+// The fragments of K-chunk jj (8 floats of k) of a wave's 64x64 patch: two 32-row A tiles and two 32-column W tiles.
+struct Frag {
+  float4 a0, a1, b0, b1;
+};
+__device__ __forceinline__ Frag lds_read_frag(const float* ap, const float* bp, int jj) {
+  Frag f;
+  f.a0 = *reinterpret_cast<const float4*>(ap + 8 * jj);
+  f.a1 = *reinterpret_cast<const float4*>(ap + 32 * LDS_STRIDE + 8 * jj);
+  f.b0 = *reinterpret_cast<const float4*>(bp + 8 * jj);
+  f.b1 = *reinterpret_cast<const float4*>(bp + 32 * LDS_STRIDE + 8 * jj);
+  return f;
+}
+
+// The MFMAs of one fragment on the 2x2 accumulator tiles: 16 of v_mfma_f32_32x32x2_f32 (k pairs x, y, z, w in that order), or 4
+// of v_mfma_f32_32x32x16_bf16 on the same 16 bytes read as 8 bf16.
+#define GDR_MFMA4(f_, x_)                                                                 \
+  acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(f_.a0.x_, f_.b0.x_, acc[0][0], 0, 0, 0); \
+  acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(f_.a0.x_, f_.b1.x_, acc[0][1], 0, 0, 0); \
+  acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(f_.a1.x_, f_.b0.x_, acc[1][0], 0, 0, 0); \
+  acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(f_.a1.x_, f_.b1.x_, acc[1][1], 0, 0, 0);
+#define GDR_MFMA_BF(A, B, C) \
+  C = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, A), __builtin_bit_cast(bf16x8_t, B), C, 0, 0, 0);
+template <bool BF16 = false>
+__device__ __forceinline__ void mfma_frag(f32x16 (&acc)[2][2], const Frag& f) {
+  if constexpr (BF16) {
+    GDR_MFMA_BF(f.a0, f.b0, acc[0][0]) GDR_MFMA_BF(f.a0, f.b1, acc[0][1]) GDR_MFMA_BF(f.a1, f.b0, acc[1][0])
+    GDR_MFMA_BF(f.a1, f.b1, acc[1][1])
+  } else {
+    GDR_MFMA4(f, x) GDR_MFMA4(f, y) GDR_MFMA4(f, z) GDR_MFMA4(f, w)
+  }
+}
+#undef GDR_MFMA4
+#undef GDR_MFMA_BF
+
+// The scheduled fp32 K-step: the MFMAs of the tile in LDS buffer `buf` while the staged tile goes to the other buffer and
+// `gload` refills the staging registers with the tile after it.  Branch-free so that it is ONE scheduling region: the 8
+// ds_write, 8 late ds_read and 8 global_load are each slotted behind one MFMA (64 issue cycles) instead of sitting in front
+// of / behind the MFMA stream with the matrix pipe idle.  Lab numbers (tools/gemm_lab.hip, MI355X): 118 -> 129..137 TFLOP/s
+// on the encoder shapes, bit-identical output (same k order).  The caller's __syncthreads() follows directly: the compiler
+// hoists it above the trailing 40 MFMAs, which then cover the wait.
+template <class GLoad>
+__device__ __forceinline__ void kstep_f32(float* As, float* Bs, int buf, int a_rd, int b_rd, int st_off, const Staged& st,
+                                          f32x16 (&acc)[2][2], GLoad&& gload) {
+  const float* a = As + buf * BM * LDS_STRIDE + a_rd;
+  const float* b = Bs + buf * BN * LDS_STRIDE + b_rd;
+  const Frag c0 = lds_read_frag(a, b, 0);
+  const Frag c1 = lds_read_frag(a, b, 1);
+  lds_store_staged(As, Bs, buf ^ 1, st_off, st);
+  mfma_frag(acc, c0);
+  const Frag c2 = lds_read_frag(a, b, 2);
+  const Frag c3 = lds_read_frag(a, b, 3);
+  gload();
+  mfma_frag(acc, c1);
+  mfma_frag(acc, c2);
+  mfma_frag(acc, c3);
+  __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);  // ds_read: chunks 0,1
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // MFMA
+    __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);  // ds_write
+  }
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);  // ds_read: chunks 2,3
+  }
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+    __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);  // global_load
+  }
+  __builtin_amdgcn_sched_group_barrier(0x008, 40, 0);
+}
+
+// Operand offsets (elements from g.A / g.W) of a thread's staging loads for tile (mt, nt), K offset k0: rows past the edge
+// are clamped (computed and discarded).  Off is int64_t in the persistent kernel and int in the stream-K kernel.  Kept as
+// integers: pointers that pass through the tile-crossing select lose their address space and the loads degrade to
+// flat_load (vmcnt AND lgkmcnt).
+template <class Off>
+__device__ __forceinline__ void staging_offsets(const GemmArgs& g, int64_t Mrows, int mt, int nt, int lrow, int lcol, int k0,
+                                                Off (&a_ld)[4], Off (&w_ld)[4]) {
+#pragma unroll
+  for (int p = 0; p < 4; ++p) {
+    int64_t ra = (int64_t)mt * BM + lrow + 32 * p;
+    ra = ra < Mrows ? ra : Mrows - 1;
+    int rw = nt * BN + lrow + 32 * p;
+    rw = rw < g.N ? rw : g.N - 1;
+    a_ld[p] = (Off)(ra * g.lda + lcol + k0);
+    w_ld[p] = (Off)((int64_t)rw * g.ldw + lcol + k0);
+  }
+}
+template <class Off>
+__device__ __forceinline__ void gload_staged(const GemmArgs& g, const Off (&a_ld)[4], const Off (&w_ld)[4], Staged& s) {
+  s.a0 = *reinterpret_cast<const f32x4*>(g.A + a_ld[0]);
+  s.a1 = *reinterpret_cast<const f32x4*>(g.A + a_ld[1]);
+  s.a2 = *reinterpret_cast<const f32x4*>(g.A + a_ld[2]);
+  s.a3 = *reinterpret_cast<const f32x4*>(g.A + a_ld[3]);
+  s.b0 = *reinterpret_cast<const f32x4*>(g.W + w_ld[0]);
+  s.b1 = *reinterpret_cast<const f32x4*>(g.W + w_ld[1]);
+  s.b2 = *reinterpret_cast<const f32x4*>(g.W + w_ld[2]);
+  s.b3 = *reinterpret_cast<const f32x4*>(g.W + w_ld[3]);
+}
+
+// Epilogue of a finished 128x128 linear tile at (m0_, n0_) in the persistent and stream-K kernels: stores only (plus the
+// residual / bias loads), no LDS — the other waves are already in the next tile's first K-step.  Leaves the accumulators
+// zeroed for the next tile.  Accumulator map (32x32 MFMA): col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5).
+//   * interior tile: uniform branches only, so that the 64 residual loads go out as one batch and the 64 stores as
+//     another (per-element flag tests serialise them behind a vmcnt(0) each); one column tile (32 accumulators) at a
+//     time, which bounds the registers in flight.
+//   * edge tile (the last, partial row panel of a packed batch; a column tail): the same batched structure — rows and
+//     columns past the matrix are CLAMPED for the loads (legal addresses, one batch) and masked for the stores.  With a
+//     per-element `continue` every residual load sat behind its own vmcnt(0) and the 6..24 edge tiles of a launch finished
+//     after everyone else: 12 350 live rows (62 in the last panel) 17.2 -> 16.05 ms of linears per encoder pass
+//     (tools/exp_edge.py; 12 416 rows = 97 full panels: 15.8 ms).
+// A macro over the kernel's g, Mrows, wm, wn, l31, h and acc, not a function: both kernels sit at the 256-VGPR cap of
+// __launch_bounds__(256, 2), and the function form (accumulators by reference) moved their spills — 2 -> 4 VGPRs in the
+// persistent kernel — while this text compiles to the instructions it compiled to inside each kernel.
+#define GDR_LINEAR_TILE_EPILOGUE(m0_, n0_)                                                                                            \
+  {                                                                                                                                   \
+    const int64_t m0 = (m0_);                                                                                                         \
+    const int n0 = (n0_);                                                                                                             \
+    if (m0 + BM <= Mrows && n0 + BN <= g.N) {                                                                                         \
+      const int64_t mrow = m0 + wm * 64 + 4 * h;                                                                                      \
+      _Pragma("unroll") for (int ni = 0; ni < 2; ++ni) {                                                                              \
+        const int ncol = n0 + wn * 64 + ni * 32 + l31;                                                                                \
+        if (g.has_bias) {                                                                                                             \
+          const float bia = g.bias[ncol];                                                                                             \
+          _Pragma("unroll") for (int mi = 0; mi < 2; ++mi)                                                                            \
+            _Pragma("unroll") for (int r = 0; r < 16; ++r) acc[mi][ni][r] += bia;                                                     \
+        }                                                                                                                             \
+        if (g.has_residual) {                                                                                                         \
+          const float* rp = g.residual + mrow * g.ldr + ncol;                                                                         \
+          _Pragma("unroll") for (int mi = 0; mi < 2; ++mi)                                                                            \
+            _Pragma("unroll") for (int r = 0; r < 16; ++r) acc[mi][ni][r] += rp[(int64_t)(mi * 32 + (r & 3) + 8 * (r >> 2)) * g.ldr]; \
+        }                                                                                                                             \
+        if (g.act == ACT_RELU) {                                                                                                      \
+          _Pragma("unroll") for (int mi = 0; mi < 2; ++mi)                                                                            \
+            _Pragma("unroll") for (int r = 0; r < 16; ++r) acc[mi][ni][r] = fmaxf(acc[mi][ni][r], 0.f);                               \
+        } else if (g.act == ACT_GELU) {                                                                                               \
+          _Pragma("unroll") for (int mi = 0; mi < 2; ++mi)                                                                            \
+            _Pragma("unroll") for (int r = 0; r < 16; ++r) acc[mi][ni][r] = gelu_erf(acc[mi][ni][r]);                                 \
+        }                                                                                                                             \
+        float* cp = g.C + mrow * g.ldc + ncol;                                                                                        \
+        _Pragma("unroll") for (int mi = 0; mi < 2; ++mi)                                                                              \
+          _Pragma("unroll") for (int r = 0; r < 16; ++r) {                                                                            \
+            cp[(int64_t)(mi * 32 + (r & 3) + 8 * (r >> 2)) * g.ldc] = acc[mi][ni][r];                                                 \
+            acc[mi][ni][r] = 0.f;                                                                                                     \
+          }                                                                                                                           \
+      }                                                                                                                               \
+    } else {                                                                                                                          \
+      const int64_t mrow = m0 + wm * 64 + 4 * h;                                                                                      \
+      _Pragma("unroll") for (int ni = 0; ni < 2; ++ni) {                                                                              \
+        const int n = n0 + wn * 64 + ni * 32 + l31;                                                                                   \
+        const bool n_ok = n < g.N;                                                                                                    \
+        const int nc = n_ok ? n : g.N - 1;                                                                                            \
+        if (g.has_bias) {                                                                                                             \
+          const float bia = g.bias[nc];                                                                                               \
+          _Pragma("unroll") for (int mi = 0; mi < 2; ++mi)                                                                            \
+            _Pragma("unroll") for (int r = 0; r < 16; ++r) acc[mi][ni][r] += bia;                                                     \
+        }                                                                                                                             \
+        if (g.has_residual) {                                                                                                         \
+          _Pragma("unroll") for (int mi = 0; mi < 2; ++mi)                                                                            \
+            _Pragma("unroll") for (int r = 0; r < 16; ++r) {                                                                          \
+              const int64_t m = mrow + mi * 32 + (r & 3) + 8 * (r >> 2);                                                              \
+              acc[mi][ni][r] += g.residual[(m < Mrows ? m : Mrows - 1) * g.ldr + nc];                                                 \
+            }                                                                                                                         \
+        }                                                                                                                             \
+        if (g.act == ACT_RELU) {                                                                                                      \
+          _Pragma("unroll") for (int mi = 0; mi < 2; ++mi)                                                                            \
+            _Pragma("unroll") for (int r = 0; r < 16; ++r) acc[mi][ni][r] = fmaxf(acc[mi][ni][r], 0.f);                               \
+        } else if (g.act == ACT_GELU) {                                                                                               \
+          _Pragma("unroll") for (int mi = 0; mi < 2; ++mi)                                                                            \
+            _Pragma("unroll") for (int r = 0; r < 16; ++r) acc[mi][ni][r] = gelu_erf(acc[mi][ni][r]);                                 \
+        }                                                                                                                             \
+        _Pragma("unroll") for (int mi = 0; mi < 2; ++mi)                                                                              \
+          _Pragma("unroll") for (int r = 0; r < 16; ++r) {                                                                            \
+            const int64_t m = mrow + mi * 32 + (r & 3) + 8 * (r >> 2);                                                                \
+            if (n_ok && m < Mrows) g.C[m * g.ldc + n] = acc[mi][ni][r];                                                               \
+            acc[mi][ni][r] = 0.f;                                                                                                     \
+          }                                                                                                                           \
+      }                                                                                                                               \
+    }                                                                                                                                 \
+  }
 
 // BF16 = false: fp32 operands on v_mfma_f32_32x32x2_f32.  BF16 = true: bf16 operands (fp32 accumulate) on
 // v_mfma_f32_32x32x16_bf16.  A K-step is 128 BYTES of every row either way (32 floats / 64 bf16), so staging, LDS
@@ -97,8 +330,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_nt_f32_kernel(const Gemm
         nblk = (unsigned)live;
       }
     }
-    const unsigned q = nblk >> 3, r = nblk & 7u, xcd = bid & 7u, j = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
+    bid = xcd_remap(bid, nblk);
   }
   int split = 0;
   if (EPI == EPI_LINEAR && g.ksplit > 1) {  // splits of one tile are neighbours in the grid
@@ -159,7 +391,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_nt_f32_kernel(const Gemm
   // K tail (K % 32 != 0, K % 4 == 0): loads past K re-read the row's last float4 (a valid address) and the
   // VALUE is zeroed — never select between addresses, that demotes the loads to flat + scratch.
   const bool ktail = (klen % BKE) != 0;
-  float4 ra0, ra1, ra2, ra3, rb0, rb1, rb2, rb3;
+  Staged st;
 
 #define GDR_GLOAD(kt_)                                                                    \
   do {                                                                                    \
@@ -169,84 +401,49 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_nt_f32_kernel(const Gemm
       ok = (kt_)*BKE + lcole < klen;                                                      \
       koff = ok ? koff : (klen - 16 / ES - lcole) * ES;                                   \
     }                                                                                     \
-    ra0 = *reinterpret_cast<const float4*>(a_src[0] + koff);                              \
-    ra1 = *reinterpret_cast<const float4*>(a_src[1] + koff);                              \
-    ra2 = *reinterpret_cast<const float4*>(a_src[2] + koff);                              \
-    ra3 = *reinterpret_cast<const float4*>(a_src[3] + koff);                              \
-    rb0 = *reinterpret_cast<const float4*>(w_src[0] + koff);                              \
-    rb1 = *reinterpret_cast<const float4*>(w_src[1] + koff);                              \
-    rb2 = *reinterpret_cast<const float4*>(w_src[2] + koff);                              \
-    rb3 = *reinterpret_cast<const float4*>(w_src[3] + koff);                              \
+    st.a0 = *reinterpret_cast<const f32x4*>(a_src[0] + koff);                            \
+    st.a1 = *reinterpret_cast<const f32x4*>(a_src[1] + koff);                            \
+    st.a2 = *reinterpret_cast<const f32x4*>(a_src[2] + koff);                            \
+    st.a3 = *reinterpret_cast<const f32x4*>(a_src[3] + koff);                            \
+    st.b0 = *reinterpret_cast<const f32x4*>(w_src[0] + koff);                            \
+    st.b1 = *reinterpret_cast<const f32x4*>(w_src[1] + koff);                            \
+    st.b2 = *reinterpret_cast<const f32x4*>(w_src[2] + koff);                            \
+    st.b3 = *reinterpret_cast<const f32x4*>(w_src[3] + koff);                            \
     if (ktail && !ok) {                                                                   \
-      ra0 = ra1 = ra2 = ra3 = make_float4(0.f, 0.f, 0.f, 0.f);                            \
-      rb0 = rb1 = rb2 = rb3 = make_float4(0.f, 0.f, 0.f, 0.f);                            \
+      st.a0 = st.a1 = st.a2 = st.a3 = f32x4{0.f, 0.f, 0.f, 0.f};                    \
+      st.b0 = st.b1 = st.b2 = st.b3 = f32x4{0.f, 0.f, 0.f, 0.f};                    \
     }                                                                                     \
   } while (0)
 
-#define GDR_LSTORE(buf_)                                                                  \
-  do {                                                                                    \
-    float* a_ = As + (buf_)*BM * LDS_STRIDE + st_off;                                     \
-    float* b_ = Bs + (buf_)*BN * LDS_STRIDE + st_off;                                     \
-    *reinterpret_cast<float4*>(a_) = ra0;                                                 \
-    *reinterpret_cast<float4*>(a_ + 32 * LDS_STRIDE) = ra1;                               \
-    *reinterpret_cast<float4*>(a_ + 64 * LDS_STRIDE) = ra2;                               \
-    *reinterpret_cast<float4*>(a_ + 96 * LDS_STRIDE) = ra3;                               \
-    *reinterpret_cast<float4*>(b_) = rb0;                                                 \
-    *reinterpret_cast<float4*>(b_ + 32 * LDS_STRIDE) = rb1;                               \
-    *reinterpret_cast<float4*>(b_ + 64 * LDS_STRIDE) = rb2;                               \
-    *reinterpret_cast<float4*>(b_ + 96 * LDS_STRIDE) = rb3;                               \
-  } while (0)
-
   GDR_GLOAD(0);
-  GDR_LSTORE(0);
+  lds_store_staged(As, Bs, 0, st_off, st);
   __syncthreads();
 
-#define GDR_READ(A0, A1, B0, B1, ap, bp, jj)                                         \
-  A0 = *reinterpret_cast<const float4*>((ap) + 8 * (jj));                             \
-  A1 = *reinterpret_cast<const float4*>((ap) + 32 * LDS_STRIDE + 8 * (jj));           \
-  B0 = *reinterpret_cast<const float4*>((bp) + 8 * (jj));                             \
-  B1 = *reinterpret_cast<const float4*>((bp) + 32 * LDS_STRIDE + 8 * (jj));
-#define GDR_MFMA4(A0, A1, B0, B1, x_)                                                 \
-  acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(A0.x_, B0.x_, acc[0][0], 0, 0, 0); \
-  acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(A0.x_, B1.x_, acc[0][1], 0, 0, 0); \
-  acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(A1.x_, B0.x_, acc[1][0], 0, 0, 0); \
-  acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(A1.x_, B1.x_, acc[1][1], 0, 0, 0);
-#define GDR_MFMA_BF(A, B, C) \
-  C = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, A), __builtin_bit_cast(bf16x8_t, B), C, 0, 0, 0);
-#define GDR_MFMA16(A0, A1, B0, B1)                                                                                   \
-  if constexpr (BF16) {                                                                                              \
-    GDR_MFMA_BF(A0, B0, acc[0][0]) GDR_MFMA_BF(A0, B1, acc[0][1]) GDR_MFMA_BF(A1, B0, acc[1][0])                     \
-    GDR_MFMA_BF(A1, B1, acc[1][1])                                                                                   \
-  } else {                                                                                                           \
-    GDR_MFMA4(A0, A1, B0, B1, x) GDR_MFMA4(A0, A1, B0, B1, y) GDR_MFMA4(A0, A1, B0, B1, z) GDR_MFMA4(A0, A1, B0, B1, w) \
-  }
-
   if (!ktail) {
-    // Steady-state loop (K % 32 == 0), branch-free so that it is ONE scheduling region: the staging registers run
-    // one tile ahead (tile kt+1 is written to LDS while tile kt+2 is being fetched), and the 8 ds_write, 8 late
-    // ds_read and 8 global_load of a K-step are each slotted behind one MFMA (64 issue cycles) instead of sitting
-    // in front of / behind the MFMA stream with the matrix pipe idle.  Lab numbers (tools/gemm_lab.hip, MI355X):
-    // 118 -> 129..137 TFLOP/s on the encoder shapes, bit-identical output (same k order).
-    // The last two iterations re-fetch / re-store the last tile: in-bounds, never read.
+    // Steady-state loop (K % 32 == 0) of scheduled K-steps (kstep_f32): the staging registers run one tile ahead (tile
+    // kt+1 is written to LDS while tile kt+2 is being fetched).  The last two iterations re-fetch / re-store the last
+    // tile: in-bounds, never read.
     GDR_GLOAD(nk > 1 ? 1 : 0);
     for (int kt = 0; kt < nk; ++kt) {
       const int buf = kt & 1;
-      const float* a = As + buf * BM * LDS_STRIDE + a_rd;
-      const float* b = Bs + buf * BN * LDS_STRIDE + b_rd;
-      float4 c0a0, c0a1, c0b0, c0b1, c1a0, c1a1, c1b0, c1b1, c2a0, c2a1, c2b0, c2b1, c3a0, c3a1, c3b0, c3b1;
-      GDR_READ(c0a0, c0a1, c0b0, c0b1, a, b, 0)
-      GDR_READ(c1a0, c1a1, c1b0, c1b1, a, b, 1)
-      GDR_LSTORE(buf ^ 1);
       const int nxt = kt + 2 < nk ? kt + 2 : nk - 1;
-      GDR_MFMA16(c0a0, c0a1, c0b0, c0b1)
-      GDR_READ(c2a0, c2a1, c2b0, c2b1, a, b, 2)
-      GDR_READ(c3a0, c3a1, c3b0, c3b1, a, b, 3)
-      GDR_GLOAD(nxt);
-      GDR_MFMA16(c1a0, c1a1, c1b0, c1b1)
-      GDR_MFMA16(c2a0, c2a1, c2b0, c2b1)
-      GDR_MFMA16(c3a0, c3a1, c3b0, c3b1)
-      __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);  // ds_read: chunks 0,1
-      if constexpr (BF16) {  // 16 MFMAs of 32 cycles per K-step: two memory instructions behind each of the first 12
+      auto gload_next = [&] { GDR_GLOAD(nxt); };
+      if constexpr (!BF16) {
+        kstep_f32(As, Bs, buf, a_rd, b_rd, st_off, st, acc, gload_next);
+      } else {  // the same K-step with 16 MFMAs of 32 cycles: two memory instructions behind each of the first 12
+        const float* a = As + buf * BM * LDS_STRIDE + a_rd;
+        const float* b = Bs + buf * BN * LDS_STRIDE + b_rd;
+        const Frag c0 = lds_read_frag(a, b, 0);
+        const Frag c1 = lds_read_frag(a, b, 1);
+        lds_store_staged(As, Bs, buf ^ 1, st_off, st);
+        mfma_frag<true>(acc, c0);
+        const Frag c2 = lds_read_frag(a, b, 2);
+        const Frag c3 = lds_read_frag(a, b, 3);
+        gload_next();
+        mfma_frag<true>(acc, c1);
+        mfma_frag<true>(acc, c2);
+        mfma_frag<true>(acc, c3);
+        __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);  // ds_read: chunks 0,1
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
@@ -263,23 +460,6 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_nt_f32_kernel(const Gemm
           __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);
         }
         __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
-      } else {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // MFMA
-          __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);  // ds_write
-        }
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-          __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);  // ds_read: chunks 2,3
-        }
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-          __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);  // global_load
-        }
-        __builtin_amdgcn_sched_group_barrier(0x008, 40, 0);
       }
       __syncthreads();
     }
@@ -291,20 +471,12 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_nt_f32_kernel(const Gemm
       const float* a = As + buf * BM * LDS_STRIDE + a_rd;
       const float* b = Bs + buf * BN * LDS_STRIDE + b_rd;
 #pragma unroll
-      for (int jj = 0; jj < 4; ++jj) {
-        float4 a0, a1, b0, b1;
-        GDR_READ(a0, a1, b0, b1, a, b, jj)
-        GDR_MFMA16(a0, a1, b0, b1)
-      }
-      if (more) GDR_LSTORE(buf ^ 1);
+      for (int jj = 0; jj < 4; ++jj) mfma_frag<BF16>(acc, lds_read_frag(a, b, jj));
+      if (more) lds_store_staged(As, Bs, buf ^ 1, st_off, st);
       __syncthreads();
     }
   }
-#undef GDR_READ
-#undef GDR_MFMA4
-#undef GDR_MFMA16
 #undef GDR_GLOAD
-#undef GDR_LSTORE
 
   // ---- epilogue.  Accumulator map (32x32 MFMA): col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5) ----
   if (EPI == EPI_SIM_SAMPLE || EPI == EPI_SIM_FILTER) {
@@ -417,11 +589,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_nt_f32_persistent_kernel
   __shared__ __attribute__((aligned(16))) float smem[2 * BM * LDS_STRIDE + 2 * BN * LDS_STRIDE];
   float* const As = smem;
   float* const Bs = smem + 2 * BM * LDS_STRIDE;
-  unsigned bid = blockIdx.x;
-  {
-    const unsigned nblk = gridDim.x, q = nblk >> 3, r = nblk & 7u, xcd = bid & 7u, j = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-  }
+  const unsigned bid = xcd_remap(blockIdx.x, gridDim.x);
   const int G = (int)gridDim.x;
   const int tid = threadIdx.x;
   const int lrow = tid >> 3;
@@ -436,93 +604,37 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_nt_f32_persistent_kernel
   const int64_t Mrows = live_rows_padded(g);  // ragged batches: a device-side value <= g.M, in whole row panels
   const int tiles_m = (int)((Mrows + BM - 1) / BM);
   const int total_tiles = g.m_dev ? tiles_m * g.tiles_n : total_tiles_host;
-  constexpr int S = 1;  // whole tiles only (the stream-K kernel's macros of the same name also serve (tile, chunk) units)
   // a device-side row count of 0 (prefix-table decode when every beam hits the table): no tile exists to park the load
-  // stream on — the prologue below would divide by gm_ = 0 and clamp rows to -1.  Uniform exit before anything is loaded.
+  // stream on — the prologue below would divide by a supertile height of 0 and clamp rows to -1.  Uniform exit before
+  // anything is loaded.
   if (total_tiles <= 0) return;
 
-  int64_t a_ld[4];  // element offsets from g.A / g.W — kept as integers: pointers that pass through the tile-crossing
-  int64_t w_ld[4];  // select lose their address space and the loads degrade to flat_load (vmcnt AND lgkmcnt)
-// tile index -> (row panel, column tile): supertiles of GM row panels x all column tiles, row-panel-fastest inside, so
-// that the 64 tiles an XCD works on at a time are ~8 row panels x 8 column tiles (16 operand panels through its L2)
-// instead of a few row panels x every column tile (N=3072: 27 panels).  GM travels in g.ksplit (unused by this kernel).
-#define P_TILE_MN(item_, mt_, nt_)                                           \
-  {                                                                          \
-    const int tile_ = S > 1 ? (item_) / S : (item_);                         \
-    const int per_ = g.ksplit * g.tiles_n;                                   \
-    const int grp_ = (tile_) / per_, loc_ = (tile_) - grp_ * per_;           \
-    const int gm_ = min(g.ksplit, tiles_m - grp_ * g.ksplit);                \
-    nt_ = loc_ / gm_;                                                        \
-    mt_ = grp_ * g.ksplit + (loc_ - nt_ * gm_);                              \
-  }
-#define P_SETPTRS(tile_)                                                     \
-  {                                                                          \
-    int mt_, nt_;                                                            \
-    P_TILE_MN(tile_, mt_, nt_)                                               \
-    _Pragma("unroll") for (int p = 0; p < 4; ++p) {                          \
-      int64_t ra_ = (int64_t)mt_ * BM + lrow + 32 * p;                       \
-      ra_ = ra_ < Mrows ? ra_ : Mrows - 1;                                   \
-      int rw_ = nt_ * BN + lrow + 32 * p;                                    \
-      rw_ = rw_ < g.N ? rw_ : g.N - 1;                                       \
-      a_ld[p] = ra_ * g.lda + lcol;                                          \
-      w_ld[p] = (int64_t)rw_ * g.ldw + lcol;                                 \
-    }                                                                        \
-  }
-  float4 ra0, ra1, ra2, ra3, rb0, rb1, rb2, rb3;
-#define P_GLOAD                                          \
-  ra0 = *reinterpret_cast<const float4*>(g.A + a_ld[0]); \
-  ra1 = *reinterpret_cast<const float4*>(g.A + a_ld[1]); \
-  ra2 = *reinterpret_cast<const float4*>(g.A + a_ld[2]); \
-  ra3 = *reinterpret_cast<const float4*>(g.A + a_ld[3]); \
-  rb0 = *reinterpret_cast<const float4*>(g.W + w_ld[0]); \
-  rb1 = *reinterpret_cast<const float4*>(g.W + w_ld[1]); \
-  rb2 = *reinterpret_cast<const float4*>(g.W + w_ld[2]); \
-  rb3 = *reinterpret_cast<const float4*>(g.W + w_ld[3]);
+  int64_t a_ld[4], w_ld[4];  // element offsets from g.A / g.W (staging_offsets)
+  auto set_tile = [&](int tile_) {
+    int mt_, nt_;
+    supertile_mn(g, tiles_m, tile_, mt_, nt_);
+    staging_offsets(g, Mrows, mt_, nt_, lrow, lcol, 0, a_ld, w_ld);
+  };
+  Staged st;
 #define P_ADVANCE                                                            \
   if (++ld_kt == nk) { /* the load stream crosses into the workgroup's next tile (or parks on its first) */ \
     ld_kt = 0;                                                               \
     ld_tile += G;                                                            \
-    const int t_ = ld_tile < total_tiles ? ld_tile : park;                   \
-    P_SETPTRS(t_)                                                            \
+    set_tile(ld_tile < total_tiles ? ld_tile : park);                        \
   } else {                                                                   \
     _Pragma("unroll") for (int p = 0; p < 4; ++p) a_ld[p] += BK, w_ld[p] += BK; \
   }
-#define P_LSTORE(buf_)                                                       \
-  {                                                                          \
-    float* a_ = As + (buf_)*BM * LDS_STRIDE + st_off;                        \
-    float* b_ = Bs + (buf_)*BN * LDS_STRIDE + st_off;                        \
-    *reinterpret_cast<float4*>(a_) = ra0;                                    \
-    *reinterpret_cast<float4*>(a_ + 32 * LDS_STRIDE) = ra1;                  \
-    *reinterpret_cast<float4*>(a_ + 64 * LDS_STRIDE) = ra2;                  \
-    *reinterpret_cast<float4*>(a_ + 96 * LDS_STRIDE) = ra3;                  \
-    *reinterpret_cast<float4*>(b_) = rb0;                                    \
-    *reinterpret_cast<float4*>(b_ + 32 * LDS_STRIDE) = rb1;                  \
-    *reinterpret_cast<float4*>(b_ + 64 * LDS_STRIDE) = rb2;                  \
-    *reinterpret_cast<float4*>(b_ + 96 * LDS_STRIDE) = rb3;                  \
-  }
-#define P_READ(A0, A1, B0, B1, ap, bp, jj)                                   \
-  A0 = *reinterpret_cast<const float4*>((ap) + 8 * (jj));                    \
-  A1 = *reinterpret_cast<const float4*>((ap) + 32 * LDS_STRIDE + 8 * (jj));  \
-  B0 = *reinterpret_cast<const float4*>((bp) + 8 * (jj));                    \
-  B1 = *reinterpret_cast<const float4*>((bp) + 32 * LDS_STRIDE + 8 * (jj));
-#define P_MFMA4(A0, A1, B0, B1, x_)                                                   \
-  acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(A0.x_, B0.x_, acc[0][0], 0, 0, 0); \
-  acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(A0.x_, B1.x_, acc[0][1], 0, 0, 0); \
-  acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(A1.x_, B0.x_, acc[1][0], 0, 0, 0); \
-  acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(A1.x_, B1.x_, acc[1][1], 0, 0, 0);
-#define P_MFMA16(A0, A1, B0, B1) \
-  P_MFMA4(A0, A1, B0, B1, x) P_MFMA4(A0, A1, B0, B1, y) P_MFMA4(A0, A1, B0, B1, z) P_MFMA4(A0, A1, B0, B1, w)
 
   // a workgroup whose list is exhausted (or empty: with a device-side row count the grid may exceed the tile count)
   // parks its load stream on a valid tile
   const int park = (int)bid < total_tiles ? (int)bid : 0;
   int ld_tile = (int)bid, ld_kt = 0;
-  P_SETPTRS(park)
-  P_GLOAD
+  set_tile(park);
+  gload_staged(g, a_ld, w_ld, st);
   P_ADVANCE
-  P_LSTORE(0)
+  lds_store_staged(As, Bs, 0, st_off, st);
   __syncthreads();
-  P_GLOAD
+  gload_staged(g, a_ld, w_ld, st);
   P_ADVANCE
 
   f32x16 acc[2][2];
@@ -535,150 +647,19 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_nt_f32_persistent_kernel
 
   int tile = (int)bid, kt = 0, buf = 0;
   while (tile < total_tiles) {
-    {
-      const float* a = As + buf * BM * LDS_STRIDE + a_rd;
-      const float* b = Bs + buf * BN * LDS_STRIDE + b_rd;
-      float4 c0a0, c0a1, c0b0, c0b1, c1a0, c1a1, c1b0, c1b1, c2a0, c2a1, c2b0, c2b1, c3a0, c3a1, c3b0, c3b1;
-      P_READ(c0a0, c0a1, c0b0, c0b1, a, b, 0)
-      P_READ(c1a0, c1a1, c1b0, c1b1, a, b, 1)
-      P_LSTORE(buf ^ 1)
-      P_MFMA16(c0a0, c0a1, c0b0, c0b1)
-      P_READ(c2a0, c2a1, c2b0, c2b1, a, b, 2)
-      P_READ(c3a0, c3a1, c3b0, c3b1, a, b, 3)
-      P_GLOAD
-      P_MFMA16(c1a0, c1a1, c1b0, c1b1)
-      P_MFMA16(c2a0, c2a1, c2b0, c2b1)
-      P_MFMA16(c3a0, c3a1, c3b0, c3b1)
-      __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);  // ds_read: chunks 0,1
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // MFMA
-        __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);  // ds_write
-      }
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);  // ds_read: chunks 2,3
-      }
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);  // global_load
-      }
-      __builtin_amdgcn_sched_group_barrier(0x008, 40, 0);
-    }
-    __syncthreads();  // stays in the MFMA block: the compiler hoists it above the trailing 40 MFMAs, which then cover the wait
+    kstep_f32(As, Bs, buf, a_rd, b_rd, st_off, st, acc, [&] { gload_staged(g, a_ld, w_ld, st); });
+    __syncthreads();  // stays in the MFMA block (kstep_f32)
     P_ADVANCE
     buf ^= 1;
     if (++kt == nk) {
-      // epilogue of this tile: stores only (plus the residual / bias loads), no LDS — the other waves are already
-      // in the next tile's first K-step.  Accumulator map: col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5).
       int mt, nt;
-      P_TILE_MN(tile, mt, nt)
-      const int64_t m0 = (int64_t)mt * BM;
-      const int n0 = nt * BN;
-      if (m0 + BM <= Mrows && n0 + BN <= g.N) {
-        // interior tile: uniform branches only, so that the 64 residual loads go out as one batch and the 64 stores
-        // as another (per-element flag tests serialise them behind a vmcnt(0) each)
-        const int64_t mrow = m0 + wm * 64 + 4 * h;
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni) {  // one column tile (32 accumulators) at a time: bounds the registers in flight
-          const int ncol = n0 + wn * 64 + ni * 32 + l31;
-          if (g.has_bias) {
-            const float bia = g.bias[ncol];
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-              for (int r = 0; r < 16; ++r) acc[mi][ni][r] += bia;
-          }
-          if (g.has_residual) {
-            const float* rp = g.residual + mrow * g.ldr + ncol;
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-              for (int r = 0; r < 16; ++r) acc[mi][ni][r] += rp[(int64_t)(mi * 32 + (r & 3) + 8 * (r >> 2)) * g.ldr];
-          }
-          if (g.act == ACT_RELU) {
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-              for (int r = 0; r < 16; ++r) acc[mi][ni][r] = fmaxf(acc[mi][ni][r], 0.f);
-          } else if (g.act == ACT_GELU) {
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-              for (int r = 0; r < 16; ++r) acc[mi][ni][r] = gelu_erf(acc[mi][ni][r]);
-          }
-          float* cp = g.C + mrow * g.ldc + ncol;
-#pragma unroll
-          for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-              cp[(int64_t)(mi * 32 + (r & 3) + 8 * (r >> 2)) * g.ldc] = acc[mi][ni][r];
-              acc[mi][ni][r] = 0.f;
-            }
-        }
-      } else {
-        // edge tile (the last, partial row panel of a packed batch; a column tail): the same batched structure — rows and
-        // columns past the matrix are CLAMPED for the loads (legal addresses, one batch) and masked for the stores.  With a
-        // per-element `continue` every residual load sat behind its own vmcnt(0) and the 6..24 edge tiles of a launch finished
-        // after everyone else: 12 350 live rows (62 in the last panel) 17.2 -> 16.05 ms of linears per encoder pass
-        // (tools/exp_edge.py; 12 416 rows = 97 full panels: 15.8 ms).
-        const int64_t mrow = m0 + wm * 64 + 4 * h;
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni) {
-          const int n = n0 + wn * 64 + ni * 32 + l31;
-          const bool n_ok = n < g.N;
-          const int nc = n_ok ? n : g.N - 1;
-          if (g.has_bias) {
-            const float bia = g.bias[nc];
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-              for (int r = 0; r < 16; ++r) acc[mi][ni][r] += bia;
-          }
-          if (g.has_residual) {
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-              for (int r = 0; r < 16; ++r) {
-                const int64_t m = mrow + mi * 32 + (r & 3) + 8 * (r >> 2);
-                acc[mi][ni][r] += g.residual[(m < Mrows ? m : Mrows - 1) * g.ldr + nc];
-              }
-          }
-          if (g.act == ACT_RELU) {
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-              for (int r = 0; r < 16; ++r) acc[mi][ni][r] = fmaxf(acc[mi][ni][r], 0.f);
-          } else if (g.act == ACT_GELU) {
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-              for (int r = 0; r < 16; ++r) acc[mi][ni][r] = gelu_erf(acc[mi][ni][r]);
-          }
-#pragma unroll
-          for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-              const int64_t m = mrow + mi * 32 + (r & 3) + 8 * (r >> 2);
-              if (n_ok && m < Mrows) g.C[m * g.ldc + n] = acc[mi][ni][r];
-              acc[mi][ni][r] = 0.f;
-            }
-        }
-      }
+      supertile_mn(g, tiles_m, tile, mt, nt);
+      GDR_LINEAR_TILE_EPILOGUE((int64_t)mt * BM, nt * BN)
       kt = 0;
       tile += G;
     }
   }
-#undef P_TILE_MN
-#undef P_SETPTRS
-#undef P_GLOAD
 #undef P_ADVANCE
-#undef P_LSTORE
-#undef P_READ
-#undef P_MFMA4
-#undef P_MFMA16
 }
 
 // ---- stream-K tail for the persistent kernel ----------------------------------------------------------------------
@@ -693,7 +674,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_nt_f32_persistent_kernel
 // bit-identical to the one-workgroup tile.  In the tail a workgroup runs its BEGINNING fragment first (it depends on
 // nobody), then its whole tile, and the CONTINUED fragment last, by which time the predecessor published long ago (a range
 // is at least one tile long, so the predecessor's fragment is shorter than what precedes the take-over); the wait is a
-// bounded spin.  Same flattened K-step stream, same K-step body and schedule as above.
+// bounded spin.  Same flattened K-step stream and the same kstep_f32 as above.
 // Memory model (MI355X_MICROARCH.md, visibility): the XCDs' L2s are not coherent with each other inside a kernel.  The
 // producer stores its accumulators write-through (sc1 buffer stores: no L2 write-back fence needed), every wave drains its
 // stores (s_waitcnt vmcnt(0)), the workgroup meets, one lane stores the flag (relaxed, agent scope).  The consumer's lane 0
@@ -792,8 +773,7 @@ static bool streamk_wanted(int64_t tiles, int nk) {
   return rem != 0 && (512 - rem) * nk > (int64_t)thr * 512;
 }
 // K slabs of the 128x128 split-K form (tiles < 192: the grid cannot fill the chip): about 384 workgroups per launch, at
-// least two K-steps per slab, and no more slabs than the workspace holds.  < 2: not split.  launch_linear_f32_ws and
-// gdr_linear_f32_form both ask here.
+// least two K-steps per slab, and no more slabs than the workspace holds.  < 2: not split.
 static int linear_f32_splitk_slabs(int64_t tiles, int nk, size_t ws_bytes) {
   constexpr int target = 384;  // desired number of workgroups per split launch
   const size_t tile_bytes = (size_t)BM * BN * sizeof(float);
@@ -808,11 +788,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_nt_f32_streamk_kernel(co
   __shared__ __attribute__((aligned(16))) float smem[2 * BM * LDS_STRIDE + 2 * BN * LDS_STRIDE];
   float* const As = smem;
   float* const Bs = smem + 2 * BM * LDS_STRIDE;
-  unsigned bid = blockIdx.x;
-  {
-    const unsigned nblk = gridDim.x, q = nblk >> 3, r = nblk & 7u, xcd = bid & 7u, j = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-  }
+  const unsigned bid = xcd_remap(blockIdx.x, gridDim.x);
   const int G = (int)gridDim.x;
   const int tid = threadIdx.x;
   const int lrow = tid >> 3;
@@ -831,76 +807,21 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_nt_f32_streamk_kernel(co
 
   int a_ld[4];  // element offsets from g.A / g.W, 32-bit (the launcher sends operands of >= 2^31 elements to the whole-tile
   int w_ld[4];  // kernel): with 64-bit offsets the segment bookkeeping pushed three spills into the K-step
-// tile index -> (row panel, column tile): supertiles of GM row panels x all column tiles, row-panel-fastest inside, so
-// that the 64 tiles an XCD works on at a time are ~8 row panels x 8 column tiles (16 operand panels through its L2)
-// instead of a few row panels x every column tile (N=3072: 27 panels).  GM travels in g.ksplit (unused by this kernel).
-#define P_TILE_MN(item_, mt_, nt_)                                           \
-  {                                                                          \
-    const int tile_ = S > 1 ? (item_) / S : (item_);                         \
-    const int per_ = g.ksplit * g.tiles_n;                                   \
-    const int grp_ = (tile_) / per_, loc_ = (tile_) - grp_ * per_;           \
-    const int gm_ = min(g.ksplit, tiles_m - grp_ * g.ksplit);                \
-    nt_ = loc_ / gm_;                                                        \
-    mt_ = grp_ * g.ksplit + (loc_ - nt_ * gm_);                              \
-  }
-#define P_SETPTRS(tile_)                                                     \
-  {                                                                          \
-    int mt_, nt_;                                                            \
-    P_TILE_MN(tile_, mt_, nt_)                                               \
-    _Pragma("unroll") for (int p = 0; p < 4; ++p) {                          \
-      int64_t ra_ = (int64_t)mt_ * BM + lrow + 32 * p;                       \
-      ra_ = ra_ < Mrows ? ra_ : Mrows - 1;                                   \
-      int rw_ = nt_ * BN + lrow + 32 * p;                                    \
-      rw_ = rw_ < g.N ? rw_ : g.N - 1;                                       \
-      const int ks_ = S > 1 ? ((tile_) % S) * g.kchunk : 0;                  \
-      a_ld[p] = (int)(ra_ * g.lda + lcol + ks_);                             \
-      w_ld[p] = (int)((int64_t)rw_ * g.ldw + lcol + ks_);                    \
-    }                                                                        \
-  }
-  float4 ra0, ra1, ra2, ra3, rb0, rb1, rb2, rb3;
-#define P_GLOAD                                          \
-  ra0 = *reinterpret_cast<const float4*>(g.A + a_ld[0]); \
-  ra1 = *reinterpret_cast<const float4*>(g.A + a_ld[1]); \
-  ra2 = *reinterpret_cast<const float4*>(g.A + a_ld[2]); \
-  ra3 = *reinterpret_cast<const float4*>(g.A + a_ld[3]); \
-  rb0 = *reinterpret_cast<const float4*>(g.W + w_ld[0]); \
-  rb1 = *reinterpret_cast<const float4*>(g.W + w_ld[1]); \
-  rb2 = *reinterpret_cast<const float4*>(g.W + w_ld[2]); \
-  rb3 = *reinterpret_cast<const float4*>(g.W + w_ld[3]);
+  auto set_item = [&](int item_) {  // a tile, or unit = tile * S + s: chunk s starts s * g.kchunk into the rows
+    int mt_, nt_;
+    supertile_mn(g, tiles_m, S > 1 ? item_ / S : item_, mt_, nt_);
+    staging_offsets(g, Mrows, mt_, nt_, lrow, lcol, S > 1 ? (item_ % S) * g.kchunk : 0, a_ld, w_ld);
+  };
+  Staged st;
 #define P_ADVANCE                                                            \
   if (++ld_kt == ld_kend) { /* the load stream crosses into the next segment (or parks on the last one's start) */ \
     ld_seg = ld_seg + 1 < nseg ? ld_seg + 1 : nseg - 1;                      \
     SK_SEG(ld_seg, ld_tile, ld_kt, ld_kend)                                  \
-    P_SETPTRS(ld_tile)                                                       \
+    set_item(ld_tile);                                                       \
     _Pragma("unroll") for (int p = 0; p < 4; ++p) a_ld[p] += ld_kt * BK, w_ld[p] += ld_kt * BK; \
   } else {                                                                   \
     _Pragma("unroll") for (int p = 0; p < 4; ++p) a_ld[p] += BK, w_ld[p] += BK; \
   }
-#define P_LSTORE(buf_)                                                       \
-  {                                                                          \
-    float* a_ = As + (buf_)*BM * LDS_STRIDE + st_off;                        \
-    float* b_ = Bs + (buf_)*BN * LDS_STRIDE + st_off;                        \
-    *reinterpret_cast<float4*>(a_) = ra0;                                    \
-    *reinterpret_cast<float4*>(a_ + 32 * LDS_STRIDE) = ra1;                  \
-    *reinterpret_cast<float4*>(a_ + 64 * LDS_STRIDE) = ra2;                  \
-    *reinterpret_cast<float4*>(a_ + 96 * LDS_STRIDE) = ra3;                  \
-    *reinterpret_cast<float4*>(b_) = rb0;                                    \
-    *reinterpret_cast<float4*>(b_ + 32 * LDS_STRIDE) = rb1;                  \
-    *reinterpret_cast<float4*>(b_ + 64 * LDS_STRIDE) = rb2;                  \
-    *reinterpret_cast<float4*>(b_ + 96 * LDS_STRIDE) = rb3;                  \
-  }
-#define P_READ(A0, A1, B0, B1, ap, bp, jj)                                   \
-  A0 = *reinterpret_cast<const float4*>((ap) + 8 * (jj));                    \
-  A1 = *reinterpret_cast<const float4*>((ap) + 32 * LDS_STRIDE + 8 * (jj));  \
-  B0 = *reinterpret_cast<const float4*>((bp) + 8 * (jj));                    \
-  B1 = *reinterpret_cast<const float4*>((bp) + 32 * LDS_STRIDE + 8 * (jj));
-#define P_MFMA4(A0, A1, B0, B1, x_)                                                   \
-  acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(A0.x_, B0.x_, acc[0][0], 0, 0, 0); \
-  acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(A0.x_, B1.x_, acc[0][1], 0, 0, 0); \
-  acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(A1.x_, B0.x_, acc[1][0], 0, 0, 0); \
-  acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(A1.x_, B1.x_, acc[1][1], 0, 0, 0);
-#define P_MFMA16(A0, A1, B0, B1) \
-  P_MFMA4(A0, A1, B0, B1, x) P_MFMA4(A0, A1, B0, B1, y) P_MFMA4(A0, A1, B0, B1, z) P_MFMA4(A0, A1, B0, B1, w)
 
   // ---- this workgroup's range of K-steps and its segments, in processing order:
   //      [begun fragment: tile t_last, k 0..k_last) -> stored]  [whole tiles t_full0 .. t_full0+n_full)]
@@ -968,13 +889,13 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_nt_f32_streamk_kernel(co
   }
   int ld_seg = 0, ld_kt, ld_kend, ld_tile;
   SK_SEG(0, ld_tile, ld_kt, ld_kend)
-  P_SETPTRS(ld_tile)
+  set_item(ld_tile);
   _Pragma("unroll") for (int p = 0; p < 4; ++p) a_ld[p] += ld_kt * BK, w_ld[p] += ld_kt * BK;
-  P_GLOAD
+  gload_staged(g, a_ld, w_ld, st);
   P_ADVANCE
-  P_LSTORE(0)
+  lds_store_staged(As, Bs, 0, st_off, st);
   __syncthreads();
-  P_GLOAD
+  gload_staged(g, a_ld, w_ld, st);
   P_ADVANCE
 
   f32x16 acc[2][2];
@@ -989,39 +910,8 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_nt_f32_streamk_kernel(co
   SK_SEG(0, tile, kt, kend)  // never the continued fragment: with total_tiles >= G a range is at least nk steps long, so
                              // something (a begun fragment or a whole tile) always precedes it
   while (seg < nseg) {
-    {
-      const float* a = As + buf * BM * LDS_STRIDE + a_rd;
-      const float* b = Bs + buf * BN * LDS_STRIDE + b_rd;
-      float4 c0a0, c0a1, c0b0, c0b1, c1a0, c1a1, c1b0, c1b1, c2a0, c2a1, c2b0, c2b1, c3a0, c3a1, c3b0, c3b1;
-      P_READ(c0a0, c0a1, c0b0, c0b1, a, b, 0)
-      P_READ(c1a0, c1a1, c1b0, c1b1, a, b, 1)
-      P_LSTORE(buf ^ 1)
-      P_MFMA16(c0a0, c0a1, c0b0, c0b1)
-      P_READ(c2a0, c2a1, c2b0, c2b1, a, b, 2)
-      P_READ(c3a0, c3a1, c3b0, c3b1, a, b, 3)
-      P_GLOAD
-      P_MFMA16(c1a0, c1a1, c1b0, c1b1)
-      P_MFMA16(c2a0, c2a1, c2b0, c2b1)
-      P_MFMA16(c3a0, c3a1, c3b0, c3b1)
-      __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);  // ds_read: chunks 0,1
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // MFMA
-        __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);  // ds_write
-      }
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);  // ds_read: chunks 2,3
-      }
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);  // global_load
-      }
-      __builtin_amdgcn_sched_group_barrier(0x008, 40, 0);
-    }
-    __syncthreads();  // stays in the MFMA block: the compiler hoists it above the trailing 40 MFMAs, which then cover the wait
+    kstep_f32(As, Bs, buf, a_rd, b_rd, st_off, st, acc, [&] { gload_staged(g, a_ld, w_ld, st); });
+    __syncthreads();  // stays in the MFMA block (kstep_f32)
     P_ADVANCE
     buf ^= 1;
     if (++kt == kend) {
@@ -1046,12 +936,6 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_nt_f32_streamk_kernel(co
       __syncthreads();
       if (tid == 0) __hip_atomic_store(sk.flag + bid, sk.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
      } else {
-      // epilogue of this tile: stores only (plus the residual / bias loads), no LDS — the other waves are already
-      // in the next tile's first K-step.  Accumulator map: col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5).
-      int mt, nt;
-      P_TILE_MN(tile, mt, nt)
-      const int64_t m0 = (int64_t)mt * BM;
-      const int n0 = nt * BN;
       if (UNITS) {  // a finished (tile, chunk) unit: the raw partial, in gemm_nt_f32_kernel's slab layout
         float* slab = sk.slabs + (int64_t)tile * (BM * BN) + (wm * 64 + 4 * h) * BN + wn * 64 + l31;  // unit index = tile * S + s already
 #pragma unroll
@@ -1063,95 +947,10 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_nt_f32_streamk_kernel(co
               slab[(mi * 32 + (r & 3) + 8 * (r >> 2)) * BN + ni * 32] = acc[mi][ni][r];
               acc[mi][ni][r] = 0.f;
             }
-      } else if (m0 + BM <= Mrows && n0 + BN <= g.N) {
-        // interior tile: uniform branches only, so that the 64 residual loads go out as one batch and the 64 stores
-        // as another (per-element flag tests serialise them behind a vmcnt(0) each)
-        const int64_t mrow = m0 + wm * 64 + 4 * h;
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni) {  // one column tile (32 accumulators) at a time: bounds the registers in flight
-          const int ncol = n0 + wn * 64 + ni * 32 + l31;
-          if (g.has_bias) {
-            const float bia = g.bias[ncol];
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-              for (int r = 0; r < 16; ++r) acc[mi][ni][r] += bia;
-          }
-          if (g.has_residual) {
-            const float* rp = g.residual + mrow * g.ldr + ncol;
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-              for (int r = 0; r < 16; ++r) acc[mi][ni][r] += rp[(int64_t)(mi * 32 + (r & 3) + 8 * (r >> 2)) * g.ldr];
-          }
-          if (g.act == ACT_RELU) {
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-              for (int r = 0; r < 16; ++r) acc[mi][ni][r] = fmaxf(acc[mi][ni][r], 0.f);
-          } else if (g.act == ACT_GELU) {
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-              for (int r = 0; r < 16; ++r) acc[mi][ni][r] = gelu_erf(acc[mi][ni][r]);
-          }
-          float* cp = g.C + mrow * g.ldc + ncol;
-#pragma unroll
-          for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-              cp[(int64_t)(mi * 32 + (r & 3) + 8 * (r >> 2)) * g.ldc] = acc[mi][ni][r];
-              acc[mi][ni][r] = 0.f;
-            }
-        }
       } else {
-        // edge tile (the last, partial row panel of a packed batch; a column tail): the same batched structure — rows and
-        // columns past the matrix are CLAMPED for the loads (legal addresses, one batch) and masked for the stores.  With a
-        // per-element `continue` every residual load sat behind its own vmcnt(0) and the 6..24 edge tiles of a launch finished
-        // after everyone else: 12 350 live rows (62 in the last panel) 17.2 -> 16.05 ms of linears per encoder pass
-        // (tools/exp_edge.py; 12 416 rows = 97 full panels: 15.8 ms).
-        const int64_t mrow = m0 + wm * 64 + 4 * h;
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni) {
-          const int n = n0 + wn * 64 + ni * 32 + l31;
-          const bool n_ok = n < g.N;
-          const int nc = n_ok ? n : g.N - 1;
-          if (g.has_bias) {
-            const float bia = g.bias[nc];
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-              for (int r = 0; r < 16; ++r) acc[mi][ni][r] += bia;
-          }
-          if (g.has_residual) {
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-              for (int r = 0; r < 16; ++r) {
-                const int64_t m = mrow + mi * 32 + (r & 3) + 8 * (r >> 2);
-                acc[mi][ni][r] += g.residual[(m < Mrows ? m : Mrows - 1) * g.ldr + nc];
-              }
-          }
-          if (g.act == ACT_RELU) {
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-              for (int r = 0; r < 16; ++r) acc[mi][ni][r] = fmaxf(acc[mi][ni][r], 0.f);
-          } else if (g.act == ACT_GELU) {
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-              for (int r = 0; r < 16; ++r) acc[mi][ni][r] = gelu_erf(acc[mi][ni][r]);
-          }
-#pragma unroll
-          for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-              const int64_t m = mrow + mi * 32 + (r & 3) + 8 * (r >> 2);
-              if (n_ok && m < Mrows) g.C[m * g.ldc + n] = acc[mi][ni][r];
-              acc[mi][ni][r] = 0.f;
-            }
-        }
+        int mt, nt;
+        supertile_mn(g, tiles_m, tile, mt, nt);
+        GDR_LINEAR_TILE_EPILOGUE((int64_t)mt * BM, nt * BN)
       }
      }
       if (++seg < nseg) {
@@ -1162,14 +961,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_nt_f32_streamk_kernel(co
   }
 #undef SK_SEG
 #undef SK_TAKEOVER
-#undef P_TILE_MN
-#undef P_SETPTRS
-#undef P_GLOAD
 #undef P_ADVANCE
-#undef P_LSTORE
-#undef P_READ
-#undef P_MFMA4
-#undef P_MFMA16
 }
 
 template <int EPI, bool BF16 = false>
@@ -1234,230 +1026,221 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
   }
 }
 
+// ---- which form a linear takes: the one ladder.  launch_linear_f32_ws switches on its answer, the other launchers and
+// gdr_linear_f32_form / gdr_linear_f32_splitk ask it; no threshold lives anywhere else.
+enum LinearForm {
+  FORM_NONE = 0,       // no valid shape (M, N or K <= 0, K % 4 != 0)
+  FORM_TILES,          // one 128x128 tile per workgroup (any K % 4 == 0)
+  FORM_PERSISTENT,     // more than 512 tiles: 512 workgroups walk the tiles
+  FORM_SMALL,          // 64x64 tiles (gemm_small.hip), `slabs` K slabs (1: whole K)
+  FORM_SPLITK,         // 128x128 tiles x `slabs` K slabs of `chunk_steps` K-steps in the workspace + fixed-order reduction
+  FORM_STREAMK_UNITS,  // the same (tile, slab) units dealt by K-step ranges to 256 workgroups; device-side row count only
+  FORM_STREAMK_256,    // whole-K tiles dealt by K-step ranges to 256 workgroups
+  FORM_STREAMK_TAIL    // more than 512 tiles: whole-tile rounds, then the stream-K tail, on 512 workgroups
+};
+struct LinearRoute {
+  LinearForm form;
+  int slabs, chunk_steps;  // the split forms
+  int grid;                // workgroups of the persistent / stream-K forms
+};
+struct LinearCall {
+  int64_t M;  // the rows the grid is sized for
+  int N, K;
+  int64_t lda, ldw;
+  size_t ws_bytes;   // 0: no workspace
+  bool has_sk;       // a StreamK scratch is present
+  bool dev_rows;     // the live row count is on the device
+  int64_t row_hint;  // the live row count if the host happens to know it (< 0: unknown) — a tuning input only
+  bool whole_k;      // launch_linear_f32_dev: no small-tile / split-K form (their k order differs: a row's result must not depend
+                     // on how many rows happen to be live), and the stream-K admission goes by the LIVE tile count of the hint
+};
+static LinearRoute linear_f32_route(const LinearCall& c) {
+  if (c.M <= 0 || c.N <= 0 || c.K <= 0 || c.K % 4 != 0) return {FORM_NONE, 0, 0, 0};
+  const int tiles_n = (c.N + BN - 1) / BN;
+  const int64_t tiles = ((c.M + BM - 1) / BM) * tiles_n;
+  const int nk = c.K / BK;
+  const bool kfull = c.K % BK == 0;
+  if (!c.whole_k && tiles < 192 && nk >= 4 && kfull) {  // the grid cannot fill the chip (decode: M = batch*beams rows)
+    if (c.M <= 1536) {
+      // few rows: 64x64 tiles, split along K only as far as still needed.  With more rows (a 64-query encoder batch) the
+      // 128x128 core with split-K measured 5 % faster.
+      const int S = linear_f32_small_splits(c.M, c.N, c.K, c.ws_bytes > 0, c.ws_bytes);
+      if (S) return {FORM_SMALL, S, 0, 0};
+    }
+    const int S = linear_f32_splitk_slabs(tiles, nk, c.ws_bytes);
+    if (S >= 2) {
+      const int chunk_steps = (nk + S - 1) / S, S2 = (nk + chunk_steps - 1) / chunk_steps;
+      // A packed batch (device-side row count, live rows known to the host as a hint) whose LIVE (tile, chunk) units number
+      // between one and two per CU: one workgroup per unit leaves every CU waiting for those that got two (a 64-query
+      // encoder pass, N = 768: 78 live tiles x 4 chunks = 312 workgroups on 256 CUs, 94 us for K = 3072).  The stream-K
+      // kernel on 256 workgroups deals the same units by K-step ranges instead — same chunks, same k order inside a chunk,
+      // same slabs, same reduction: bit-identical — and the busiest CU runs ~1.2 units' worth instead of 2.
+      // Taken for every packed batch of this size class: the live row count is on the device (a host copy would cost a
+      // synchronisation), and the kernel is right for any count — up to 256 live units each gets its own workgroup like
+      // in the one-unit-per-workgroup form, above that they are dealt by ranges.  With the host's hint (the bench) a
+      // launch whose units all fit one per CU keeps the plain form.
+      const int64_t units_hint = c.dev_rows && c.row_hint >= 0 ? ((c.row_hint + BM - 1) / BM) * tiles_n * S2 : -1;
+      const size_t need = STREAMK_BYTES + (size_t)tiles * S2 * BM * BN * sizeof(float);
+      const bool units = c.has_sk && c.dev_rows && nk % chunk_steps == 0 && tiles * S2 > 256 && (units_hint < 0 || units_hint > 256) &&
+                         need <= c.ws_bytes && streamk_fits(c.M, c.lda, c.N, c.ldw);
+      return {units ? FORM_STREAMK_UNITS : FORM_SPLITK, S2, chunk_steps, units ? 256 : 0};
+    }
+  }
+  const int64_t tiles_adm = c.whole_k && c.row_hint >= 0 ? ((c.row_hint + BM - 1) / BM) * tiles_n : tiles;
+  const bool sk_ok = c.has_sk && kfull && streamk_fits(c.M, c.lda, c.N, c.ldw);
+  if (sk_ok && tiles > 256 && streamk_mid_wanted(tiles_adm)) return {FORM_STREAMK_256, 0, 0, 256};
+  if (tiles > 512 && tiles < 0x7fffffff && kfull)  // more than one round of tiles on 256 CUs x 2 resident workgroups
+    return {sk_ok && streamk_wanted(tiles_adm, nk) ? FORM_STREAMK_TAIL : FORM_PERSISTENT, 0, 0, 512};
+  return {FORM_TILES, 0, 0, 0};
+}
+
+// Supertile height of the persistent / stream-K forms (supertile_mn; travels in GemmArgs.ksplit).  Measured HBM-side fetch
+// per launch (PMC, M = 20480): N=3072 1112 -> 557 MB and N=2304 653 -> 443 MB with 8-panel supertiles, but N=768 552 -> 684 MB
+// (its 6 column tiles already fit one XCD's L2 next to 10 row panels): wide outputs only.  Time is unchanged either way (the
+// kernel is MFMA-bound); this is traffic and energy.
+static int supertile_height(int tiles_n) { return tiles_n >= 12 ? 8 : 1; }
+
+// Validates a linear call, decodes its epilogue and fills the kernel arguments, for every launcher below.  `what` heads the
+// messages; K, lda and ldw must be multiples of `mult` elements (16 bytes: 4 floats, 8 bf16).
+static int build_linear_args(const char* what, int mult, const void* A, int64_t lda, const void* W, int64_t ldw, float* C,
+                             int64_t ldc, int64_t M, int N, int K, int epilogue, const float* bias, const float* residual,
+                             int64_t ldr, const int64_t* m_dev, GemmArgs* g) {
+  GDR_CHECK_ARG(A && W && C, "%s: null pointer", what);
+  GDR_CHECK_ARG(M >= 0 && N > 0 && K > 0, "%s: bad shape M=%lld N=%d K=%d", what, (long long)M, N, K);
+  GDR_CHECK_ARG(K % mult == 0 && lda % mult == 0 && ldw % mult == 0, "%s: K, lda, ldw must be multiples of %d", what, mult);
+  GDR_CHECK_ARG(lda >= K && ldw >= K && ldc >= N, "%s: leading dimension smaller than the row", what);
+  GDR_CHECK_ARG(aligned16(A) && aligned16(W), "%s: A and W must be 16-byte aligned", what);
+  LinearEpilogue e;
+  GDR_CHECK_ARG(decode_epilogue(epilogue, &e), "%s: unknown epilogue %d", what, epilogue);
+  GDR_CHECK_ARG(!e.has_bias || bias, "%s: epilogue %d needs bias", what, epilogue);
+  GDR_CHECK_ARG(!e.has_residual || (residual && ldr >= N), "%s: epilogue %d needs residual", what, epilogue);
+  *g = GemmArgs{};
+  g->A = static_cast<const float*>(A), g->W = static_cast<const float*>(W);  // opaque: the bf16 kernel addresses operands in bytes
+  g->C = C, g->bias = bias, g->residual = residual;
+  g->lda = lda, g->ldw = ldw, g->ldc = ldc, g->ldr = ldr;
+  g->M = M, g->N = N, g->K = K, g->m_dev = m_dev;
+  g->tiles_n = (N + BN - 1) / BN;
+  g->has_bias = e.has_bias, g->has_residual = e.has_residual, g->act = e.act;
+  return GDR_OK;
+}
+
+// Launches the stream-K kernel on `grid` (256 or 512) workgroups over `items` tiles, or (tile, slab) units of S slabs each
+// whose raw partials go to `slabs`.  Fails if an earlier launch's hand-off timed out (streamk_poll_error).
+template <bool UNITS>
+static int launch_streamk(const GemmArgs& g, int64_t items, int grid, StreamK* sk, int S, float* slabs, const char* what,
+                          hipStream_t stream) {
+  GDR_TRY(streamk_poll_error());
+  const StreamKArgs ska{sk->part, sk->flag, ++sk->epoch, streamk_err_word(), S, slabs};
+  hipLaunchKernelGGL(gemm_nt_f32_streamk_kernel<UNITS>, dim3((unsigned)grid), dim3(GEMM_THREADS), 0, stream, g, (int)items, ska);
+  GDR_CHECK_LAUNCH(what);
+  return GDR_OK;
+}
+
+// The whole-K forms of a route on the 128x128 core: stream-K, persistent, or one tile per workgroup.
+static int launch_whole_k(GemmArgs& g, const LinearRoute& r, StreamK* sk, hipStream_t stream) {
+  const int64_t tiles_m = (g.M + BM - 1) / BM, tiles = tiles_m * g.tiles_n;
+  switch (r.form) {
+    case FORM_STREAMK_256:
+    case FORM_STREAMK_TAIL:
+      g.ksplit = supertile_height(g.tiles_n);
+      return launch_streamk<false>(g, tiles, r.grid, sk, 0, nullptr,
+                                   r.grid == 256 ? "gemm_nt_f32_streamk_kernel(256)" : "gemm_nt_f32_streamk_kernel", stream);
+    case FORM_PERSISTENT:
+      g.ksplit = supertile_height(g.tiles_n);
+      hipLaunchKernelGGL(gemm_nt_f32_persistent_kernel, dim3((unsigned)r.grid), dim3(GEMM_THREADS), 0, stream, g, (int)tiles);
+      GDR_CHECK_LAUNCH("gemm_nt_f32_persistent_kernel");
+      return GDR_OK;
+    default:
+      return launch<EPI_LINEAR>(g, tiles_m, stream);
+  }
+}
+
 int launch_linear_f32(const float* A, int64_t lda, const float* W, int64_t ldw, float* C, int64_t ldc, int64_t M,
                       int N, int K, int epilogue, const float* bias, const float* residual, int64_t ldr,
                       hipStream_t stream) {
   return launch_linear_f32_ws(A, lda, W, ldw, C, ldc, M, N, K, epilogue, bias, residual, ldr, nullptr, 0, stream, nullptr);
 }
 
-// With a scratch buffer, linears whose tile grid cannot fill the chip (decode: M = batch*beams rows) are split
-// along K into partial slabs + a fixed-order reduction that applies the epilogue.
-int launch_linear_f32_ws_dev(const float* A, int64_t lda, const float* W, int64_t ldw, float* C, int64_t ldc, int64_t M_max,
-                             const int64_t* m_dev, int N, int K, int epilogue, const float* bias, const float* residual,
-                             int64_t ldr, float* splitk_ws, size_t splitk_ws_bytes, hipStream_t stream, StreamK* sk) {
-  if (M_max == 0) return GDR_OK;
-  GDR_CHECK_ARG(m_dev, "linear(dev rows): null row count");
-  const int64_t tiles = ((M_max + BM - 1) / BM) * ((N + BN - 1) / BN);
-  if (tiles < 192 && M_max <= 1536 && K / BK >= 4 && K % BK == 0) {  // the small-tile form, as launch_linear_f32_ws picks it
-    GDR_CHECK_ARG(A && W && C, "linear(dev rows): null pointer");
-    GDR_CHECK_ARG(epilogue >= GDR_EPI_NONE && epilogue <= GDR_EPI_BIAS_GELU, "linear(dev rows): unknown epilogue %d", epilogue);
-    GDR_CHECK_ARG(lda % 4 == 0 && ldw % 4 == 0 && lda >= K && ldw >= K && ldc >= N && aligned16(A) && aligned16(W),
-                  "linear(dev rows): bad leading dimension / alignment");
-    const bool nb = epilogue == GDR_EPI_BIAS || epilogue == GDR_EPI_BIAS_RELU || epilogue == GDR_EPI_BIAS_RESIDUAL ||
-                    epilogue == GDR_EPI_BIAS_GELU;
-    const bool nr = epilogue == GDR_EPI_RESIDUAL || epilogue == GDR_EPI_BIAS_RESIDUAL;
-    GDR_CHECK_ARG((!nb || bias) && (!nr || (residual && ldr >= N)), "linear(dev rows): epilogue %d lacks an operand", epilogue);
-    const int act = (epilogue == GDR_EPI_RELU || epilogue == GDR_EPI_BIAS_RELU) ? ACT_RELU
-                    : epilogue == GDR_EPI_BIAS_GELU                             ? ACT_GELU
-                                                                                : ACT_NONE;
-    const int rc = launch_linear_f32_small(A, lda, W, ldw, C, ldc, M_max, N, K, nb, nr, act, bias, residual, ldr, splitk_ws,
-                                           splitk_ws_bytes, stream, m_dev, nullptr, nullptr, sk ? sk->live : nullptr);
-    if (rc <= 0) return rc;
-  }
-  return launch_linear_f32_dev(A, lda, W, ldw, C, ldc, M_max, m_dev, N, K, epilogue, bias, residual, ldr, -1, stream, sk);
-}
-
 // m_dev (may be null): the live row count on the device, *m_dev <= M.  Every kernel FORM is chosen from M alone, so a row's
 // result does not depend on how many rows are live (the padded and the packed encoder forms agree bit for bit); tiles past
 // the live rows exit at once and the stream-K forms deal only the live tiles' K-steps.  prof_rows: the live count if the
-// host happens to know it — profiler flop accounting only.
+// host happens to know it — profiler flop accounting, and the hint of the stream-K-over-units admission.
+// With a scratch buffer, linears whose tile grid cannot fill the chip (decode: M = batch*beams rows) are split along K into
+// partial slabs + a fixed-order reduction that applies the epilogue.
 int launch_linear_f32_ws(const float* A, int64_t lda, const float* W, int64_t ldw, float* C, int64_t ldc, int64_t M,
                          int N, int K, int epilogue, const float* bias, const float* residual, int64_t ldr,
                          float* splitk_ws, size_t splitk_ws_bytes, hipStream_t stream, StreamK* sk, const int64_t* m_dev,
                          int64_t prof_rows) {
   if (M == 0) return GDR_OK;  // empty batch: nothing to do (pointers of empty tensors may be null)
-  GDR_CHECK_ARG(A && W && C, "linear: null pointer");
-  GDR_CHECK_ARG(M >= 0 && N > 0 && K > 0, "linear: bad shape M=%lld N=%d K=%d", (long long)M, N, K);
-  GDR_CHECK_ARG(K % 4 == 0 && lda % 4 == 0 && ldw % 4 == 0, "linear: K, lda, ldw must be multiples of 4");
-  GDR_CHECK_ARG(lda >= K && ldw >= K && ldc >= N, "linear: leading dimension smaller than the row");
-  GDR_CHECK_ARG(aligned16(A) && aligned16(W), "linear: A and W must be 16-byte aligned");
-  const bool needs_bias = epilogue == GDR_EPI_BIAS || epilogue == GDR_EPI_BIAS_RELU ||
-                          epilogue == GDR_EPI_BIAS_RESIDUAL || epilogue == GDR_EPI_BIAS_GELU;
-  const bool needs_res = epilogue == GDR_EPI_RESIDUAL || epilogue == GDR_EPI_BIAS_RESIDUAL;
-  GDR_CHECK_ARG(!needs_bias || bias, "linear: epilogue %d needs bias", epilogue);
-  GDR_CHECK_ARG(!needs_res || (residual && ldr >= N), "linear: epilogue %d needs residual", epilogue);
-  if (M == 0) return GDR_OK;
-  GemmArgs g{};
-  g.A = A, g.W = W, g.C = C, g.bias = bias, g.residual = residual;
-  g.lda = lda, g.ldw = ldw, g.ldc = ldc, g.ldr = ldr;
-  g.M = M, g.N = N, g.K = K, g.m_dev = m_dev;
-  g.tiles_n = (N + BN - 1) / BN;
-  const int64_t tiles_m = (M + BM - 1) / BM;
-  g.has_bias = needs_bias, g.has_residual = needs_res;
-  g.act = (epilogue == GDR_EPI_RELU || epilogue == GDR_EPI_BIAS_RELU) ? ACT_RELU
-          : epilogue == GDR_EPI_BIAS_GELU                             ? ACT_GELU
-                                                                      : ACT_NONE;
-  if (epilogue < GDR_EPI_NONE || epilogue > GDR_EPI_BIAS_GELU) {
-    set_error("linear: unknown epilogue %d", epilogue);
-    return GDR_EINVAL;
-  }
-  const double flops = 2.0 * (double)(m_dev && prof_rows >= 0 ? prof_rows : M) * (double)N * (double)K;  // profiler, by tile share
-  const int64_t tiles = tiles_m * g.tiles_n;
-  const int nk = K / BK;
-  constexpr int64_t SLOTS = 512;                      // 256 CUs x 2 resident workgroups
-  const size_t tile_bytes = (size_t)BM * BN * sizeof(float);
-  auto split_launch = [&](int64_t first_tile, int64_t n_tiles, int S) -> int {
-    const int chunk_steps = (nk + S - 1) / S;
-    S = (nk + chunk_steps - 1) / chunk_steps;
+  GemmArgs g;
+  GDR_TRY(build_linear_args("linear", 4, A, lda, W, ldw, C, ldc, M, N, K, epilogue, bias, residual, ldr, m_dev, &g));
+  LinearRoute r = linear_f32_route({M, N, K, lda, ldw, splitk_ws ? splitk_ws_bytes : 0, sk != nullptr, m_dev != nullptr, prof_rows, false});
+  // the units' slabs follow the hand-off scratch inside ONE workspace: a scratch that lives elsewhere keeps the plain split form
+  if (r.form == FORM_STREAMK_UNITS && sk->part != splitk_ws) r.form = FORM_SPLITK;
+  const double flops = 2.0 * (double)(m_dev && prof_rows >= 0 ? prof_rows : M) * (double)N * (double)K;  // profiler
+  if (r.form == FORM_SMALL)
+    return launch_linear_f32_small(A, lda, W, ldw, C, ldc, M, N, K, g.has_bias, g.has_residual, g.act, bias, residual, ldr, splitk_ws,
+                                   splitk_ws_bytes, stream, m_dev, nullptr, nullptr, sk ? sk->live : nullptr);
+  if (r.form == FORM_SPLITK || r.form == FORM_STREAMK_UNITS) {
+    // raw partial tiles into the workspace (behind the hand-off scratch if the stream-K kernel deals them), then the reduction
+    const int64_t tiles = ((M + BM - 1) / BM) * g.tiles_n;
+    float* slabs = r.form == FORM_SPLITK ? splitk_ws : reinterpret_cast<float*>(reinterpret_cast<char*>(splitk_ws) + STREAMK_BYTES);
     GemmArgs p = g;
-    p.C = splitk_ws, p.has_bias = 0, p.has_residual = 0, p.act = ACT_NONE;
-    p.ksplit = S, p.kchunk = chunk_steps * BK, p.tile_base = (int)first_tile;
-    const int64_t blocks = n_tiles * S;
-    {
-      ProfScope prof(PROF_LINEAR, flops * (double)n_tiles / (double)tiles, stream);
-      hipLaunchKernelGGL(gemm_nt_f32_kernel<EPI_LINEAR>, dim3((unsigned)blocks), dim3(GEMM_THREADS), 0, stream, p);
+    p.C = slabs, p.has_bias = 0, p.has_residual = 0, p.act = ACT_NONE;
+    p.kchunk = r.chunk_steps * BK, p.tile_base = 0;
+    if (r.form == FORM_SPLITK) {
+      p.ksplit = r.slabs;
+      {
+        ProfScope prof(PROF_LINEAR, flops, stream);
+        hipLaunchKernelGGL(gemm_nt_f32_kernel<EPI_LINEAR>, dim3((unsigned)(tiles * r.slabs)), dim3(GEMM_THREADS), 0, stream, p);
+      }
+      GDR_CHECK_LAUNCH("gemm_nt_f32_kernel(split)");
+    } else {
+      p.ksplit = 1;  // supertile height, unused at these widths
+      ProfScope prof(PROF_LINEAR, flops, stream);
+      GDR_TRY(launch_streamk<true>(p, tiles * r.slabs, r.grid, sk, r.slabs, slabs, "gemm_nt_f32_streamk_kernel(units)", stream));
     }
-    GDR_CHECK_LAUNCH("gemm_nt_f32_kernel(split)");
     ProfScope prof_r(PROF_REDUCE, 0.0, stream);
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)(n_tiles * 16)), dim3(256), 0, stream, splitk_ws, S,
-                       (int)first_tile, g.tiles_n, M, N, C, ldc, needs_bias ? bias : nullptr,
-                       needs_res ? residual : nullptr, ldr, g.act, m_dev);
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)(tiles * 16)), dim3(256), 0, stream, slabs, r.slabs, 0, g.tiles_n, M, N,
+                       C, ldc, g.has_bias ? bias : nullptr, g.has_residual ? residual : nullptr, ldr, g.act, m_dev);
     GDR_CHECK_LAUNCH("splitk_reduce_kernel");
     return GDR_OK;
-  };
-  if (tiles < 192 && M <= 1536 && nk >= 4 && K % BK == 0) {
-    // few rows (decode: M = batch*beams): 64x64 tiles (gemm_small.hip), split along K only as far as still needed.
-    // With more rows (a 64-query encoder batch) the 128x128 core with split-K measured 5 % faster.
-    const int rc = launch_linear_f32_small(A, lda, W, ldw, C, ldc, M, N, K, needs_bias, needs_res, g.act, bias, residual, ldr,
-                                           splitk_ws, splitk_ws_bytes, stream, m_dev, nullptr, nullptr, sk ? sk->live : nullptr);
-    if (rc <= 0) return rc;
-  }
-  if (splitk_ws && K % BK == 0 && tiles < 0x7fffffff / 64) {
-    if (tiles < 192 && nk >= 4) {
-      // (a) the grid cannot fill the chip (decode: M = batch*beams rows): split every tile along K
-      const int S = linear_f32_splitk_slabs(tiles, nk, splitk_ws_bytes);
-      if (S >= 2) {
-        // A packed batch (device-side row count, live rows known to the host as a hint) whose LIVE (tile, chunk) units number
-        // between one and two per CU: one workgroup per unit leaves every CU waiting for those that got two (a 64-query
-        // encoder pass, N = 768: 78 live tiles x 4 chunks = 312 workgroups on 256 CUs, 94 us for K = 3072).  The stream-K
-        // kernel on 256 workgroups deals the same units by K-step ranges instead — same chunks, same k order inside a chunk,
-        // same slabs, same reduction: bit-identical — and the busiest CU runs ~1.2 units' worth instead of 2.
-        const int chunk_steps = (nk + S - 1) / S;
-        const int S2 = (nk + chunk_steps - 1) / chunk_steps;
-        // Taken for every packed batch of this size class: the live row count is on the device (a host copy would cost a
-        // synchronisation), and the kernel is right for any count — up to 256 live units each gets its own workgroup like
-        // in the one-unit-per-workgroup form, above that they are dealt by ranges.  With the host's hint (the bench) a
-        // launch whose units all fit one per CU keeps the plain form.
-        const int64_t units_hint = m_dev && prof_rows >= 0 ? ((prof_rows + BM - 1) / BM) * g.tiles_n * S2 : -1;
-        const size_t need = STREAMK_BYTES + (size_t)tiles * S2 * tile_bytes;
-        if (sk && m_dev && sk->part == splitk_ws && nk % chunk_steps == 0 && tiles * S2 > 256 && (units_hint < 0 || units_hint > 256) &&
-            need <= splitk_ws_bytes && streamk_fits(M, lda, N, ldw)) {
-          if (int rc_ = streamk_poll_error()) return rc_;
-          float* slabs = reinterpret_cast<float*>(reinterpret_cast<char*>(splitk_ws) + STREAMK_BYTES);
-          GemmArgs p = g;
-          p.has_bias = 0, p.has_residual = 0, p.act = ACT_NONE;
-          p.ksplit = 1 /* supertile height, unused at these widths */, p.kchunk = chunk_steps * BK, p.tile_base = 0;
-          const StreamKArgs ska{sk->part, sk->flag, ++sk->epoch, streamk_err_word(), S2, slabs};
-          {
-            ProfScope prof(PROF_LINEAR, flops, stream);
-            hipLaunchKernelGGL(gemm_nt_f32_streamk_kernel<true>, dim3(256), dim3(GEMM_THREADS), 0, stream, p, (int)(tiles * S2), ska);
-          }
-          GDR_CHECK_LAUNCH("gemm_nt_f32_streamk_kernel(units)");
-          ProfScope prof_r(PROF_REDUCE, 0.0, stream);
-          hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)(tiles * 16)), dim3(256), 0, stream, slabs, S2, 0, g.tiles_n, M, N,
-                             C, ldc, needs_bias ? bias : nullptr, needs_res ? residual : nullptr, ldr, g.act, m_dev);
-          GDR_CHECK_LAUNCH("splitk_reduce_kernel");
-          return GDR_OK;
-        }
-        return split_launch(0, tiles, S);
-      }
-    }
   }
   ProfScope prof(PROF_LINEAR, flops, stream);
-  if (sk && streamk_mid_wanted(tiles) && K % BK == 0 && streamk_fits(M, lda, N, ldw)) {
-    g.ksplit = g.tiles_n >= 12 ? 8 : 1;
-    if (int rc_ = streamk_poll_error()) return rc_;
-      const StreamKArgs ska{sk->part, sk->flag, ++sk->epoch, streamk_err_word()};
-    hipLaunchKernelGGL(gemm_nt_f32_streamk_kernel<false>, dim3(256), dim3(GEMM_THREADS), 0, stream, g, (int)tiles, ska);
-    GDR_CHECK_LAUNCH("gemm_nt_f32_streamk_kernel(256)");
-    return GDR_OK;
-  }
-  if (tiles > SLOTS && tiles < 0x7fffffff && K % BK == 0) {  // more than one round of tiles: persistent form
-    {
-      // Measured HBM-side fetch per launch (PMC, M = 20480): N=3072 1112 -> 557 MB and N=2304 653 -> 443 MB with 8-panel
-      // supertiles, but N=768 552 -> 684 MB (its 6 column tiles already fit one XCD's L2 next to 10 row panels): wide
-      // outputs only.  Time is unchanged either way (the kernel is MFMA-bound); this is traffic and energy.
-      g.ksplit = g.tiles_n >= 12 ? 8 : 1;
-    }
-    if (sk && streamk_wanted(tiles, K / BK) && streamk_fits(M, lda, N, ldw)) {
-      if (int rc_ = streamk_poll_error()) return rc_;
-      const StreamKArgs ska{sk->part, sk->flag, ++sk->epoch, streamk_err_word()};
-      hipLaunchKernelGGL(gemm_nt_f32_streamk_kernel<false>, dim3((unsigned)SLOTS), dim3(GEMM_THREADS), 0, stream, g, (int)tiles, ska);
-      GDR_CHECK_LAUNCH("gemm_nt_f32_streamk_kernel");
-      return GDR_OK;
-    }
-    hipLaunchKernelGGL(gemm_nt_f32_persistent_kernel, dim3((unsigned)SLOTS), dim3(GEMM_THREADS), 0, stream, g, (int)tiles);
-    GDR_CHECK_LAUNCH("gemm_nt_f32_persistent_kernel");
-    return GDR_OK;
-  }
-  return launch<EPI_LINEAR>(g, tiles_m, stream);
+  return launch_whole_k(g, r, sk, stream);
+}
+
+// Decode-time linear over a device-side row count: the small-tile form if launch_linear_f32_ws would pick it for M_max,
+// else the whole-K forms of launch_linear_f32_dev.
+int launch_linear_f32_ws_dev(const float* A, int64_t lda, const float* W, int64_t ldw, float* C, int64_t ldc, int64_t M_max,
+                             const int64_t* m_dev, int N, int K, int epilogue, const float* bias, const float* residual,
+                             int64_t ldr, float* splitk_ws, size_t splitk_ws_bytes, hipStream_t stream, StreamK* sk) {
+  if (M_max == 0) return GDR_OK;
+  GDR_CHECK_ARG(m_dev, "linear(dev rows): null row count");
+  const LinearRoute r = linear_f32_route({M_max, N, K, lda, ldw, splitk_ws ? splitk_ws_bytes : 0, sk != nullptr, true, -1, false});
+  if (r.form != FORM_SMALL)
+    return launch_linear_f32_dev(A, lda, W, ldw, C, ldc, M_max, m_dev, N, K, epilogue, bias, residual, ldr, -1, stream, sk);
+  GemmArgs g;
+  GDR_TRY(build_linear_args("linear(dev rows)", 4, A, lda, W, ldw, C, ldc, M_max, N, K, epilogue, bias, residual, ldr, m_dev, &g));
+  return launch_linear_f32_small(A, lda, W, ldw, C, ldc, M_max, N, K, g.has_bias, g.has_residual, g.act, bias, residual, ldr, splitk_ws,
+                                 splitk_ws_bytes, stream, m_dev, nullptr, nullptr, sk ? sk->live : nullptr);
 }
 
 // The linear over a device-side row count (ragged batches): rows [0, *m_dev) of A, *m_dev <= M_max.  The grid is sized for
-// M_max and the kernels read the count themselves, so there is no host round trip.  No split-K / small-tile forms (their
-// k order differs: a row's result must not depend on how many rows happen to be live) — callers use this at encoder
-// batch sizes, where the 128x128 grid fills the chip anyway.  prof_rows: the live-row count if the host happens to
-// know it (< 0: unknown, M_max is used) — only the opt-in profiler's flop accounting reads it.
+// M_max and the kernels read the count themselves, so there is no host round trip.  Whole-K forms only (LinearCall.whole_k)
+// — callers use this at encoder batch sizes, where the 128x128 grid fills the chip anyway.  prof_rows: the live-row count
+// if the host happens to know it (< 0: unknown, M_max is used) — the stream-K admission and the opt-in profiler read it.
 int launch_linear_f32_dev(const float* A, int64_t lda, const float* W, int64_t ldw, float* C, int64_t ldc, int64_t M_max,
                           const int64_t* m_dev, int N, int K, int epilogue, const float* bias, const float* residual,
                           int64_t ldr, int64_t prof_rows, hipStream_t stream, StreamK* sk) {
   if (M_max == 0) return GDR_OK;
-  GDR_CHECK_ARG(A && W && C && m_dev, "linear(dev rows): null pointer");
-  GDR_CHECK_ARG(M_max > 0 && N > 0 && K > 0 && K % BK == 0, "linear(dev rows): bad shape M<=%lld N=%d K=%d (K %% 32 == 0)",
-                (long long)M_max, N, K);
-  GDR_CHECK_ARG(lda % 4 == 0 && ldw % 4 == 0 && lda >= K && ldw >= K && ldc >= N, "linear(dev rows): bad leading dimension");
-  GDR_CHECK_ARG(aligned16(A) && aligned16(W), "linear(dev rows): A and W must be 16-byte aligned");
-  GDR_CHECK_ARG(epilogue >= GDR_EPI_NONE && epilogue <= GDR_EPI_BIAS_GELU, "linear(dev rows): unknown epilogue %d", epilogue);
-  const bool needs_bias = epilogue == GDR_EPI_BIAS || epilogue == GDR_EPI_BIAS_RELU ||
-                          epilogue == GDR_EPI_BIAS_RESIDUAL || epilogue == GDR_EPI_BIAS_GELU;
-  const bool needs_res = epilogue == GDR_EPI_RESIDUAL || epilogue == GDR_EPI_BIAS_RESIDUAL;
-  GDR_CHECK_ARG(!needs_bias || bias, "linear(dev rows): epilogue %d needs bias", epilogue);
-  GDR_CHECK_ARG(!needs_res || (residual && ldr >= N), "linear(dev rows): epilogue %d needs residual", epilogue);
-  GemmArgs g{};
-  g.A = A, g.W = W, g.C = C, g.bias = bias, g.residual = residual;
-  g.lda = lda, g.ldw = ldw, g.ldc = ldc, g.ldr = ldr;
-  g.M = M_max, g.N = N, g.K = K, g.m_dev = m_dev;
-  g.tiles_n = (N + BN - 1) / BN;
-  g.has_bias = needs_bias, g.has_residual = needs_res;
-  g.act = (epilogue == GDR_EPI_RELU || epilogue == GDR_EPI_BIAS_RELU) ? ACT_RELU
-          : epilogue == GDR_EPI_BIAS_GELU                             ? ACT_GELU
-                                                                      : ACT_NONE;
-  const int64_t tiles_m = (M_max + BM - 1) / BM, tiles = tiles_m * g.tiles_n;
-  GDR_CHECK_ARG(tiles < 0x7fffffff, "linear(dev rows): grid too large");
+  GDR_CHECK_ARG(m_dev, "linear(dev rows): null row count");
+  GemmArgs g;
+  GDR_TRY(build_linear_args("linear(dev rows)", 4, A, lda, W, ldw, C, ldc, M_max, N, K, epilogue, bias, residual, ldr, m_dev, &g));
+  GDR_CHECK_ARG(M_max > 0 && K % BK == 0, "linear(dev rows): bad shape M<=%lld N=%d K=%d (K %% 32 == 0)", (long long)M_max, N, K);
+  GDR_CHECK_ARG(((M_max + BM - 1) / BM) * g.tiles_n < 0x7fffffff, "linear(dev rows): grid too large");
   ProfScope prof(PROF_LINEAR, 2.0 * (double)(prof_rows >= 0 ? prof_rows : M_max) * (double)N * (double)K, stream);
-  const int64_t tiles_live = prof_rows >= 0 ? ((prof_rows + BM - 1) / BM) * g.tiles_n : tiles;
-  if (sk && tiles > 256 && streamk_mid_wanted(tiles_live) && streamk_fits(M_max, lda, N, ldw)) {
-    g.ksplit = g.tiles_n >= 12 ? 8 : 1;
-    if (int rc_ = streamk_poll_error()) return rc_;
-      const StreamKArgs ska{sk->part, sk->flag, ++sk->epoch, streamk_err_word()};
-    hipLaunchKernelGGL(gemm_nt_f32_streamk_kernel<false>, dim3(256), dim3(GEMM_THREADS), 0, stream, g, (int)tiles, ska);
-    GDR_CHECK_LAUNCH("gemm_nt_f32_streamk_kernel(256, dev rows)");
-    return GDR_OK;
-  }
-  if (tiles > 512) {
-    g.ksplit = g.tiles_n >= 12 ? 8 : 1;  // supertile height, as in launch_linear_f32_ws
-    if (sk && streamk_wanted(tiles_live, K / BK) && streamk_fits(M_max, lda, N, ldw)) {
-      if (int rc_ = streamk_poll_error()) return rc_;
-      const StreamKArgs ska{sk->part, sk->flag, ++sk->epoch, streamk_err_word()};
-      hipLaunchKernelGGL(gemm_nt_f32_streamk_kernel<false>, dim3(512), dim3(GEMM_THREADS), 0, stream, g, (int)tiles, ska);
-      GDR_CHECK_LAUNCH("gemm_nt_f32_streamk_kernel(dev rows)");
-      return GDR_OK;
-    }
-    hipLaunchKernelGGL(gemm_nt_f32_persistent_kernel, dim3(512), dim3(GEMM_THREADS), 0, stream, g, (int)tiles);
-    GDR_CHECK_LAUNCH("gemm_nt_f32_persistent_kernel(dev rows)");
-    return GDR_OK;
-  }
-  return launch<EPI_LINEAR>(g, tiles_m, stream);
+  return launch_whole_k(g, linear_f32_route({M_max, N, K, lda, ldw, 0, sk != nullptr, true, prof_rows, true}), sk, stream);
 }
 
 // bf16 operands (fp32 accumulate, fp32 output): the precision mode of config C5.  Same tiling as the fp32 linears on
@@ -1466,38 +1249,14 @@ int launch_linear_bf16(const void* A, int64_t lda, const void* W, int64_t ldw, f
                        int K, int epilogue, const float* bias, const float* residual, int64_t ldr, hipStream_t stream,
                        const int64_t* m_dev) {
   if (M == 0) return GDR_OK;
-  GDR_CHECK_ARG(A && W && C, "linear_bf16: null pointer");
-  GDR_CHECK_ARG(M >= 0 && N > 0 && K > 0, "linear_bf16: bad shape M=%lld N=%d K=%d", (long long)M, N, K);
-  GDR_CHECK_ARG(K % 8 == 0 && lda % 8 == 0 && ldw % 8 == 0, "linear_bf16: K, lda, ldw must be multiples of 8");
-  GDR_CHECK_ARG(lda >= K && ldw >= K && ldc >= N, "linear_bf16: leading dimension smaller than the row");
-  GDR_CHECK_ARG(aligned16(A) && aligned16(W), "linear_bf16: A and W must be 16-byte aligned");
-  if (epilogue < GDR_EPI_NONE || epilogue > GDR_EPI_BIAS_GELU) {
-    set_error("linear_bf16: unknown epilogue %d", epilogue);
-    return GDR_EINVAL;
-  }
-  const bool needs_bias = epilogue == GDR_EPI_BIAS || epilogue == GDR_EPI_BIAS_RELU ||
-                          epilogue == GDR_EPI_BIAS_RESIDUAL || epilogue == GDR_EPI_BIAS_GELU;
-  const bool needs_res = epilogue == GDR_EPI_RESIDUAL || epilogue == GDR_EPI_BIAS_RESIDUAL;
-  GDR_CHECK_ARG(!needs_bias || bias, "linear_bf16: epilogue %d needs bias", epilogue);
-  GDR_CHECK_ARG(!needs_res || (residual && ldr >= N), "linear_bf16: epilogue %d needs residual", epilogue);
-  if (M == 0) return GDR_OK;
-  GemmArgs g{};
-  g.A = static_cast<const float*>(A), g.W = static_cast<const float*>(W);  // opaque: the kernel addresses operands in bytes
-  g.C = C, g.bias = bias, g.residual = residual;
-  g.lda = lda, g.ldw = ldw, g.ldc = ldc, g.ldr = ldr;
-  g.M = M, g.N = N, g.K = K;
-  g.tiles_n = (N + BN - 1) / BN;
-  g.has_bias = needs_bias, g.has_residual = needs_res;
-  g.act = (epilogue == GDR_EPI_RELU || epilogue == GDR_EPI_BIAS_RELU) ? ACT_RELU
-          : epilogue == GDR_EPI_BIAS_GELU                             ? ACT_GELU
-                                                                      : ACT_NONE;
+  GemmArgs g;
+  GDR_TRY(build_linear_args("linear_bf16", 8, A, lda, W, ldw, C, ldc, M, N, K, epilogue, bias, residual, ldr, m_dev, &g));
   ProfScope prof(PROF_LINEAR, 2.0 * (double)M * (double)N * (double)K, stream);
   {  // the LDS-DMA kernel (gemm_bf16.hip) serves K % 64 == 0 with 16-byte aligned operands; other shapes the generic core
-    const int rc = launch_linear_bf16_glds(A, lda, W, ldw, C, ldc, M, N, K, needs_bias, needs_res, g.act, bias, residual, ldr, 0,
+    const int rc = launch_linear_bf16_glds(A, lda, W, ldw, C, ldc, M, N, K, g.has_bias, g.has_residual, g.act, bias, residual, ldr, 0,
                                            stream, m_dev);
     if (rc <= 0) return rc;
   }
-  g.m_dev = m_dev;
   return launch<EPI_LINEAR, true>(g, (M + BM - 1) / BM, stream);
 }
 
@@ -1549,46 +1308,41 @@ extern "C" int gdr_linear_f32_splitk(const float* A, int64_t lda, const float* W
   hipStream_t st = static_cast<hipStream_t>(stream);
   // a workspace that can hold the stream-K hand-off scratch also serves the balanced forms of the big grids (the same
   // region: a launch uses it for split-K slabs or for the hand-off, never both); its 2 KB of flags are zeroed per call
-  const int64_t tiles = ((M + BM - 1) / BM) * (int64_t)((N + BN - 1) / BN);
-  if (workspace && workspace_bytes >= STREAMK_BYTES && K > 0 && K % BK == 0 && M > 0 && N > 0 && lda >= K && ldw >= K &&
-      (streamk_mid_wanted(tiles) || (tiles > 512 && streamk_wanted(tiles, K / BK))) && streamk_fits(M, lda, N, ldw)) {
-    StreamK sk{static_cast<float*>(workspace),
-               reinterpret_cast<int32_t*>(static_cast<char*>(workspace) + STREAMK_PART_BYTES), 0};
-    if (hipMemsetAsync(sk.flag, 0, 512 * sizeof(int32_t), st) != hipSuccess) {
-      set_error("linear: memset of the stream-K flags failed");
-      return GDR_EHIP;
+  if (workspace && workspace_bytes >= STREAMK_BYTES && lda >= K && ldw >= K) {
+    const LinearForm form = linear_f32_route({M, N, K, lda, ldw, workspace_bytes, true, false, -1, false}).form;
+    if (form == FORM_STREAMK_256 || form == FORM_STREAMK_TAIL) {
+      StreamK sk{static_cast<float*>(workspace),
+                 reinterpret_cast<int32_t*>(static_cast<char*>(workspace) + STREAMK_PART_BYTES), 0};
+      if (hipMemsetAsync(sk.flag, 0, 512 * sizeof(int32_t), st) != hipSuccess) {
+        set_error("linear: memset of the stream-K flags failed");
+        return GDR_EHIP;
+      }
+      return launch_linear_f32_ws(A, lda, W, ldw, C, ldc, M, N, K, epilogue, bias, residual, ldr, static_cast<float*>(workspace),
+                                  workspace_bytes, st, &sk);
     }
-    return launch_linear_f32_ws(A, lda, W, ldw, C, ldc, M, N, K, epilogue, bias, residual, ldr, static_cast<float*>(workspace),
-                                workspace_bytes, st, &sk);
   }
   return launch_linear_f32_ws(A, lda, W, ldw, C, ldc, M, N, K, epilogue, bias, residual, ldr, static_cast<float*>(workspace),
                               workspace_bytes, st);
 }
 
-// Which kernel form gdr_linear_f32 (workspace_bytes == 0) / gdr_linear_f32_splitk give a dense launch: the decisions of
-// gdr_linear_f32_splitk and launch_linear_f32_ws above, in their order, without the launches.  Must mirror the order of
-// those branches; every threshold and slab count (streamk_mid_wanted, streamk_wanted, linear_f32_small_splits,
-// linear_f32_splitk_slabs) is the launchers' own routine.  A workspace is "given" when workspace_bytes > 0: a non-NULL
-// workspace of 0 bytes launches like NULL (no slab fits, no stream-K scratch fits).
+// Which kernel form gdr_linear_f32 (workspace_bytes == 0) / gdr_linear_f32_splitk give a dense launch of contiguous
+// operands: linear_f32_route's answer for it.  A workspace is "given" when workspace_bytes > 0: a non-NULL workspace of
+// 0 bytes launches like NULL (no slab fits, no stream-K scratch fits).
 extern "C" int gdr_linear_f32_form(int64_t M, int N, int K, size_t workspace_bytes) {
   using namespace gdr;
-  if (M <= 0 || N <= 0 || K <= 0 || K % 4 != 0) return 0;
-  const bool has_ws = workspace_bytes > 0;
-  const int64_t tiles = ((M + BM - 1) / BM) * (int64_t)((N + BN - 1) / BN);
-  const int nk = K / BK;
-  const bool kfull = K % BK == 0;
-  const bool sk = has_ws && workspace_bytes >= STREAMK_BYTES && kfull &&
-                  (streamk_mid_wanted(tiles) || (tiles > 512 && streamk_wanted(tiles, nk))) && streamk_fits(M, K, N, K);
-  if (tiles < 192 && M <= 1536 && nk >= 4 && kfull) {
-    const int S = linear_f32_small_splits(M, N, K, has_ws, workspace_bytes);
-    if (S) return S > 1 ? GDR_F32_FORM_SMALL_SPLITK : GDR_F32_FORM_SMALL;
+  const LinearRoute r = linear_f32_route({M, N, K, K, K, workspace_bytes, workspace_bytes >= STREAMK_BYTES, false, -1, false});
+  switch (r.form) {
+    case FORM_NONE: return 0;
+    case FORM_TILES: return GDR_F32_FORM_TILES;
+    case FORM_PERSISTENT: return GDR_F32_FORM_PERSISTENT;
+    case FORM_SMALL: return r.slabs > 1 ? GDR_F32_FORM_SMALL_SPLITK : GDR_F32_FORM_SMALL;
+    case FORM_SPLITK:
+    case FORM_STREAMK_UNITS:  // needs a device-side row count (encoder-internal): not reached from a dense call
+      return GDR_F32_FORM_SPLITK;
+    case FORM_STREAMK_256: return GDR_F32_FORM_STREAMK_256;
+    case FORM_STREAMK_TAIL: return GDR_F32_FORM_STREAMK_TAIL;
   }
-  if (has_ws && kfull && tiles < 0x7fffffff / 64 && tiles < 192 && nk >= 4) {
-    if (linear_f32_splitk_slabs(tiles, nk, workspace_bytes) >= 2) return GDR_F32_FORM_SPLITK;  // (the stream-K form over split-K units needs a device-side row count: encoder-internal)
-  }
-  if (sk && streamk_mid_wanted(tiles)) return GDR_F32_FORM_STREAMK_256;
-  if (tiles > 512 && tiles < 0x7fffffff && kfull) return sk && streamk_wanted(tiles, nk) ? GDR_F32_FORM_STREAMK_TAIL : GDR_F32_FORM_PERSISTENT;
-  return GDR_F32_FORM_TILES;
+  return 0;
 }
 
 extern "C" int gdr_linear_bf16(const void* A, int64_t lda, const void* W, int64_t ldw, float* C, int64_t ldc, int64_t M,

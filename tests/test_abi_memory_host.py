@@ -84,6 +84,27 @@ def test_linear_f32_leaves_the_stream_k_forms_when_a_crosses_2_31_elements():
     assert l.gdr_linear_f32_form(700_001, 3072, 320, streamk_bytes) == tail and l.gdr_linear_f32_form(700_001, 3072, 64, streamk_bytes) == persistent
 
 
+def test_linear_f32_routing_reproduces_the_recorded_table():
+    """gdr_linear_f32_form over the grid of tests/golden/make_golden_linear_forms.py (tile counts around 192 / 256 / 512 and
+    multiples of 512, M around 1536, K / 32 around 4, K tails, operands around 2^31 elements, seven workspace sizes) answers
+    exactly what the library answered when the table was recorded: an edit that is meant to leave the routing alone leaves
+    every one of the 2 835 answers alone.  The stream-K knobs move thresholds, so the test refuses to run with one set."""
+    import pytest
+    from conftest import golden
+    from gdr_amd import _ffi
+    knobs = [k for k in ("GDR_GEMM_STREAMK", "GDR_GEMM_STREAMK_MID") if k in os.environ]
+    if knobs:
+        pytest.fail(f"{knobs} set in the environment: the recorded routing table holds for the default thresholds only; unset and rerun")
+    table = golden("g20_linear_f32_forms")["cases"]
+    assert table.shape[1] == 5 and table.shape[0] >= 2000
+    l = _ffi.lib()
+    codes = {getattr(_ffi, n) for n in dir(_ffi) if n.startswith("F32_FORM_")}
+    assert len(codes) == 7 and set(table[:, 4].tolist()) == codes | {0}, "every form code and 0 occur in the table"
+    wrong = [(m, n, k, ws, want, got) for m, n, k, ws, want in table.tolist()
+             for got in [l.gdr_linear_f32_form(m, n, k, ws)] if got != want]
+    assert not wrong, f"{len(wrong)} of {len(table)} shapes route differently; (M, N, K, workspace, recorded, now): {wrong[:10]}"
+
+
 def test_sim_topk_refuses_an_idx_offset_that_leaves_int32_before_any_launch():
     """ids are row + idx_offset in int32: idx_offset + N > 2^31 - 1 is GDR_EINVAL with a message, in all three entry points,
     before anything is launched (the pointers below are never dereferenced)."""
