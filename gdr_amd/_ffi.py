@@ -13,6 +13,7 @@ GDR_OK, GDR_EINVAL, GDR_ENOSPC, GDR_EHIP = 0, -1, -2, -3
 ABI_VERSION = 9                  # what this binding was written against (gdr_abi_version(), csrc/common.hip)
 RERANK_POSITIONS = 1
 RERANK_CHUNKED = 2
+RERANK_ROW_QUERIES = 8           # q holds a row per (query, segment); 4 stays an unknown flag (tests/test_rerank_long_host.py pins it)
 SIM_EXHAUSTIVE = 1
 SIM_NO_STREAM = 2
 SIM_LIVE_MASK = 4                # the workspace starts with a live-row bitmap (ops.LiveRows): rank the live rows only

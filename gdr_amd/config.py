@@ -113,6 +113,30 @@ _ONLY = [
 _PLAIN_PAIR = ("adaptor_decode", "adaptor_efficient")   # both 0: the adaptor-free model (GDRConfig.has_adaptor is False)
 
 
+def stage2_query_form(args, sharded=False):
+    """Which vector a decoded cluster's candidates are scored against in stage 2 (main_models.py:1464-1594): ("encoder", None) —
+    the query's encoder CLS row, the shipped setting; ("special", None) / ("avg", None) — per hypothesis, the decoder's last hidden
+    state at the EOS position / its mean over the hypothesis' tokens (--use_query_embed_encoder 0 with
+    --use_query_embed_decoder_special 1 / --use_query_embed_decoder_avg 1; `special` wins when both are set, as the reference's
+    later assignment does).  (None, why) for a combination that is not implemented.  A namespace without the flags reads the
+    reference's defaults (1, 0, 0)."""
+    enc = getattr(args, "use_query_embed_encoder", 1)
+    special = getattr(args, "use_query_embed_decoder_special", 0)
+    avg = getattr(args, "use_query_embed_decoder_avg", 0)
+    if enc and (special or avg):
+        return None, ("--use_query_embed_encoder 1 together with --use_query_embed_decoder_special / --use_query_embed_decoder_avg "
+                      "fuses the encoder and decoder vectors through fusion_layer (main_models.py:1553-1562), which this build does "
+                      "not implement; pass --use_query_embed_encoder 0 for the decoder-side queries alone")
+    if not enc and not (special or avg):
+        return None, ("--use_query_embed_encoder 0 without --use_query_embed_decoder_special 1 or --use_query_embed_decoder_avg 1 "
+                      "leaves stage 2 without a query vector (the reference fails at main_models.py:1587)")
+    form = "encoder" if enc else ("special" if special else "avg")
+    if sharded and form != "encoder":
+        return None, (f"the decoder-side stage-2 queries (--use_query_embed_decoder_{form}) are not implemented for the sharded "
+                      "two-stage path (--n_gpu > 1): its exchange row carries one query vector per query, not one per hypothesis")
+    return form, None
+
+
 def unsupported_variant(args):
     """None when `args` selects the model variant the HIP path implements, else one sentence naming the first flag that
     does not (reference: main_models.py:748-780 forwards these into T5Config; modeling_t5.py:1578-1640 branches on them)."""
@@ -123,6 +147,9 @@ def unsupported_variant(args):
         if hasattr(args, name) and getattr(args, name) != only:
             return (f"--{name} {getattr(args, name)!r} selects a reference model variant this build does not implement "
                     f"(implemented: {only!r}; {what})")
+    why = stage2_query_form(args)[1]
+    if why:
+        return why
     if getattr(args, "model_info", "base") in ("3b", "11b"):
         return (f"--model_info {args.model_info}: the reference sets no sizes for 3b / 11b (main.py:422-442 covers small / base / "
                 "large only, so args.d_kv is undefined at main_models.py:757); refusing to run a base-sized model under that name")

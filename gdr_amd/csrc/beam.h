@@ -64,6 +64,7 @@ size_t beam_layout(const BeamDims& bd, char* base, BeamBufs* bb);
 
 int check_beam_dims(const BeamDims& bd, int max_length);
 int check_greedy_dims(const BeamDims& bd, int max_length);
+int check_forced_dims(const BeamDims& bd, int max_length);
 
 // num_beams >= 2: once per call; after bb.logits holds the logits of position `pos`; after the last step
 int beam_begin(const BeamBufs& bb, const BeamDims& bd, hipStream_t stream, bool dedup0 = false);
@@ -74,5 +75,12 @@ int beam_end(const BeamBufs& bb, const BeamDims& bd, int max_length, int cur, in
 // num_beams = 1: out_ids / out_len are written as the steps go, there is no end
 int greedy_begin(const BeamBufs& bb, const BeamDims& bd, int64_t* out_ids, int32_t* out_len, double* out_scores, hipStream_t stream);
 int greedy_step(const BeamBufs& bb, const BeamDims& bd, int pos, int cur, int64_t* out_ids, int32_t* out_len, hipStream_t stream);
+// given tokens (teacher forcing, gdr_t5_generate's score mode): `ids` [rows][maxlen] are read, never written.  Once per call; after
+// bb.logits holds the logits of position `pos` (none behind the last position, pos = maxlen - 1) and `hl` [rows][d] its last hidden
+// states, which go into `planes` [maxlen + 2][rows][d] when that is given; after the last position
+int forced_begin(const BeamBufs& bb, const BeamDims& bd, const int64_t* ids, hipStream_t stream);
+int forced_step(const BeamBufs& bb, const BeamDims& bd, int pos, const int64_t* ids, const float* hl, int d, float* planes,
+                hipStream_t stream);
+int forced_end(const BeamBufs& bb, const BeamDims& bd, const int64_t* ids, int d, float* planes, double* out_scores, hipStream_t stream);
 
 }  // namespace gdr

@@ -716,6 +716,102 @@ __global__ __launch_bounds__(256) void greedy_step_kernel(BeamBufs bb, BeamDims 
   }
 }
 
+// ---- given tokens: gdr_t5_generate's score mode (out_len == NULL) ----------------------------------------------------------------
+// Nothing is searched: row r of `ids` [rows][maxlen] is START, tokens, then EOS, then PAD, as beam_finalize_kernel lays a hypothesis
+// out, and the call reports the score the search gives that hypothesis.  Every row keeps its own cache slots (the ancestor of row r
+// at position p is row r), the step's input token is the row's own, and what the select does in a search is one wave per row here:
+// the log-softmax of the row's V + 1 live logits — beam_topk_kernel's / beam_norm_kernel's lane assignment and order, so the
+// log-probabilities get the same bits — read off at the forced token and added to the row's sum in fp32, as the search adds it to
+// beam_scores.  maxlen <= MAXLEN_CAP < 64: lane t of the wave looks at the row's token t.
+__device__ __forceinline__ int forced_first_eos(const int64_t* __restrict__ row, int ml, int lane) {
+  const unsigned long long m = __ballot(lane >= 1 && lane < ml && row[lane] == EOS_ID);
+  return m ? (int)__ffsll((long long)m) - 1 : ml;  // ml: the row never ends
+}
+
+__global__ void forced_init_kernel(BeamBufs bb, BeamDims bd, const int64_t* __restrict__ ids) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r < bd.B * bd.R) {
+    bb.beam_scores[r] = 0.f;
+    bb.cur_tok[r] = ids[(size_t)r * bd.maxlen];
+    bb.kv_rows[r] = r;  // step 0: stride 1, position 0
+  }
+  if (r == 0) *bb.n_done = 0, *bb.live = 1;
+}
+
+// After position `pos` of every row.  planes (optional) [maxlen + 2][rows][d]: plane t < maxlen the last hidden state of position t
+// (zero behind the row's first EOS), plane maxlen the one AT the first EOS (zero for a row without), plane maxlen + 1 the sum over
+// t = 0 and every t >= 1 with ids[t] != PAD, ascending in fp32 (forced_finish_kernel divides it by the count).
+__global__ __launch_bounds__(256) void forced_step_kernel(BeamBufs bb, BeamDims bd, int pos, const int64_t* __restrict__ ids,
+                                                          const float* __restrict__ hl, int d4, float* __restrict__ planes) {
+  const int r = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const int rows = bd.B * bd.R, ml = bd.maxlen, V = bd.V, V1 = V + 1;
+  if (r >= rows) return;
+  const int64_t* row = ids + (size_t)r * ml;
+  const int eos = forced_first_eos(row, ml, lane);
+  if (pos + 1 < ml && pos < eos) {  // the token behind this position counts: up to and including the first EOS
+    const float* lg = bb.logits + (size_t)r * V1;
+    float mx = -INFINITY;
+    for (int c = lane; c < V1; c += 64) mx = fmaxf(mx, lg[c]);
+    mx = wave_max(mx);
+    float sm = 0.f;
+    for (int c = lane; c < V1; c += 64) sm += expf(lg[c] - mx);
+    sm = wave_sum(sm);
+    // column V is EOS' alone: the first digit token of the NEXT position, pos * V + 2 + V, is no live column of this one.  A token
+    // that is no live column of this position holds the masked logit (select_valid_embedding: exactly -1e9)
+    const int64_t tok = row[pos + 1], digit = tok - ((int64_t)pos * V + 2);
+    const int64_t c = tok == EOS_ID ? V : ((digit >= 0 && digit < V) ? digit : -1);
+    const float lgt = c >= 0 ? lg[c] : -1e9f;
+    const float logp = (lgt - mx) - logf(sm);
+    if (lane == 0) bb.beam_scores[r] = logp + bb.beam_scores[r];
+  }
+  if (planes) {
+    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+    const float4* h = reinterpret_cast<const float4*>(hl) + (size_t)r * d4;
+    float4* p4 = reinterpret_cast<float4*>(planes);
+    float4* tr = p4 + ((size_t)pos * rows + r) * d4;
+    float4* at_eos = p4 + ((size_t)ml * rows + r) * d4;
+    float4* mean = p4 + ((size_t)(ml + 1) * rows + r) * d4;
+    const bool counted = pos == 0 || row[pos] != PAD_ID;
+    for (int c = lane; c < d4; c += 64) {
+      const float4 v = h[c];
+      tr[c] = pos <= eos ? v : zero;
+      if (pos == 0) {
+        at_eos[c] = zero;  // eos >= 1: the step that reaches it writes over this
+        mean[c] = v;
+      } else {
+        if (pos == eos) at_eos[c] = v;
+        if (counted) {
+          const float4 m = mean[c];
+          mean[c] = make_float4(m.x + v.x, m.y + v.y, m.z + v.z, m.w + v.w);
+        }
+      }
+    }
+  }
+  if (pos + 1 < ml) {  // the next position's input token and key list: the row's own slots of positions 0 .. pos + 1
+    const int stride = pos + 2;
+    if (lane == 0) bb.cur_tok[r] = row[pos + 1];
+    if (lane < stride) bb.kv_rows[(size_t)r * stride + lane] = lane * rows + r;
+  }
+}
+
+// score = sum / len^length_penalty in double (hyp_add, beam_finalize_kernel): len = the EOS position, maxlen for a row without
+__global__ __launch_bounds__(256) void forced_finish_kernel(BeamBufs bb, BeamDims bd, const int64_t* __restrict__ ids, int d4,
+                                                            float* __restrict__ planes, double* __restrict__ out_scores) {
+  const int r = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const int rows = bd.B * bd.R, ml = bd.maxlen;
+  if (r >= rows) return;
+  const int64_t* row = ids + (size_t)r * ml;
+  const int eos = forced_first_eos(row, ml, lane);
+  if (lane == 0) out_scores[r] = (double)bb.beam_scores[r] / pow((double)eos, bd.lp);
+  if (!planes) return;
+  const float n = (float)(1 + __popcll(__ballot(lane >= 1 && lane < ml && row[lane] != PAD_ID)));
+  float4* mean = reinterpret_cast<float4*>(planes) + ((size_t)(ml + 1) * rows + r) * d4;
+  for (int c = lane; c < d4; c += 64) {
+    const float4 m = mean[c];
+    mean[c] = make_float4(m.x / n, m.y / n, m.z / n, m.w / n);
+  }
+}
+
 // ------------------------------------------------------------------------------------------ driver pieces
 // dynamic LDS of the two kernels that hold a query's hypothesis heap
 static size_t beam_update_lds(const BeamDims& bd) {
@@ -753,6 +849,44 @@ int check_greedy_dims(const BeamDims& bd, int max_length) {
   GDR_CHECK_ARG(max_length >= 2 && max_length <= MAXLEN_CAP, "generate: max_length=%d must be in [2,%d]", max_length, MAXLEN_CAP);
   GDR_CHECK_ARG(bd.V >= 1 && bd.Vd >= bd.V * (max_length - 1) + 2, "generate: decode vocab %d too small for V=%d, max_length=%d",
                 bd.Vd, bd.V, max_length);
+  return GDR_OK;
+}
+
+// The score mode of gdr_t5_generate: any 1 .. GDR_MAX_BEAMS rows per query — no candidate list and no hypothesis heap, so neither the
+// select's nor the LDS limit applies.  Every row is reported: num_return_sequences = num_beams.
+int check_forced_dims(const BeamDims& bd, int max_length) {
+  GDR_CHECK_ARG(bd.B > 0, "generate(score mode, out_len=NULL): B=%d must be positive", bd.B);
+  GDR_CHECK_ARG(bd.R >= 1 && bd.R <= GDR_MAX_BEAMS, "generate(score mode, out_len=NULL): num_beams=%d rows per query must be in [1,%d]", bd.R,
+                GDR_MAX_BEAMS);
+  GDR_CHECK_ARG(bd.nret == bd.R, "generate(score mode, out_len=NULL): num_return_sequences=%d must equal num_beams=%d (every given row is scored)",
+                bd.nret, bd.R);
+  GDR_CHECK_ARG(max_length >= 2 && max_length <= MAXLEN_CAP, "generate(score mode, out_len=NULL): max_length=%d must be in [2,%d]", max_length,
+                MAXLEN_CAP);
+  GDR_CHECK_ARG(bd.V >= 1 && bd.Vd >= bd.V * (max_length - 1) + 2, "generate(score mode, out_len=NULL): decode vocab %d too small for V=%d, max_length=%d",
+                bd.Vd, bd.V, max_length);
+  GDR_CHECK_ARG(bd.lp > 0.0, "generate(score mode, out_len=NULL): length_penalty must be > 0");
+  return GDR_OK;
+}
+
+int forced_begin(const BeamBufs& bb, const BeamDims& bd, const int64_t* ids, hipStream_t stream) {
+  const int rows = bd.B * bd.R;
+  hipLaunchKernelGGL(forced_init_kernel, dim3((rows + 255) / 256), dim3(256), 0, stream, bb, bd, ids);
+  GDR_CHECK_LAUNCH("forced_init_kernel");
+  return GDR_OK;
+}
+
+int forced_step(const BeamBufs& bb, const BeamDims& bd, int pos, const int64_t* ids, const float* hl, int d, float* planes,
+                hipStream_t stream) {
+  const int rows = bd.B * bd.R;
+  hipLaunchKernelGGL(forced_step_kernel, dim3((rows + 3) / 4), dim3(256), 0, stream, bb, bd, pos, ids, hl, d / 4, planes);
+  GDR_CHECK_LAUNCH("forced_step_kernel");
+  return GDR_OK;
+}
+
+int forced_end(const BeamBufs& bb, const BeamDims& bd, const int64_t* ids, int d, float* planes, double* out_scores, hipStream_t stream) {
+  const int rows = bd.B * bd.R;
+  hipLaunchKernelGGL(forced_finish_kernel, dim3((rows + 3) / 4), dim3(256), 0, stream, bb, bd, ids, d / 4, planes, out_scores);
+  GDR_CHECK_LAUNCH("forced_finish_kernel");
   return GDR_OK;
 }
 

@@ -614,7 +614,7 @@ struct GenCall {
   size_t workspace_bytes;
   bool bf16;
   hipStream_t stream;
-  bool greedy, plain;  // set by validate() / lay_out()
+  bool forced, greedy, plain;  // set by validate() / lay_out()
   BeamDims bd;
   GenBufs g;
   int d, H, dk, inner, rows, V1, aH, ahd, aff;
@@ -630,11 +630,21 @@ struct GenCall {
   int cur;  // index of the current seq / node buffer: flips every step
 
   int validate(double length_penalty, int num_return_sequences, const GdrTrie* trie) {
-    GDR_CHECK_ARG(w && enc_hidden && enc_mask && out_ids && out_len && out_scores && workspace, "generate: null pointer");
+    // out_len == NULL selects the score mode: out_ids holds GIVEN rows (read, never written), out_scores receives the score the search
+    // reports for each of them and step_scores, when given, the decoder's last hidden states (forced_step_kernel's planes).  There is
+    // nothing to search or constrain, and one row's tokens say nothing about a prefix-table node
+    GDR_CHECK_ARG(w && enc_hidden && enc_mask && out_ids && out_scores && workspace, "generate: null pointer");
+    forced = out_len == nullptr;
+    if (forced) {
+      GDR_CHECK_ARG(!trie, "generate(score mode, out_len=NULL): trie must be NULL (the rows are given, nothing is constrained)");
+      GDR_CHECK_ARG(!ptab, "generate(score mode, out_len=NULL): prefix_table must be NULL");
+      GDR_CHECK_ARG(!step_tokens,
+                    "generate(score mode, out_len=NULL): step_tokens must be NULL (step_scores receives the hidden states; there is no top-2R trace)");
+    }
     const GdrT5Dims& dm = w->dims;
     // num_beams = 1 is the reference's non-beam branch (greedy_step_kernel): one sequence per query, and neither the trie constraint nor
     // the top-2R trace, which exist for the beam search only — refused here, before anything behind those pointers is looked at
-    greedy = num_beams == 1;
+    greedy = !forced && num_beams == 1;
     if (greedy) {
       GDR_CHECK_ARG(num_return_sequences == 1, "generate: num_return_sequences=%d must be 1 at num_beams=1 (greedy decoding gives one sequence per query)",
                     num_return_sequences);
@@ -679,7 +689,7 @@ struct GenCall {
     bd = BeamDims{B, num_beams, w->out_vocab, dm.vocab_size, max_length, num_return_sequences, length_penalty,
                   trie ? trie->child : (ptab ? ptab->child : nullptr), trie ? trie->eos_ok : nullptr,
                   trie ? trie->n_nodes : (ptab ? ptab->n_nodes : 0)};
-    GDR_TRY(greedy ? check_greedy_dims(bd, max_length) : check_beam_dims(bd, max_length));
+    GDR_TRY(forced ? check_forced_dims(bd, max_length) : greedy ? check_greedy_dims(bd, max_length) : check_beam_dims(bd, max_length));
     GDR_CHECK_ARG(L >= 1 && L <= T5_MAX_LEN, "generate: L=%d must be in [1,%d]", L, T5_MAX_LEN);
     GDR_CHECK_ARG(max_length <= w->max_out_len, "generate: max_length=%d > max_output_length=%d of the head", max_length,
                   w->max_out_len);
@@ -718,9 +728,11 @@ struct GenCall {
     static const bool dedup0_on = env_flag("GDR_DECODE_DEDUP0", true);     // exact A/B knob: 0 = run step 0 on all B*R (identical) beam rows
     static const bool early_on = env_flag("GDR_DECODE_EARLY_EXIT", true);  // A/B knob: 0 = always run all max_length - 1 steps
     static const bool slab_q = env_flag("GDR_DECODE_SLAB_Q", true);        // A/B knob: 0 = reduce the cross-attention q projection in its own launch
-    dedup0 = dedup0_on, slab_q_on = slab_q;
+    dedup0 = dedup0_on && !forced, slab_q_on = slab_q;  // score mode: the rows of a query differ from position 1 on and keep a slot each
     BeamBufs& bb = g.bb;
-    GDR_TRY(greedy ? greedy_begin(bb, bd, out_ids, out_len, out_scores, stream) : beam_begin(bb, bd, stream, dedup0));
+    GDR_TRY(forced   ? forced_begin(bb, bd, out_ids, stream)
+            : greedy ? greedy_begin(bb, bd, out_ids, out_len, out_scores, stream)
+                     : beam_begin(bb, bd, stream, dedup0));
     // stream-K hand-off scratch of the two chains' big linears (gemm_f32.hip) inside their split-K regions — a launch uses one
     // or the other; both flag blocks are zeroed here, on the caller's stream, before the adaptor stream is first forked
     sk1 = StreamK{g.skw, reinterpret_cast<int32_t*>(reinterpret_cast<char*>(g.skw) + STREAMK_PART_BYTES), 0};
@@ -732,7 +744,7 @@ struct GenCall {
     }
     // early exit (see done_words): not while a caller wants the per-step trace — its rows of the steps not run would be undefined
     done_word = nullptr, my_epoch = 0;
-    if (early_on && !step_scores && !step_tokens) {
+    if (early_on && !forced && !step_scores && !step_tokens) {  // score mode: every position of every row is wanted
       if (int32_t* words = done_words()) {
         my_epoch = g_done_epoch.fetch_add(1) + 1;  // never 0
         done_word = words + (my_epoch & 63);
@@ -812,13 +824,15 @@ struct GenCall {
   }
 
   // the decoder's input rows with the first norm of its stack; the adaptor chain starts beside it, its input rows on `as`
-  int embed_and_fork(int s) {
+  // (adaptor = false: a position with no head behind it, the score mode's last — the decoder stack alone)
+  int embed_and_fork(int s, bool adaptor = true) {
     const BeamBufs& bb = g.bb;
     const int rows_s = rows_at(s);
     img1.src = img2.src = nullptr;  // the embedding kernels rewrite nx / xa without a bf16 image
     hipLaunchKernelGGL(embed_rmsnorm_kernel, dim3((unsigned)((rows_s + 3) / 4)), dim3(256), 0, stream, w->dec_embed, bb.cur_tok, rows_s,
                        d / 4, w->dims.vocab_size, w->layers[0].ln_self, w->dims.eps, g.xd, g.nx, sk1.live);
     GDR_CHECK_LAUNCH("embed_rmsnorm_kernel");
+    if (!adaptor) return GDR_OK;
     // plain head: no second chain — nothing is forked or joined per step (the cross K/V projections are joined through
     // their own per-layer events at step 0)
     if (lease.ss && !plain) GDR_TRY(stream_after(as, lease.ss->fork, stream, "generate: fork to the adaptor stream failed"));
@@ -983,6 +997,27 @@ struct GenCall {
   int end() const {  // greedy_step_kernel wrote out_ids / out_len as it went
     return greedy ? GDR_OK : beam_end(g.bb, bd, max_length, cur, out_ids, out_len, out_scores, stream);
   }
+
+  // ---------------- score mode: the step loop over GIVEN rows.  The pieces above as they are, with the identity ancestor table and the
+  // rows' own tokens that forced_step_kernel leaves where the select would; all max_length positions run (one more than a search:
+  // the hidden state of the last one is wanted, the caches hold max_length positions), and the last has no head — head_e ends at
+  // max_out_len - 1 slices and nothing follows that position.  No early exit, no epoch, no hypothesis heap.
+  int score_given_rows() {
+    for (int s = 0; s < max_length; ++s) {
+      const bool headed = s + 1 < max_length;
+      GDR_TRY(embed_and_fork(s, headed));
+      for (int l = 0; l < w->dims.num_layers || (headed && l < w->adaptor_layers); ++l) {
+        if (l < w->dims.num_layers) GDR_TRY(dec_layer(l, s));
+        if (headed && l < w->adaptor_layers) GDR_TRY(ad_layer(l, s));
+      }
+      if (headed) {
+        GDR_TRY(join(s));
+        GDR_TRY(head(s));
+      }
+      GDR_TRY(forced_step(g.bb, bd, s, out_ids, g.hl, d, step_scores, stream));
+    }
+    return forced_end(g.bb, bd, out_ids, d, step_scores, out_scores, stream);
+  }
 };
 
 }  // namespace gdr
@@ -1007,6 +1042,7 @@ static int generate_impl(const GdrT5DecoderWeights* w, const float* enc_hidden, 
   GDR_TRY(c.lay_out());
   GDR_TRY(c.begin());
   GDR_TRY(c.cross_kv());
+  if (c.forced) return c.score_given_rows();
   for (int s = 0; s + 1 < max_length; ++s) {  // position s, cur_len = s + 1 (generation_utils.py:676)
     if (c.all_done(s)) {
       g_early_exits.fetch_add(1);

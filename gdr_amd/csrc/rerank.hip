@@ -53,7 +53,11 @@ __device__ __forceinline__ CandSeg cand_seg(const int32_t* cand_offsets, int b, 
   return CandSeg{off, (int64_t)off[0]};
 }
 
-template <bool BF16>
+// ROWQ (GDR_RERANK_ROW_QUERIES): q is [B*R][d] and a candidate of segment j of query b meets q[b*R + j] — the reference's
+// doc_similarity_all[i][cluster i's columns] (main_models.py:1588-1594).  The four candidates of a wave may lie in different
+// segments: each finds its own among the query's R + 1 offsets (the last segment that starts at or before it; empty segments hold
+// nothing) and runs the fmaf chain of the one-query form over its own row, so R equal rows give the one-query form's bits.
+template <bool BF16, bool ROWQ>
 __global__ __launch_bounds__(256) void rerank_dot_kernel(const float* __restrict__ q, const void* __restrict__ D, int d4,
                                                          const int32_t* __restrict__ cand_offsets,
                                                          const int32_t* __restrict__ cand_ids, int R, int func,
@@ -83,8 +87,23 @@ __global__ __launch_bounds__(256) void rerank_dot_kernel(const float* __restrict
     for (int i = 0; i < 4; ++i)
       if (!on[i]) row[i] = any_row;  // rows outside the shard read a valid row (uniform control flow), masked below
     const float4* q4 = reinterpret_cast<const float4*>(q) + (int64_t)b * d4;
+    const float4* qr[4] = {q4, q4, q4, q4};
+    if (ROWQ) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int c = c0 + i < ncand ? c0 + i : ncand - 1;  // c0 < ncand: a candidate of the list
+        int lo = 0, hi = R;  // segments [0, lo] start at or before c, segments >= hi start behind it
+        while (hi - lo > 1) {
+          const int mid = (lo + hi) >> 1;
+          if (cs.off[mid] - cs.off[0] <= c) lo = mid;
+          else hi = mid;
+        }
+        qr[i] = reinterpret_cast<const float4*>(q) + ((int64_t)b * R + lo) * d4;
+      }
+    }
     for (int e = lane; e < d4; e += 64) {
-      const float4 x = q4[e];
+      float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (!ROWQ) x = q4[e];  // one query row serves the four candidates
       float4 y[4];
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
@@ -98,10 +117,11 @@ __global__ __launch_bounds__(256) void rerank_dot_kernel(const float* __restrict
       }
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        acc[i] = fmaf(x.x, y[i].x, acc[i]);
-        acc[i] = fmaf(x.y, y[i].y, acc[i]);
-        acc[i] = fmaf(x.z, y[i].z, acc[i]);
-        acc[i] = fmaf(x.w, y[i].w, acc[i]);
+        const float4 xi = ROWQ ? qr[i][e] : x;
+        acc[i] = fmaf(xi.x, y[i].x, acc[i]);
+        acc[i] = fmaf(xi.y, y[i].y, acc[i]);
+        acc[i] = fmaf(xi.z, y[i].z, acc[i]);
+        acc[i] = fmaf(xi.w, y[i].w, acc[i]);
       }
     }
   }
@@ -281,7 +301,7 @@ static int rerank_impl(const float* q, const void* D, bool bf16, int d, const in
                 "rerank: bad shape B=%d R=%d A=%d k=%d d=%d", B, R, A, k, d);
   GDR_CHECK_ARG(func == 0 || func == 1, "rerank: func must be 0 (tanh) or 1 (sigmoid)");
   GDR_CHECK_ARG(max_cand >= 1 && max_cand <= RR_LONG_MAX_CAND, "rerank: max_cand=%d must be in [1,%d]", max_cand, RR_LONG_MAX_CAND);
-  GDR_CHECK_ARG((flags & ~(GDR_RERANK_POSITIONS | GDR_RERANK_CHUNKED)) == 0, "rerank: unknown flags %d", flags);
+  GDR_CHECK_ARG((flags & ~(GDR_RERANK_POSITIONS | GDR_RERANK_CHUNKED | GDR_RERANK_ROW_QUERIES)) == 0, "rerank: unknown flags %d", flags);
   const bool chunked = max_cand > RR_MAX_CAND || (flags & GDR_RERANK_CHUNKED) != 0;
   GDR_CHECK_ARG(!chunked || k <= RR_LONG_MAX_K, "rerank: k=%d must be <= %d for a list of more than %d candidates (max_cand=%d) or with "
                 "GDR_RERANK_CHUNKED", k, RR_LONG_MAX_K, RR_MAX_CAND, max_cand);
@@ -297,12 +317,15 @@ static int rerank_impl(const float* q, const void* D, bool bf16, int d, const in
   {
     ProfScope prof(PROF_RERANK, bytes, stream);
     const dim3 grid((unsigned)((max_cand + RR_CH - 1) / RR_CH), (unsigned)B);
-    if (bf16)
-      hipLaunchKernelGGL(rerank_dot_kernel<true>, grid, dim3(256), 0, stream, q, D, d / 4, cand_offsets, cand_ids, R, func, doc_lo,
-                         doc_hi, max_cand, cand_stride, sim);
-    else
-      hipLaunchKernelGGL(rerank_dot_kernel<false>, grid, dim3(256), 0, stream, q, D, d / 4, cand_offsets, cand_ids, R, func, doc_lo,
-                         doc_hi, max_cand, cand_stride, sim);
+#define GDR_RERANK_DOT(BF, RQ)                                                                                                      \
+  hipLaunchKernelGGL((rerank_dot_kernel<BF, RQ>), grid, dim3(256), 0, stream, q, D, d / 4, cand_offsets, cand_ids, R, func, doc_lo, \
+                     doc_hi, max_cand, cand_stride, sim)
+    const bool rowq = (flags & GDR_RERANK_ROW_QUERIES) != 0;  // q holds a row per (query, segment)
+    if (bf16 && rowq) GDR_RERANK_DOT(true, true);
+    else if (bf16) GDR_RERANK_DOT(true, false);
+    else if (rowq) GDR_RERANK_DOT(false, true);
+    else GDR_RERANK_DOT(false, false);
+#undef GDR_RERANK_DOT
     GDR_CHECK_LAUNCH("rerank_dot_kernel");
   }
   const int positions = (flags & GDR_RERANK_POSITIONS) ? 1 : 0;

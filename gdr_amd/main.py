@@ -33,7 +33,7 @@ if __package__ in (None, ""):
     __package__ = "gdr_amd"
 
 from . import _ffi, codec, launch, synth        # noqa: E402
-from .config import GDRConfig, unsupported_variant   # noqa: E402
+from .config import GDRConfig, stage2_query_form, unsupported_variant   # noqa: E402
 from .ops import T5_MAX_LEN                           # noqa: E402
 
 # (flag, type, default[, choices]) — names, types and defaults of main.py:262-396
@@ -378,6 +378,9 @@ def main(argv=None):
         if args.adaptor_decode == 0 and args.adaptor_efficient == 0 and args.prefix_table:
             raise SystemExit("gdr_amd: --prefix_table 1 cannot be combined with --adaptor_decode 0 --adaptor_efficient 0: the prefix "
                              "table stores the adaptor's results and the adaptor-free model has none — pass --prefix_table 0")
+        why = stage2_query_form(args, sharded=args.n_gpu > 1 and bool(args.is_train_encoder))[1]
+        if why:                                              # the sharded stage 2 has no per-hypothesis query rows
+            raise SystemExit("gdr_amd: " + why)
         if args.expand_index and args.n_gpu > 1:
             raise SystemExit("gdr_amd: --expand_index 1 runs on one GPU: it cannot be combined with --n_gpu > 1")
         if args.n_gpu > 1 and not launch.under_launcher():

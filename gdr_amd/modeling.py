@@ -15,7 +15,7 @@ import types
 import torch
 
 from . import _ffi, codec, ops
-from .config import GDRConfig
+from .config import GDRConfig, stage2_query_form
 
 
 class ModelOutput(dict):
@@ -168,6 +168,29 @@ class GDRModel:
             expanded = enc_h.repeat_interleave(num_beams, dim=0)
             return output, ModelOutput(last_hidden_state=expanded)
         return output, None
+
+    @torch.no_grad()
+    def score_docids(self, input_ids, docid_ids, attention_mask=None, length_penalty=1.0, hidden=False):
+        """Teacher forcing: encodes the queries and runs the decoder over the GIVEN docid token rows instead of searching for them
+        (ops.T5DecoderHandle.score).  docid_ids int64[B*n, width] holds n rows per query, query-major, each START, the docid's
+        tokens, EOS, then PAD — what generate() returns at num_return_sequences == num_beams, gold docids or another system's
+        candidates (codec encodes docid strings); width <= max_output_length.  Returns float64[B*n] on the device: each row's
+        sum of token log-probabilities / len ** length_penalty, the score generate() reports for that hypothesis.  hidden=True
+        returns (scores, trace, eos_state, mean) as ops.T5DecoderHandle.score does."""
+        if self.dec is None:
+            raise _ffi.GdrError("this GDRModel was built with with_decoder=False")
+        assert input_ids is not None and docid_ids is not None, "score_docids() needs input_ids and docid_ids"
+        assert length_penalty > 0, "`length_penalty` should be strictly positive."
+        B = input_ids.shape[0]
+        if docid_ids.dim() != 2 or docid_ids.shape[0] == 0 or docid_ids.shape[0] % B:
+            raise ValueError(f"score_docids: docid_ids must hold a whole number of rows per query ({B} queries), got "
+                             f"{tuple(docid_ids.shape)}")
+        if attention_mask is None:
+            attention_mask = torch.ones_like(input_ids)
+        input_ids, attention_mask = input_ids.to(self.device), attention_mask.to(self.device)
+        enc_h, _ = self.enc.forward(input_ids, attention_mask, want_pooled=False, ragged=self.ragged)
+        return self.dec.score(enc_h, attention_mask, docid_ids.to(self.device, torch.int64), docid_ids.shape[0] // B,
+                              length_penalty, hidden=hidden)
 
     def _generate_launch(self, input_ids, attention_mask, num_beams, max_length, length_penalty, num_return_sequences):
         """The device part of generate(): encoder + beam decode enqueued on the current stream, nothing read back.
@@ -383,6 +406,10 @@ class GDRRetriever:
         to the unsharded rerank.  Every rank must call validation_step_i the same number of times with the same batch size
         (the collectives are fixed-size); `cluster_index` is the index of the WHOLE corpus on every rank."""
         self._need_beams(args)
+        # the stage-2 query vector: the encoder CLS row, or per hypothesis the decoder's EOS state / masked mean
+        self.query_form, why = stage2_query_form(args, sharded=sharded is not None)
+        if why:
+            raise _ffi.GdrError("GDRRetriever: " + why)
         self.model, self.args, self.index = model, args, cluster_index
         self.doc_embed = doc_embed if doc_embed is not None or sharded is None else sharded.D
         self.sharded = sharded
@@ -723,12 +750,39 @@ class GDRRetriever:
                                                    position=getattr(a, "position", 1), kary=a.kary)
         return self._dci
 
+    def _decoder_queries(self, state):
+        """The decoder-side stage-2 queries, fp32[B*R, d]: the decoder runs over the step's own hypotheses (ops.T5DecoderHandle.score
+        on state["ids"], already on the device) and every hypothesis brings its last hidden state at the EOS position
+        (use_query_embed_decoder_special, main_models.py:1568-1571) or the mean over its tokens (use_query_embed_decoder_avg,
+        :1469-1476,1507).  A hypothesis that never emitted EOS has no `special` vector — the reference's boolean gather then
+        returns fewer rows than hypotheses and every later row meets another hypothesis' candidates; here it raises.  That check reads
+        one number back before the rerank is enqueued (the encoder-CLS path and `avg` enqueue everything first), so `special`
+        overlaps less across the batches of validation_steps(depth > 1)."""
+        a = self.args
+        mask = state["batch"].get("source_mask")
+        mask = torch.ones_like(state["batch"]["source_ids"]) if mask is None else mask
+        _scores, _trace, at_eos, mean = self.model.dec.score(state["enc_h"], mask.to(state["enc_h"].device), state["ids"],
+                                                            a.num_return_sequences, a.length_penalty, hidden=True)
+        if self.query_form == "avg":
+            return mean
+        open_rows = int((~(state["ids"][:, 1:] == 1).any(dim=1)).sum().item())
+        if open_rows:
+            raise _ffi.GdrError(f"use_query_embed_decoder_special: {open_rows} of {state['ids'].shape[0]} decoded hypotheses never "
+                                "emitted EOS and have no EOS hidden state to query with (constrain the decode with the docid trie, "
+                                "or use use_query_embed_decoder_avg)")
+        return at_eos
+
     def _step_finish(self, state, reencode=False):
         a = self.args
         R = a.num_return_sequences
         batch = state["batch"]
-        query_embeds = self.encoder(query_enc=state["enc_h"]).contiguous()      # CLS rows (main_models.py:1466)
-        B = query_embeds.shape[0]
+        row_queries = self.query_form != "encoder"
+        if row_queries:
+            query_embeds = self._decoder_queries(state)                         # [B*R, d] (main_models.py:1467-1571)
+            B = query_embeds.shape[0] // R
+        else:
+            query_embeds = self.encoder(query_enc=state["enc_h"]).contiguous()  # CLS rows (main_models.py:1466)
+            B = query_embeds.shape[0]
         alphas, func = list(a.score_rate), getattr(a, "loss_func", "tanh")
         dci = self._device_index()
         stride = 0
@@ -769,11 +823,11 @@ class GDRRetriever:
                 live = dev_ids.reshape(-1)[:1]
             cand_embeds = self._reencode(live)                                      # [total, d], candidate order
             vals, pos = ops.rerank_topk(query_embeds, cand_embeds, offs, local, beam_scores, alphas, R, func=func,
-                                        max_cand=max_cand, cand_stride=stride)
+                                        max_cand=max_cand, cand_stride=stride, row_queries=row_queries)
             idx = torch.where(pos >= 0, live[pos.clamp(min=0).long()], pos)         # candidate position -> doc id
         else:
             vals, idx = ops.rerank_topk(query_embeds, self.doc_embed, offs, dev_ids, beam_scores, alphas, R, func=func,
-                                        max_cand=max_cand, cand_stride=stride)
+                                        max_cand=max_cand, cand_stride=stride, row_queries=row_queries)
         if outs is None:                                                            # first read-back of the step
             outs, scores = ops.finish_generate_output(state["ids"], state["lens"], state["scores"], a.max_output_length)
         outs_h = outs.cpu().numpy()

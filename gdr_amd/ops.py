@@ -384,7 +384,7 @@ _RERANK_WS = {}
 
 
 def rerank_topk(q, D, cand_offsets, cand_ids, beam_scores, alphas, k, func="tanh", max_cand=None, doc_range=None,
-                positions=False, workspace=None, cand_stride=0, chunked=False):
+                positions=False, workspace=None, cand_stride=0, chunked=False, row_queries=False):
     """In-cluster rerank — gdr_rerank_topk / gdr_rerank_topk_bf16 (chosen by D.dtype; a bf16 corpus is gathered as bf16,
     never up-cast).  Returns (values fp32[B,A,k], doc ids int32[B,A,k]).
     cand_stride=0: cand_offsets int32[B*R+1] is ONE CSR into cand_ids (the reference's concatenation order);
@@ -394,7 +394,9 @@ def rerank_topk(q, D, cand_offsets, cand_ids, beam_scores, alphas, k, func="tanh
     their first k merged (k <= 1024 there) — the same list bit for bit.  chunked=True takes that form at any max_cand
     (GDR_RERANK_CHUNKED: the A/B switch of tests and tools).
     doc_range=(lo, hi): D holds rows [lo, hi) of the corpus, candidates outside are skipped (sharded GDR mode, dist.py);
-    positions=True returns candidate positions within the query's list instead of doc ids (what the shard merge needs)."""
+    positions=True returns candidate positions within the query's list instead of doc ids (what the shard merge needs).
+    row_queries=True (GDR_RERANK_ROW_QUERIES): q is fp32[B*R, d], a vector per (query, segment) — a candidate of segment j of
+    query b is scored against q[b*R + j] (the decoder-side stage-2 queries); everything else is unchanged."""
     _need_cuda(q, D, cand_offsets, cand_ids, beam_scores)
     q, beam_scores = _f32c(q), _f32c(beam_scores)
     if D.dtype == torch.bfloat16:
@@ -404,6 +406,8 @@ def rerank_topk(q, D, cand_offsets, cand_ids, beam_scores, alphas, k, func="tanh
     if D.dim() != 2 or D.shape[1] != q.shape[1]:
         raise _ffi.GdrError(f"rerank_topk: dim mismatch {tuple(q.shape)} vs {tuple(D.shape)}")
     B, R = beam_scores.shape
+    if row_queries and (q.dim() != 2 or q.shape[0] != B * R):
+        raise _ffi.GdrError(f"rerank_topk: row_queries needs q of B*R = {B * R} rows, got {tuple(q.shape)}")
     al = torch.as_tensor(alphas, dtype=torch.float32, device=q.device)
     A = al.numel()
     if max_cand is None:
@@ -424,7 +428,8 @@ def rerank_topk(q, D, cand_offsets, cand_ids, beam_scores, alphas, k, func="tanh
     oi = torch.empty((B, A, k), dtype=torch.int32, device=q.device)
     check(fn(ptr(q), ptr(D), q.shape[1], ptr(cand_offsets), ptr(cand_ids), ptr(beam_scores), B, R, ptr(al), A, k,
              0 if func == "tanh" else 1, ptr(ov), ptr(oi), max_cand, int(cand_stride), lo, hi,
-             (_ffi.RERANK_POSITIONS if positions else 0) | (_ffi.RERANK_CHUNKED if chunked else 0),
+             (_ffi.RERANK_POSITIONS if positions else 0) | (_ffi.RERANK_CHUNKED if chunked else 0) |
+             (_ffi.RERANK_ROW_QUERIES if row_queries else 0),
              ptr(ws), ws.numel(), stream_ptr()), "gdr_rerank_topk")
     return ov, oi
 
@@ -1303,6 +1308,37 @@ class T5DecoderHandle:
             tt = torch.empty((max_length - 1, B, 2 * R), dtype=torch.int32, device=dev_)
         call(enc_hidden, mask, ids, lens, scores, ts, tt, ws)
         return (ids, lens, scores, ts, tt) if trace else (ids, lens, scores)
+
+    def score(self, enc_hidden, enc_mask, ids, rows_per_query, length_penalty, hidden=False):
+        """Teacher forcing — gdr_t5_generate's score mode (out_len = NULL, include/gdr_hip.h): the decoder runs over the GIVEN docid
+        rows `ids` int64[B*rows_per_query, max_length] (START, tokens, EOS, then PAD: what generate() returns at
+        num_return_sequences == num_beams; row b*rows_per_query + r belongs to query b) and returns the score generate() reports for
+        each of them, float64[rows].  hidden=True also returns the decoder's last hidden states: (scores, trace fp32[max_length,
+        rows, d] — zero behind a row's first EOS —, the state at the first EOS fp32[rows, d] — zero without one —, the mean over the
+        row's START and non-PAD positions fp32[rows, d]).  `ids` is only read.  No host synchronisation."""
+        _need_cuda(enc_hidden, enc_mask, ids)
+        if enc_hidden.dim() != 3 or enc_hidden.shape[2] != self.cfg.d_model:
+            raise ValueError(f"score: enc_hidden must be [B, L, {self.cfg.d_model}], got {tuple(enc_hidden.shape)}")
+        B, L, d = enc_hidden.shape
+        R = int(rows_per_query)
+        if tuple(enc_mask.shape) != (B, L):
+            raise ValueError(f"score: enc_mask must be [{B}, {L}], got {tuple(enc_mask.shape)}")
+        if ids.dtype != torch.int64:
+            raise TypeError(f"score: ids must be int64 (generate()'s out_ids), got {ids.dtype}")
+        if R < 1 or ids.dim() != 2 or ids.shape[0] != B * R:
+            raise ValueError(f"score: ids must be [B*rows_per_query = {B * R}, max_length], got {tuple(ids.shape)}")
+        max_length = int(ids.shape[1])
+        enc_hidden = _f32c(enc_hidden)
+        mask = enc_mask.to(torch.int64).contiguous()
+        ids = ids.contiguous()
+        dev_ = enc_hidden.device
+        fn = lib().gdr_t5_generate_bf16 if self.dtype == torch.bfloat16 else lib().gdr_t5_generate
+        ws = self.ws.get(lib().gdr_t5_generate_workspace_bytes(C.byref(self.struct), B, L, R, max_length))
+        scores = torch.empty((B * R,), dtype=torch.float64, device=dev_)
+        planes = torch.empty((max_length + 2, B * R, d), dtype=torch.float32, device=dev_) if hidden else None
+        check(fn(C.byref(self.struct), ptr(enc_hidden), ptr(mask), B, L, R, max_length, float(length_penalty), R, None, None,
+                 ptr(ids), None, ptr(scores), ptr(planes), None, ptr(ws), ws.numel(), stream_ptr()), "gdr_t5_generate")
+        return (scores, planes[:max_length], planes[max_length], planes[max_length + 1]) if hidden else scores
 
 
 class DeviceTrie:

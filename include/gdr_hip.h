@@ -358,6 +358,13 @@ int gdr_topk_merge_packed(const void* pairs, int G, int B, int k, float* out_val
  * ---------------------------------------------------------------------------------------------- */
 #define GDR_RERANK_POSITIONS 1
 #define GDR_RERANK_CHUNKED 2
+/* GDR_RERANK_ROW_QUERIES: q is fp32[B*R, d], one query vector per (query, segment): a candidate of segment j of query b is
+ * scored against q[b*R + j] — the reference's doc_similarity_all[i][cluster i's columns] of the decoder-side stage-2 forms
+ * (main_models.py:1588-1594), where every decoded hypothesis brings its own vector.  Only the dot pass differs (a candidate finds
+ * its segment among the query's R + 1 offsets); the beam softmax, the keys, both selects, both layouts, the bf16 corpus, doc
+ * ranges and the other flags are untouched, and R equal rows per query give the one-vector call's result bit for bit.  The
+ * value is 8: 4 stays an unknown flag (GDR_EINVAL), as it has been refused since the flags argument exists. */
+#define GDR_RERANK_ROW_QUERIES 8
 size_t gdr_rerank_workspace_bytes(int B, int max_cand);
 int gdr_rerank_topk(const float* q, const float* D, int d, const int32_t* cand_offsets, const int32_t* cand_ids,
                     const float* beam_scores, int B, int R, const float* alphas, int A, int k, int func,
@@ -720,7 +727,27 @@ size_t gdr_t5_generate_workspace_bytes(const GdrT5DecoderWeights* w, int B, int 
  * the trie constraint, the trace, the early exit and its counters, L up to 512 and stream capture all apply.  prefix_table must be
  * NULL (GDR_EINVAL naming it: the table stores adaptor results, and lm_head alone has nothing query-independent to store).
  * gdr_t5_generate_workspace_bytes leaves out the adaptor K/V cache, the adaptor activations and the rows x (V+1) x d head-matrix
- * buffer for such weights. */
+ * buffer for such weights.
+ *
+ * Score mode — out_len == NULL: the decoder runs over GIVEN docid rows instead of searching for them (teacher forcing; the forward
+ * the reference's validation step makes with decoder_input_ids = outs, main_models.py:1467-1571).  Contract:
+ *   rows = B * num_beams with 1 <= num_beams <= 1024 rows per query (row b*num_beams + r belongs to query b); neither the
+ *   hypothesis-heap LDS limit nor the num_beams * (V+1) candidate limit applies (no heap, no select);
+ *   num_return_sequences must equal num_beams; trie, prefix_table and step_tokens must be NULL; length_penalty > 0; max_length in
+ *   [2, max_out_len] — any violation is GDR_EINVAL naming the argument, before any launch;
+ *   out_ids int64[rows, max_length] is an INPUT that is only read: rows as a search with nret == num_beams writes them (START,
+ *   tokens, EOS, then PAD);
+ *   out_scores fp64[rows] = what the search reports for that hypothesis: sum_t log_softmax(logits_t)[ids[t+1]] / len^length_penalty
+ *   over the positions before the row's first EOS (the EOS' own log-probability included), len = the EOS position, max_length
+ *   for a row without EOS; logits_t are the V+1 live columns of position t, and a token that is no live column of its position
+ *   counts as the masked logit, exactly -1e9; the sum is accumulated in fp32 in position order, as the search accumulates it;
+ *   step_scores (optional) fp32[max_length + 2][rows][d_model], an output: planes 0 .. max_length-1 the decoder's last hidden state
+ *   of each position (after final_layer_norm; zero behind a row's first EOS), plane max_length the hidden state AT the first EOS
+ *   (a zero row without one), plane max_length + 1 the mean over t = 0 and every t >= 1 with ids[t] != PAD (summed ascending in
+ *   fp32, one division by the count);
+ *   workspace: gdr_t5_generate_workspace_bytes(w, B, L, num_beams, max_length) serves the mode.
+ * All max_length positions run (one more than a search; the head is not run behind the last), every row keeps cache slots of its
+ * own, there is no early exit and no host synchronisation; stream capture, both precision modes and both head forms apply. */
 int gdr_t5_generate(const GdrT5DecoderWeights* w, const float* enc_hidden, const int64_t* enc_mask, int B, int L,
                     int num_beams, int max_length, double length_penalty, int num_return_sequences,
                     const GdrTrie* trie, const GdrPrefixTable* prefix_table /* NULL: compute every row */, int64_t* out_ids,
