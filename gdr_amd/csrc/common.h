@@ -131,7 +131,7 @@ int launch_linear_f32_ws_dev(const float* A, int64_t lda, const float* W, int64_
                              StreamK* sk = nullptr);
 int launch_linear_f32_dev(const float* A, int64_t lda, const float* W, int64_t ldw, float* C, int64_t ldc, int64_t M_max,
                           const int64_t* m_dev, int N, int K, int epilogue, const float* bias, const float* residual,
-                          int64_t ldr, int64_t prof_rows, hipStream_t stream, StreamK* sk = nullptr);
+                          int64_t ldr, int64_t prof_rows, hipStream_t stream, StreamK* sk = nullptr, int grid_cap = 0);
 // docs D[N,d] take the GEMM's row role, queries Q[B,d] the column role: a lane owns one query.
 int launch_sim_gemm(const void* D, int64_t N, const void* Q, int B, int d, const SimEpilogue& ep, bool bf16,
                     hipStream_t stream);

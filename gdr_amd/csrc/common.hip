@@ -1,3 +1,4 @@
+#include <algorithm>
 #include <atomic>
 
 #include "common.h"
@@ -92,6 +93,12 @@ extern "C" int gdr_prof_enable(int max_events) {
 // Synchronises the recorded events, accumulates per class {launches, total ms, total work} into the three
 // host arrays of length 8, then disables and frees the profiler.  Returns the number of events lost to a
 // full buffer (0 = none) or a negative error code.
+// total ms of a class is the length of the UNION of its launches' [start, stop] intervals on one time axis: launches that
+// overlap (two chains of one call on two streams, two batches in flight) each run slower while they share the chip, and
+// the sum of their durations would count that time twice — work / total ms would fall while the step got faster.  For
+// launches that do not overlap the union is the sum.  The axis: every start is placed relative to an anchor event and the
+// anchor moves every 64 launches (hipEventElapsedTime is a float of milliseconds: over a run of seconds a single base
+// would resolve microseconds only); a launch's own duration is always its own start -> stop difference.
 extern "C" int gdr_prof_collect(int64_t* launches, double* total_ms, double* total_work) {
   using namespace gdr;
   if (!g_prof.on) {
@@ -100,16 +107,37 @@ extern "C" int gdr_prof_collect(int64_t* launches, double* total_ms, double* tot
   }
   for (int c = 0; c < PROF_NCLASS; ++c) launches[c] = 0, total_ms[c] = 0.0, total_work[c] = 0.0;
   int rc = GDR_OK;
+  struct Span {
+    double t0, t1;
+  };
+  std::vector<Span> spans[PROF_NCLASS];
+  double anchor_t = 0.0;
+  int anchor = 0;
   for (int i = 0; i < g_prof.used; ++i) {
-    float ms = 0.f;
+    float ms = 0.f, rel = 0.f;
     if (hipEventSynchronize(g_prof.stop[i]) != hipSuccess ||
-        hipEventElapsedTime(&ms, g_prof.start[i], g_prof.stop[i]) != hipSuccess) {
+        hipEventElapsedTime(&ms, g_prof.start[i], g_prof.stop[i]) != hipSuccess ||
+        (i != anchor && hipEventElapsedTime(&rel, g_prof.start[anchor], g_prof.start[i]) != hipSuccess)) {
       set_error("prof_collect: event query failed");
       rc = GDR_EHIP;
       break;
     }
+    const double t0 = anchor_t + (double)rel;  // may lie before the anchor: a start on another stream
+    if (i - anchor >= 64) anchor = i, anchor_t = t0;
     const int c = g_prof.cls[i];
-    launches[c] += 1, total_ms[c] += ms, total_work[c] += g_prof.work[i];
+    launches[c] += 1, total_work[c] += g_prof.work[i];
+    spans[c].push_back(Span{t0, t0 + (double)ms});
+  }
+  for (int c = 0; c < PROF_NCLASS && rc == GDR_OK; ++c) {
+    std::sort(spans[c].begin(), spans[c].end(), [](const Span& a, const Span& b) { return a.t0 < b.t0; });
+    double end = 0.0;
+    for (size_t i = 0; i < spans[c].size(); ++i) {
+      const Span& s = spans[c][i];
+      if (i == 0 || s.t0 >= end)
+        total_ms[c] += s.t1 - s.t0, end = s.t1;
+      else if (s.t1 > end)
+        total_ms[c] += s.t1 - end, end = s.t1;
+    }
   }
   for (int i = 0; i < g_prof.cap; ++i) {
     (void)hipEventDestroy(g_prof.start[i]);

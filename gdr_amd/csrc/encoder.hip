@@ -13,6 +13,9 @@
 // [buckets,H] table (layer 0's, shared by all layers as in :790-795).
 #include <stdlib.h>
 
+#include <mutex>
+#include <vector>
+
 #include "layers.h"
 
 namespace gdr {
@@ -216,17 +219,121 @@ static bool ragged_packs(const GdrT5Dims& dm, int B, int L) {
 static bool ragged_packs_small(const GdrT5Dims& dm, int B, int L) {
   return dm.d_kv == 64 && (int64_t)B * L >= 256 && dm.d_model % 32 == 0 && dm.d_ff % 32 == 0 && (dm.num_heads * dm.d_kv) % 32 == 0;
 }
+
+// ---- two chains (GDR_ENC_CHAINS=2; DESIGN 4 "Two encoder chains") ------------------------------------------------------
+// A pooled-only fp32 call whose two halves [0, B/2) and [B/2, B) both satisfy ragged_packs runs as two independent packed
+// forwards — sequences do not interact — each on its own slice of ids / mask / out_pooled and its own workspace (its own pack
+// plan and stream-K scratch): chain A on the caller's stream, chain B on a leased side stream forked from and joined to
+// the caller's stream by events, so the caller sees one stream-ordered call (and a capture of it stays legal).  While one
+// chain is in a norm, an attention, a GEMM's ramp or its hand-off, the other holds the matrix pipes.
+// Co-residency: every persistent / stream-K linear of a chain is capped at ENC_CHAIN_GRID workgroups, so a call never has
+// more than 2 x 256 = 512 of them in flight — the chip's slots (256 CUs x 2): a stream-K workgroup's predecessor is
+// resident or becomes so as soon as a short non-GEMM kernel retires, never behind the other chain's GEMM.
+// A row's bits do not depend on the chain count: every whole-K form gives the same bits and the CLS tail is un-split.
+constexpr int ENC_CHAIN_GRID = 256;
+constexpr int ENC_CHAINS_DEFAULT = 2;  // GDR_ENC_CHAINS when unset (DESIGN 4 "Two encoder chains": the A/B that decided it)
+// Chain B starts behind this many of chain A's block-0 linears (0..3).  Started together the chains reach every boundary
+// together and the step is slower than one chain; behind A's o projection (1) they stay half a block apart.  Measured
+// 0 / 1 / 2 / 3: +0.5 % / -2.0 % / -1.9 % / +0.8 % of the C2 step (profiles/r21_enc_chains_stagger.txt).
+constexpr int ENC_CHAIN_STAGGER_DEFAULT = 1;
+struct EncChain {
+  int grid_cap;          // workgroups of the chain's persistent / stream-K linears
+  hipEvent_t after;      // recorded on the chain's stream behind its `after_linears`-th batch linear; null: none
+  int after_linears;
+};
+static bool enc_chains_eligible(const GdrT5Dims& dm, int B, int L) {  // B/2 is the smaller half
+  return B >= 2 && dm.num_layers >= 2 && ragged_packs(dm, B / 2, L);
+}
+static size_t ragged_one_chain_bytes(const GdrT5Dims& dm, int B, int L) {  // a multiple of 256
+  return rag_ws(dm, B, L, enc_ws(dm, (int64_t)B * L, true).total).total;
+}
+static size_t ragged_bytes(const GdrT5Dims& dm, int B, int L) {
+  const size_t one = ragged_one_chain_bytes(dm, B, L);
+  if (!enc_chains_eligible(dm, B, L)) return one;
+  const size_t two = ragged_one_chain_bytes(dm, B / 2, L) + ragged_one_chain_bytes(dm, B - B / 2, L);
+  return two > one ? two : one;
+}
+
+struct EncSide {
+  hipStream_t s = nullptr;
+  hipEvent_t fork = nullptr, stagger = nullptr, join = nullptr;
+  int dev = -1;
+};
+static std::mutex g_enc_side_mu;
+static std::vector<EncSide*> g_enc_side_free;
+// leased per call from a per-device pool, as decode.hip's side streams: created once, reused, never shared by two calls
+static EncSide* enc_side_acquire() {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return nullptr;
+  {
+    std::lock_guard<std::mutex> lock(g_enc_side_mu);
+    for (size_t i = 0; i < g_enc_side_free.size(); ++i)
+      if (g_enc_side_free[i]->dev == dev) {
+        EncSide* x = g_enc_side_free[i];
+        g_enc_side_free.erase(g_enc_side_free.begin() + i);
+        return x;
+      }
+  }
+  EncSide* x = new EncSide();
+  x->dev = dev;
+  if (hipStreamCreateWithFlags(&x->s, hipStreamNonBlocking) != hipSuccess ||
+      hipEventCreateWithFlags(&x->fork, hipEventDisableTiming) != hipSuccess ||
+      hipEventCreateWithFlags(&x->stagger, hipEventDisableTiming) != hipSuccess ||
+      hipEventCreateWithFlags(&x->join, hipEventDisableTiming) != hipSuccess) {
+    (void)hipGetLastError();
+    delete x;  // the caller runs one chain
+    return nullptr;
+  }
+  return x;
+}
+static void enc_side_release(EncSide* x) {  // when the call has finished enqueueing: the stream is in-order
+  std::lock_guard<std::mutex> lock(g_enc_side_mu);
+  g_enc_side_free.push_back(x);
+}
+
+static int ragged_impl(const GdrT5EncoderWeights* w, const int64_t* ids, const int64_t* mask, int B, int L, float* out_hidden,
+                       float* out_pooled, int64_t live_rows_hint, void* workspace, size_t workspace_bytes, bool bf16,
+                       hipStream_t stream, const EncChain* chain = nullptr);
+
+static int ragged_two_chains(const GdrT5EncoderWeights* w, const int64_t* ids, const int64_t* mask, int B, int L, float* out_pooled,
+                             int64_t live_rows_hint, char* base, int stagger, EncSide* side, hipStream_t stream) {
+  const GdrT5Dims& dm = w->dims;
+  const int BA = B / 2, BB = B - BA;
+  const size_t bytes_a = ragged_one_chain_bytes(dm, BA, L), bytes_b = ragged_one_chain_bytes(dm, BB, L);
+  const int64_t hint_a = live_rows_hint >= 0 ? live_rows_hint / 2 : -1;  // a tuning input only
+  const int64_t hint_b = live_rows_hint >= 0 ? live_rows_hint - hint_a : -1;
+  if (hipEventRecord(side->fork, stream) != hipSuccess || hipStreamWaitEvent(side->s, side->fork, 0) != hipSuccess) {
+    set_error("t5_encoder_ragged: fork to the side stream failed");
+    return GDR_EHIP;
+  }
+  const EncChain ca{ENC_CHAIN_GRID, stagger > 0 ? side->stagger : nullptr, stagger};
+  const EncChain cb{ENC_CHAIN_GRID, nullptr, 0};
+  int rc = ragged_impl(w, ids, mask, BA, L, nullptr, out_pooled, hint_a, base, bytes_a, false, stream, &ca);
+  if (rc == GDR_OK && stagger > 0 && hipStreamWaitEvent(side->s, side->stagger, 0) != hipSuccess) {
+    set_error("t5_encoder_ragged: wait on the stagger event failed");
+    rc = GDR_EHIP;
+  }
+  if (rc == GDR_OK)
+    rc = ragged_impl(w, ids + (size_t)BA * L, mask + (size_t)BA * L, BB, L, nullptr, out_pooled + (size_t)BA * dm.d_model, hint_b,
+                     base + bytes_a, bytes_b, false, side->s, &cb);
+  // the join is enqueued whatever happened above: the side stream must not stay forked (a capture would be left open)
+  if (hipEventRecord(side->join, side->s) != hipSuccess || hipStreamWaitEvent(stream, side->join, 0) != hipSuccess) {
+    if (rc == GDR_OK) set_error("t5_encoder_ragged: join of the side stream failed");
+    return rc ? rc : GDR_EHIP;
+  }
+  return rc;
+}
 }  // namespace gdr
 
 extern "C" size_t gdr_t5_encoder_ragged_workspace_bytes(const GdrT5Dims* dims, int B, int L) {
   if (!dims || B <= 0 || L <= 0) return 0;
-  return gdr::rag_ws(*dims, B, L, gdr::enc_ws(*dims, (int64_t)B * L, true).total).total;  // serves both precisions
+  return gdr::ragged_bytes(*dims, B, L);  // serves both precisions and both chain counts
 }
 
 namespace gdr {
 static int ragged_impl(const GdrT5EncoderWeights* w, const int64_t* ids, const int64_t* mask, int B, int L, float* out_hidden,
                        float* out_pooled, int64_t live_rows_hint, void* workspace, size_t workspace_bytes, bool bf16,
-                       hipStream_t stream) {
+                       hipStream_t stream, const EncChain* chain) {
   if (B == 0) return GDR_OK;
   GDR_CHECK_ARG(w && ids && mask && workspace && (out_hidden || out_pooled), "t5_encoder_ragged: null pointer");
   const GdrT5Dims& dm = w->dims;
@@ -236,12 +343,31 @@ static int ragged_impl(const GdrT5EncoderWeights* w, const int64_t* ids, const i
   const int64_t M = (int64_t)B * L;
   const EncWs ws = enc_ws(dm, M, true);
   const RagWs rw = rag_ws(dm, B, L, ws.total);
-  if (workspace_bytes < rw.total) {
-    set_error("t5_encoder_ragged: workspace %zu < required %zu", workspace_bytes, rw.total);
+  const size_t required = chain ? rw.total : ragged_bytes(dm, B, L);  // a chain's slice; a call: the documented size
+  if (workspace_bytes < required) {
+    set_error("t5_encoder_ragged: workspace %zu < required %zu", workspace_bytes, required);
     return GDR_ENOSPC;
   }
   GDR_CHECK_ARG(((uintptr_t)workspace & 255) == 0, "t5_encoder_ragged: workspace must be 256-byte aligned");
   char* base = static_cast<char*>(workspace);
+  if (!chain && !bf16 && !out_hidden && enc_chains_eligible(dm, B, L)) {
+    static const int chains = [] {
+      const char* e = getenv("GDR_ENC_CHAINS");  // exact A/B knob: 1 = one chain, 2 = two half-batch chains in flight
+      return e ? atoi(e) : ENC_CHAINS_DEFAULT;
+    }();
+    static const int stagger = [] {
+      const char* e = getenv("GDR_ENC_CHAIN_STAGGER");  // lab knob: chain B starts behind this many of chain A's linears
+      const int v = e ? atoi(e) : ENC_CHAIN_STAGGER_DEFAULT;
+      return v < 0 ? 0 : v > 3 ? 3 : v;  // block 0 of a chain has three batch linears at least (o, wi, wo)
+    }();
+    if (chains == 2) {
+      if (EncSide* side = enc_side_acquire()) {
+        const int rc2 = ragged_two_chains(w, ids, mask, B, L, out_pooled, live_rows_hint, base, stagger, side, stream);
+        enc_side_release(side);
+        return rc2;
+      }
+    }
+  }
   const int d = dm.d_model, H = dm.num_heads, dk = dm.d_kv, inner = H * dk;
   int rc;
   int32_t* seq_len = reinterpret_cast<int32_t*>(base + rw.seq_len);
@@ -351,13 +477,19 @@ static int ragged_impl(const GdrT5EncoderWeights* w, const int64_t* ids, const i
   StreamK sk{};
   if ((rc = enc_streamk(base + ws.off_splitk, &sk, stream))) return rc;
   float* skw = reinterpret_cast<float*>(base + ws.off_splitk);
+  int batch_linears = 0;  // two-chain form: chain A raises chain B's start event behind one of its first linears
   auto linear = [&](const float* A, int64_t lda, const float* W, float* C, int64_t ldc, int N, int K, int epi,
                     const float* residual) -> int {
     if (small)  // the forms the padded forward picks for B*L rows (split-K / stream-K), over the live rows only
       return launch_linear_f32_ws(A, lda, W, K, C, ldc, M, N, K, epi, nullptr, residual, ldc, skw, ENC_SPLITK_BYTES, stream, &sk,
                                   rows_dev, live_rows_hint);
-    return launch_linear_f32_dev(A, lda, W, K, C, ldc, M, rows_dev, N, K, epi, nullptr, residual, ldc, live_rows_hint, stream,
-                                 &sk);
+    GDR_TRY(launch_linear_f32_dev(A, lda, W, K, C, ldc, M, rows_dev, N, K, epi, nullptr, residual, ldc, live_rows_hint, stream, &sk,
+                                  chain ? chain->grid_cap : 0));
+    if (chain && chain->after && ++batch_linears == chain->after_linears && hipEventRecord(chain->after, stream) != hipSuccess) {
+      set_error("t5_encoder_ragged: event record behind a linear failed");
+      return GDR_EHIP;
+    }
+    return GDR_OK;
   };
   // Token table (un-split forms only): block 0's q/k/v depend on the token id alone — no position embedding, a per-row norm,
   // independent GEMM rows — so the caller may hand them in as a [vocab, 3*inner] table made with the same norm and the same

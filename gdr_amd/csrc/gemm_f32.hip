@@ -697,7 +697,9 @@ struct StreamKArgs {
 // A take-over spin that runs out (the predecessor workgroup never became resident for seconds — a co-tenant kernel that
 // starves it; the kernel itself assumes its <= 512 workgroups are co-resident, 2 per CU) used to trap, which aborts the
 // whole process.  Now the waiting lane raises this process-wide word (pinned host memory, mapped into every device) and
-// the workgroup goes on with whatever the hand-off buffer holds: the launch completes, its output is WRONG.  The word is
+// the workgroup goes on with whatever the hand-off buffer holds: the launch completes, its output is WRONG.  (The two-chain
+// encoder form runs two such launches at once, each capped at 256 workgroups — LinearCall.grid_cap — and each with a StreamK
+// scratch of its own: a call issued by that form never has more than 512 stream-K workgroups in flight.)  The word is
 // STICKY: it stays raised until the caller acknowledges it with gdr_device_fault_clear(), every stream-K launch enqueued
 // while it is raised fails with GDR_EHIP, and gdr_device_fault_pending() lets a caller check it where it synchronises
 // anyway (the Python side does after every result read-back: ops.finish_generate_output, sim_topk's status read,
@@ -1053,6 +1055,8 @@ struct LinearCall {
   int64_t row_hint;  // the live row count if the host happens to know it (< 0: unknown) — a tuning input only
   bool whole_k;      // launch_linear_f32_dev: no small-tile / split-K form (their k order differs: a row's result must not depend
                      // on how many rows happen to be live), and the stream-K admission goes by the LIVE tile count of the hint
+  int grid_cap = 0;  // whole_k only; 0: none.  Most workgroups this launch may hold resident (the two-chain encoder: 256, so
+                     // that two concurrent launches fill the chip's 512 slots and neither waits for the other's to retire)
 };
 static LinearRoute linear_f32_route(const LinearCall& c) {
   if (c.M <= 0 || c.N <= 0 || c.K <= 0 || c.K % 4 != 0) return {FORM_NONE, 0, 0, 0};
@@ -1088,6 +1092,10 @@ static LinearRoute linear_f32_route(const LinearCall& c) {
   }
   const int64_t tiles_adm = c.whole_k && c.row_hint >= 0 ? ((c.row_hint + BM - 1) / BM) * tiles_n : tiles;
   const bool sk_ok = c.has_sk && kfull && streamk_fits(c.M, c.lda, c.N, c.ldw);
+  if (c.whole_k && c.grid_cap > 0 && tiles > c.grid_cap && tiles < 0x7fffffff && kfull)
+    // capped: whole-tile rounds, then the stream-K tail, on grid_cap workgroups (the kernels are generic in gridDim.x; the
+    // tail costs nothing when the live tiles come out in whole rounds).  Without a scratch, whole tiles on as many.
+    return {sk_ok ? FORM_STREAMK_TAIL : FORM_PERSISTENT, 0, 0, c.grid_cap};
   if (sk_ok && tiles > 256 && streamk_mid_wanted(tiles_adm)) return {FORM_STREAMK_256, 0, 0, 256};
   if (tiles > 512 && tiles < 0x7fffffff && kfull)  // more than one round of tiles on 256 CUs x 2 resident workgroups
     return {sk_ok && streamk_wanted(tiles_adm, nk) ? FORM_STREAMK_TAIL : FORM_PERSISTENT, 0, 0, 512};
@@ -1230,9 +1238,10 @@ int launch_linear_f32_ws_dev(const float* A, int64_t lda, const float* W, int64_
 // M_max and the kernels read the count themselves, so there is no host round trip.  Whole-K forms only (LinearCall.whole_k)
 // — callers use this at encoder batch sizes, where the 128x128 grid fills the chip anyway.  prof_rows: the live-row count
 // if the host happens to know it (< 0: unknown, M_max is used) — the stream-K admission and the opt-in profiler read it.
+// grid_cap (0: none): most workgroups of the persistent / stream-K launch (LinearCall.grid_cap).
 int launch_linear_f32_dev(const float* A, int64_t lda, const float* W, int64_t ldw, float* C, int64_t ldc, int64_t M_max,
                           const int64_t* m_dev, int N, int K, int epilogue, const float* bias, const float* residual,
-                          int64_t ldr, int64_t prof_rows, hipStream_t stream, StreamK* sk) {
+                          int64_t ldr, int64_t prof_rows, hipStream_t stream, StreamK* sk, int grid_cap) {
   if (M_max == 0) return GDR_OK;
   GDR_CHECK_ARG(m_dev, "linear(dev rows): null row count");
   GemmArgs g;
@@ -1240,7 +1249,7 @@ int launch_linear_f32_dev(const float* A, int64_t lda, const float* W, int64_t l
   GDR_CHECK_ARG(M_max > 0 && K % BK == 0, "linear(dev rows): bad shape M<=%lld N=%d K=%d (K %% 32 == 0)", (long long)M_max, N, K);
   GDR_CHECK_ARG(((M_max + BM - 1) / BM) * g.tiles_n < 0x7fffffff, "linear(dev rows): grid too large");
   ProfScope prof(PROF_LINEAR, 2.0 * (double)(prof_rows >= 0 ? prof_rows : M_max) * (double)N * (double)K, stream);
-  return launch_whole_k(g, linear_f32_route({M_max, N, K, lda, ldw, 0, sk != nullptr, true, prof_rows, true}), sk, stream);
+  return launch_whole_k(g, linear_f32_route({M_max, N, K, lda, ldw, 0, sk != nullptr, true, prof_rows, true, grid_cap}), sk, stream);
 }
 
 // bf16 operands (fp32 accumulate, fp32 output): the precision mode of config C5.  Same tiling as the fp32 linears on

@@ -46,7 +46,10 @@ int64_t gdr_launch_count(void);
  * kernels is bracketed by a hipEvent pair recorded on the stream it is launched on.  Process-global, not
  * thread-safe, off by default (then no event is created or recorded).  gdr_prof_collect synchronises,
  * fills three host arrays of length 8 indexed by kernel class {0 linear GEMM, 1 sim sample GEMM,
- * 2 sim filter GEMM} with {launch count, total ms, total flops}, and disables the profiler again. */
+ * 2 sim filter GEMM} with {launch count, total ms, total flops}, and disables the profiler again.
+ * total ms of a class is the length of the UNION of its launches' [start, stop] intervals on one time axis, not the sum
+ * of their durations: launches that overlap (the two chains of gdr_t5_encoder_forward_ragged, two batches in flight on
+ * two streams) share the chip, and summing them would count that time twice.  Without overlap the two are equal. */
 int gdr_prof_enable(int max_events);
 int gdr_prof_collect(int64_t* launches, double* total_ms, double* total_work);
 /* Sampling: while the gate is 0 an enabled profiler records nothing (and costs nothing).  Two hipEventRecord packets per launch are
@@ -204,7 +207,18 @@ int gdr_t5_encoder_forward(const GdrT5EncoderWeights* w, const int64_t* ids, con
  *     form, the bf16 mode and the split form never read the field.
  *   - pooled-only, last block (GDR_ENC_LAST_Q_CLS, see README): k and v over every live row, q for the B CLS rows alone
  *     (gather, un-split linear, scatter into the q columns); the other q rows are stale and feed attention lanes whose
- *     output nothing reads. */
+ *     output nothing reads.
+ * Two chains (GDR_ENC_CHAINS=1|2, read once per process; default 2): a pooled-only fp32 call (out_hidden == NULL) whose halves
+ * [0, B/2) and [B/2, B) each reach those 192 tiles, with at least two layers, runs the halves as two independent forwards, the
+ * first on `stream`, the second on a library-owned side stream forked from and joined to `stream` by events before the call
+ * returns: the caller sees one stream-ordered call, and a stream capture of it stays legal.  Every persistent / stream-K linear
+ * of a chain is launched on 256 workgroups, so the call never has more than 512 of them in flight (the co-residency the
+ * stream-K hand-off assumes).  Same bits as one chain.  Calls with out_hidden, the bf16 and split forms and the padded form
+ * always run one chain.
+ * Workspace size rule: S1(B) = the one-chain layout for B sequences (activations for B*L rows, one split-K / stream-K region,
+ * the pack plan and the CLS tail's rows).  gdr_t5_encoder_ragged_workspace_bytes = S1(B) when the halves do not qualify, else
+ * max(S1(B), S1(B/2) + S1(B - B/2)): each chain owns a whole layout — its own stream-K hand-off scratch, flags and epoch
+ * included — which adds about one split-K region (112 MiB) to S1(B).  The size does not depend on the knob. */
 size_t gdr_t5_encoder_ragged_workspace_bytes(const GdrT5Dims* dims, int B, int L);
 int gdr_t5_encoder_forward_ragged(const GdrT5EncoderWeights* w, const int64_t* ids, const int64_t* mask, int B, int L,
                                   float* out_hidden, float* out_pooled, int64_t live_rows_hint, void* workspace,
