@@ -17,6 +17,7 @@ RERANK_ROW_QUERIES = 8           # q holds a row per (query, segment); 4 stays a
 SIM_EXHAUSTIVE = 1
 SIM_NO_STREAM = 2
 SIM_LIVE_MASK = 4                # the workspace starts with a live-row bitmap (ops.LiveRows): rank the live rows only
+SIM_QUERY_MASK = 8               # the workspace starts with one row bitmap per query (ops.QueryRows): rank query q's allowed rows only
 EPI_NONE, EPI_RESIDUAL, EPI_RELU, EPI_BIAS, EPI_BIAS_RELU, EPI_BIAS_RESIDUAL, EPI_BIAS_GELU = range(7)
 # gdr_linear_f32_form (include/gdr_hip.h GDR_F32_FORM_*): the kernel form of a dense fp32 linear; 0 = a shape the linear refuses
 (F32_FORM_TILES, F32_FORM_PERSISTENT, F32_FORM_SMALL, F32_FORM_SMALL_SPLITK, F32_FORM_SPLITK, F32_FORM_STREAMK_256,

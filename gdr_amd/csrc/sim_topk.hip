@@ -37,8 +37,8 @@ struct SimPlan {
 
 // survivors: by how much the filter pass's threshold admits more docs than the k-th largest sample score would (1 = that score
 // itself; the pre-filter lowers it by 2 eps_q, see prefilter_survivor_factor).
-// base: bytes in front of the plan's own scratch (GDR_SIM_LIVE_MASK: the caller's row bitmap, live_mask_bytes) — every offset and
-// the total move by it; 0 for every other call.
+// base: bytes in front of the plan's own scratch (GDR_SIM_LIVE_MASK: the caller's row bitmap, live_mask_bytes; GDR_SIM_QUERY_MASK:
+// one such bitmap per query, B of them) — every offset and the total move by it; 0 for every other call.
 static SimPlan make_plan(int B, int64_t N, int k, bool exhaustive, double survivors = 1.0, size_t base = 0) {
   SimPlan p{};
   p.tiles_m = (N + TILE - 1) / TILE;
@@ -641,25 +641,30 @@ static size_t live_mask_bytes(int64_t N) {
 }
 
 constexpr int MASK_THREADS = 256;
+// GDR_SIM_QUERY_MASK is the same sequence with a bitmap PER QUERY: B bitmaps of live_mask_bytes(N) each in front of the plan, bitmap
+// q at word q * qstride.  The mask pass reads list q against bitmap q (qstride = 0: the one bitmap of GDR_SIM_LIVE_MASK, the special
+// case where every query's bitmap is the same), and the fix-up counts per query.  A workgroup of the mask pass works on one query
+// at a time (blockIdx.y), so its bitmap reads stay inside one 40 KB region (N = 320 000) that L2 keeps.
 // Entries [lo, hi) of every query's list (blockIdx.y strides the queries), hi = hi_fixed (the sample block: the counter is not set yet) or, with hi_fixed < 0,
 // min(cnt[q], cap): an entry whose row is dead becomes (-inf, -1).  A thread takes four consecutive entries — lo and cap are
 // multiples of four (of TILE), so a group never leaves the list — loads their ids as one int4, and touches the scores only where
 // a row is dead.  Entries of a group past hi are written back as they were read.  An id outside [0, N) cannot reach the bitmap.
 __global__ __launch_bounds__(MASK_THREADS) void sim_live_mask_kernel(float* __restrict__ cand_val, int32_t* __restrict__ cand_idx,
                                                                      const int32_t* __restrict__ cnt, int64_t cap, int64_t lo,
-                                                                     int64_t hi_fixed, const uint32_t* __restrict__ live, int64_t N,
-                                                                     int B) {
+                                                                     int64_t hi_fixed, const uint32_t* __restrict__ live,
+                                                                     int64_t qstride, int64_t N, int B) {
   const int64_t step = (int64_t)gridDim.x * MASK_THREADS * 4;
   for (int64_t q = blockIdx.y; q < B; q += gridDim.y) {
     int64_t hi = hi_fixed >= 0 ? hi_fixed : (int64_t)cnt[q * CNT_STRIDE];
     if (hi > cap) hi = cap;
     float* cv = cand_val + q * cap;
     int32_t* ci = cand_idx + q * cap;
+    const uint32_t* lq = live + q * qstride;
     for (int64_t i = lo + ((int64_t)blockIdx.x * MASK_THREADS + threadIdx.x) * 4; i < hi; i += step) {
       int4 id = *reinterpret_cast<const int4*>(ci + i);
       auto dead = [&](int32_t r, int j) -> bool {
         if (i + j >= hi || r < 0) return false;  // past the list / padding already
-        return r >= N || ((live[r >> 5] >> (r & 31)) & 1u) == 0u;
+        return r >= N || ((lq[r >> 5] >> (r & 31)) & 1u) == 0u;
       };
       const bool d0 = dead(id.x, 0), d1 = dead(id.y, 1), d2 = dead(id.z, 2), d3 = dead(id.w, 3);
       if (d0 || d1 || d2 || d3) {
@@ -680,9 +685,14 @@ __global__ __launch_bounds__(MASK_THREADS) void sim_live_mask_kernel(float* __re
 // live sample count depends on the bitmap and the plan alone (the same for every query): one workgroup counts it and, if it is
 // short, lowers every thr[q] to -inf.  The filter pass then keeps every row: either the whole corpus fits the list (exact), or the
 // list overflows and status[q] = 1 sends the query to the exhaustive re-run, as for any overflow.
-__global__ __launch_bounds__(256) void sim_live_thr_fixup_kernel(const uint32_t* __restrict__ live, int64_t N, int64_t n_sample_tiles,
-                                                                 int stride, int k, float* __restrict__ thr, int B) {
+// qstride > 0 (GDR_SIM_QUERY_MASK): the count is a property of query q's own bitmap, so workgroup q (a grid of B) counts bitmap q and
+// lowers thr[q] alone — a query with a narrow filter must not cost the others their thresholds, and a single count over any one
+// bitmap would say nothing about the rest.
+__global__ __launch_bounds__(256) void sim_live_thr_fixup_kernel(const uint32_t* __restrict__ live, int64_t qstride, int64_t N,
+                                                                 int64_t n_sample_tiles, int stride, int k, float* __restrict__ thr,
+                                                                 int B) {
   __shared__ int red[4];
+  live += (int64_t)blockIdx.x * qstride;
   const int64_t n_words = (N + 31) / 32;
   int c = 0;
   for (int64_t e = threadIdx.x; e < n_sample_tiles * (TILE / 32); e += 256) {
@@ -699,17 +709,21 @@ __global__ __launch_bounds__(256) void sim_live_thr_fixup_kernel(const uint32_t*
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = c;
   __syncthreads();
   if (red[0] + red[1] + red[2] + red[3] >= k) return;
+  if (qstride) {
+    if (threadIdx.x == 0) thr[blockIdx.x] = -INFINITY;
+    return;
+  }
   for (int q = threadIdx.x; q < B; q += 256) thr[q] = -INFINITY;
 }
 
-static int launch_live_mask(const SimEpilogue& ep, const SimPlan& p, int B, int64_t lo, int64_t hi_fixed, const uint32_t* live, int64_t N,
-                            hipStream_t stream) {
+static int launch_live_mask(const SimEpilogue& ep, const SimPlan& p, int B, int64_t lo, int64_t hi_fixed, const uint32_t* live,
+                            int64_t qstride, int64_t N, hipStream_t stream) {
   const int64_t span = (hi_fixed >= 0 ? hi_fixed : p.cap) - lo;
   if (span <= 0) return GDR_OK;
   int64_t gx = (span + MASK_THREADS * 4 - 1) / (MASK_THREADS * 4);
   if (gx > 64) gx = 64;
   hipLaunchKernelGGL(sim_live_mask_kernel, dim3((unsigned)gx, (unsigned)(B < 65535 ? B : 65535)), dim3(MASK_THREADS), 0, stream, ep.cand_val,
-                     ep.cand_idx, (const int32_t*)ep.cand_cnt, p.cap, lo, hi_fixed, live, N, B);
+                     ep.cand_idx, (const int32_t*)ep.cand_cnt, p.cap, lo, hi_fixed, live, qstride, N, B);
   GDR_CHECK_LAUNCH("sim_live_mask_kernel");
   return GDR_OK;
 }
@@ -726,6 +740,9 @@ extern "C" size_t gdr_sim_topk_workspace_bytes(int B, int64_t N, int d, int k, i
   (void)d;
   if (B <= 0 || N <= 0 || k <= 0) return 0;
   const bool exhaustive = (flags & GDR_SIM_EXHAUSTIVE) != 0;
+  if ((flags & GDR_SIM_LIVE_MASK) && (flags & GDR_SIM_QUERY_MASK)) return 0;  // no such call: gdr_sim_topk refuses the pair
+  if (flags & GDR_SIM_QUERY_MASK)  // one row bitmap per query in front of the same plan
+    return gdr_sim_topk_workspace_bytes(B, N, d, k, flags & ~GDR_SIM_QUERY_MASK) + (size_t)B * gdr::live_mask_bytes(N);
   if (flags & GDR_SIM_LIVE_MASK)  // the caller's row bitmap in front of the same plan
     return gdr_sim_topk_workspace_bytes(B, N, d, k, flags & ~GDR_SIM_LIVE_MASK) + gdr::live_mask_bytes(N);
   size_t best = gdr::make_plan(B, N, k, exhaustive).total;
@@ -810,9 +827,15 @@ int gdr::sim_topk_impl(const void* Q, int B, const void* D, int64_t N, int d, in
                 (long long)N);
   GDR_CHECK_ARG(((uintptr_t)Q & 15) == 0 && ((uintptr_t)D & 15) == 0 && ((uintptr_t)workspace & 255) == 0,
                 "sim_topk: Q, D must be 16-byte and workspace 256-byte aligned");
-  // GDR_SIM_LIVE_MASK: the first live_mask_bytes(N) bytes of the workspace are the caller's row bitmap (read only); the plan sits behind it
-  const bool masked = (flags & GDR_SIM_LIVE_MASK) != 0;
-  const SimPlan p = make_plan(B, N, k, (flags & GDR_SIM_EXHAUSTIVE) != 0, 1.0, masked ? live_mask_bytes(N) : 0);
+  GDR_CHECK_ARG((flags & (GDR_SIM_LIVE_MASK | GDR_SIM_QUERY_MASK)) != (GDR_SIM_LIVE_MASK | GDR_SIM_QUERY_MASK),
+                "sim_topk: GDR_SIM_LIVE_MASK and GDR_SIM_QUERY_MASK name two workspace layouts: AND the live rows into the per-query "
+                "bitmaps on the caller's side and pass GDR_SIM_QUERY_MASK alone");
+  // GDR_SIM_LIVE_MASK: the first live_mask_bytes(N) bytes of the workspace are the caller's row bitmap (read only); the plan sits behind it.
+  // GDR_SIM_QUERY_MASK: B such bitmaps, query q's at byte q * live_mask_bytes(N).
+  const bool per_query = (flags & GDR_SIM_QUERY_MASK) != 0;
+  const bool masked = per_query || (flags & GDR_SIM_LIVE_MASK) != 0;
+  const int64_t qstride = per_query ? (int64_t)(live_mask_bytes(N) / sizeof(uint32_t)) : 0;  // words between two queries' bitmaps
+  const SimPlan p = make_plan(B, N, k, (flags & GDR_SIM_EXHAUSTIVE) != 0, 1.0, masked ? (per_query ? (size_t)B : 1) * live_mask_bytes(N) : 0);
   // A masked call is held to the size its caller was told, not to this k's own layout (which may dip below the unflagged answer,
   // see gdr_sim_topk_workspace_bytes): a buffer sized without the flag — no room reserved for the bitmap — is refused at every shape.
   const size_t required = masked ? gdr_sim_topk_workspace_bytes(B, N, d, k, flags) : p.total;
@@ -835,7 +858,7 @@ int gdr::sim_topk_impl(const void* Q, int B, const void* D, int64_t N, int d, in
   const bool stream_mode = sim_stream_supported(B, d, bf16) && !(flags & GDR_SIM_NO_STREAM);
   int rc = stream_mode ? launch_sim_stream(D, N, Q, B, d, ep, bf16, stream) : launch_sim_gemm(D, N, Q, B, d, ep, bf16, stream);
   if (rc) return rc;
-  if (masked) GDR_TRY(launch_live_mask(ep, p, B, 0, p.n_slots, live, N, stream));  // the threshold sees live sample scores only
+  if (masked) GDR_TRY(launch_live_mask(ep, p, B, 0, p.n_slots, live, qstride, N, stream));  // the threshold sees live sample scores only
   const int sel_threads = 1024;  // 1024 lanes per query: measured faster than 512 with twice the entries per lane (26.7 vs 37.7 us at 32 queries)
   const int kpad = sel_pow2(k, 1);
   static const bool sliced_on = [] {
@@ -860,14 +883,15 @@ int gdr::sim_topk_impl(const void* Q, int B, const void* D, int64_t N, int d, in
     GDR_CHECK_LAUNCH("sim_threshold_kernel");
   }
   if (p.stride > 1) {
-    if (masked) {  // fewer than k live sample rows: thr[q] = -inf (sim_live_thr_fixup_kernel)
-      hipLaunchKernelGGL(sim_live_thr_fixup_kernel, dim3(1), dim3(256), 0, stream, live, N, p.n_sample_tiles, p.stride, k, thr, B);
+    if (masked) {  // fewer than k live sample rows (per query: of query q's bitmap): thr[q] = -inf (sim_live_thr_fixup_kernel)
+      hipLaunchKernelGGL(sim_live_thr_fixup_kernel, dim3(per_query ? B : 1), dim3(256), 0, stream, live, qstride, N, p.n_sample_tiles,
+                         p.stride, k, thr, B);
       GDR_CHECK_LAUNCH("sim_live_thr_fixup_kernel");
     }
     ep.mode = 2;
     rc = stream_mode ? launch_sim_stream(D, N, Q, B, d, ep, bf16, stream) : launch_sim_gemm(D, N, Q, B, d, ep, bf16, stream);
     if (rc) return rc;
-    if (masked) GDR_TRY(launch_live_mask(ep, p, B, p.n_slots, -1, live, N, stream));  // the survivors, dead rows among them
+    if (masked) GDR_TRY(launch_live_mask(ep, p, B, p.n_slots, -1, live, qstride, N, stream));  // the survivors, dead rows among them
   }
   if (ns_sel) {
     sa.NS = ns_sel;

@@ -233,14 +233,108 @@ class LiveRows:
         return ((self._words[j >> 5].to(torch.int64) >> (j & 31)) & 1).to(torch.bool)
 
 
-def _sim_topk_raw(Q, D, k, idx_offset, workspace, flags, live=None):
+class QueryRows:
+    """Which rows of a corpus each of B queries may be given, as gdr_sim_topk's GDR_SIM_QUERY_MASK reads it: one bitmap per query in
+    LiveRows' format, `words` int32 [B, ceil(n / 32)], bit r % 32 of word [q, r // 32] is 1 when row r is allowed for query q.  The
+    words stay on `device` (any torch device: everything here is torch ops) and nothing is read back; counts() is a device tensor.
+    QueryRows(B, n, device) allows nothing; bits past n in the last word are kept 0 by the constructors and ignored by every reader."""
+
+    def __init__(self, B, n, device):
+        self.B, self.n = int(B), int(n)
+        self._words = torch.zeros((self.B, max((self.n + 31) // 32, 1)), dtype=torch.int32, device=device)
+        self.device = self._words.device
+
+    @property
+    def words(self):
+        """int32 [B, ceil(n / 32)]: the bitmaps (a view of the backing buffer)."""
+        return self._words[:, :(self.n + 31) // 32]
+
+    @classmethod
+    def from_bool(cls, allowed):
+        """allowed: bool [B, n] (True = row may be returned for that query), on the device the bitmaps are to stay on."""
+        allowed = torch.as_tensor(allowed).to(torch.bool)
+        if allowed.dim() != 2:
+            raise _ffi.GdrError(f"QueryRows.from_bool: a bool [B, n] tensor, not {tuple(allowed.shape)}")
+        out = cls(allowed.shape[0], allowed.shape[1], allowed.device)
+        if out.B and out.n:
+            sh = torch.arange(32, dtype=torch.int32, device=allowed.device)   # 1 << 31 wraps to -2^31: distinct bits, every sum an int32
+            for lo in range(0, out.B, 64):                                    # 64 queries at a time bound the int32 [*, 32 W] temporary
+                bits = torch.nn.functional.pad(allowed[lo:lo + 64], (0, -out.n % 32)).view(-1, out._words.shape[1], 32)
+                out._words[lo:lo + 64] = (bits.to(torch.int32) << sh).sum(-1, dtype=torch.int32)
+        return out
+
+    @classmethod
+    def _from_ids(cls, ids, n, device, denied):
+        ids = list(ids)
+        dev = torch.device(device) if device is not None else (torch.as_tensor(ids[0]).device if ids else torch.device("cpu"))
+        mask = torch.full((len(ids), int(n)), bool(denied), dtype=torch.bool, device=dev)
+        for q, r in enumerate(ids):
+            r = torch.as_tensor(r).reshape(-1).to(torch.int64)
+            if r.numel() == 0:
+                continue
+            if int(r.min()) < 0 or int(r.max()) >= n:                    # where the ids are: no sync for host ids
+                raise _ffi.GdrError(f"QueryRows: row ids must lie in [0, {int(n)})")
+            mask[q, r.to(dev)] = not denied
+        return cls.from_bool(mask)
+
+    @classmethod
+    def from_allowed(cls, ids, n, device=None):
+        """ids: B tensors / lists of row ids in [0, n), query q's allowed rows (repeats are fine); everything else is denied."""
+        return cls._from_ids(ids, n, device, False)
+
+    @classmethod
+    def from_denied(cls, ids, n, device=None):
+        """ids: B tensors / lists of row ids in [0, n), the rows query q must not be given; everything else is allowed."""
+        return cls._from_ids(ids, n, device, True)
+
+    def to_bool(self):
+        """bool [B, n] on the device (tests, debugging)."""
+        j = torch.arange(self.n, device=self.device)
+        return ((self._words[:, j >> 5].to(torch.int64) >> (j & 31)) & 1).to(torch.bool)
+
+    def counts(self):
+        """int64 [B] on the device: how many rows each query allows (bits past n are not counted).  No read-back."""
+        x = self.words.to(torch.int64) & 0xFFFFFFFF
+        if self.n % 32 and x.numel():
+            x = torch.cat([x[:, :-1], x[:, -1:] & ((1 << (self.n % 32)) - 1)], 1)
+        x = x - ((x >> 1) & 0x55555555)
+        x = (x & 0x33333333) + ((x >> 2) & 0x33333333)
+        x = (x + (x >> 4)) & 0x0F0F0F0F
+        return (((x * 0x01010101) >> 24) & 0xFF).sum(1)
+
+    def and_(self, live):
+        """In place: a row stays allowed only where `live` (a LiveRows over the same n rows, on this device) has it live."""
+        if not isinstance(live, LiveRows) or live.n != self.n or live.device != self.device:
+            raise _ffi.GdrError(f"QueryRows.and_: an ops.LiveRows over the same {self.n} rows, on the same device")
+        self.words.bitwise_and_(live.words)
+        return self
+
+    def rows(self, idx):
+        """The QueryRows of the sub-batch idx (a tensor / list of query numbers): a copy."""
+        idx = torch.as_tensor(idx, device=self.device).reshape(-1).to(torch.int64)
+        out = QueryRows(idx.numel(), self.n, self.device)
+        out._words = self._words[idx]
+        return out
+
+
+def _sim_topk_raw(Q, D, k, idx_offset, workspace, flags, live=None, allowed=None):
     B, d = Q.shape
     N = D.shape[0]
-    if live is not None:
+    if allowed is not None:
+        flags |= _ffi.SIM_QUERY_MASK                                 # one layout per call: live is ANDed in below
+    elif live is not None:
         flags |= _ffi.SIM_LIVE_MASK
     need = lib().gdr_sim_topk_workspace_bytes(B, N, d, k, flags)
     ws = (workspace or Workspace(Q.device)).get(need)
-    if live is not None:                                             # the bitmap is the head of the workspace (stream-ordered copy)
+    if allowed is not None:                                          # B bitmaps, M bytes apart, are the head of the workspace
+        words = allowed.words
+        M = (4 * words.shape[1] + 255) // 256 * 256
+        slots = ws[:B * M].view(torch.int32).view(B, M // 4)[:, :words.shape[1]]   # the padding up to M is ignored: left as it is
+        if live is not None:
+            torch.bitwise_and(words, live.words, out=slots)
+        else:
+            slots.copy_(words)
+    elif live is not None:                                           # the bitmap is the head of the workspace (stream-ordered copy)
         words = live.words
         ws[:words.numel() * 4].view(torch.int32).copy_(words)
     vals = torch.empty((B, k), dtype=torch.float32, device=Q.device)
@@ -252,7 +346,7 @@ def _sim_topk_raw(Q, D, k, idx_offset, workspace, flags, live=None):
     return vals, idx, status
 
 
-def sim_topk(Q, D, k, idx_offset=0, workspace=None, return_status=False, exact_on_overflow=True, flags=0, live=None):
+def sim_topk(Q, D, k, idx_offset=0, workspace=None, return_status=False, exact_on_overflow=True, flags=0, live=None, allowed=None):
     """Fused Q·Dᵀ + per-row top-k — gdr_sim_topk.  Returns (values fp32[B,k], indices int32[B,k]), 1 <= k <= min(SIM_TOPK_MAX_K, N).
     D may be an fp32 or bf16 tensor, or a PrefilteredCorpus: the pre-filter serves k <= PREFILTER_MAX_K, a deeper list is the
     plain fp32 call over its rows (the same answer: both return the top-k of the fp32 scores for every input).
@@ -263,11 +357,17 @@ def sim_topk(Q, D, k, idx_offset=0, workspace=None, return_status=False, exact_o
     and the device status tensor (1 = that row is the top-k of a subset) is theirs to act on.  flags: _ffi.SIM_* bits.
     live: a LiveRows over the N rows of D — the top-k over its live rows only (GDR_SIM_LIVE_MASK; k <= live.count): the list the
     call would return for the matrix of the live rows, with their ids in D.  A PrefilteredCorpus is then searched on the plain fp32
-    path (the pre-filter has no mask; the same answer), and the overflow re-run carries the mask."""
+    path (the pre-filter has no mask; the same answer), and the overflow re-run carries the mask.
+    allowed: a QueryRows (allowed.B == B, allowed.n == N, on D's device) — row q is the top-k over the rows query q's own bitmap
+    allows (GDR_SIM_QUERY_MASK): a filter per query in ONE call.  With live= as well the two are ANDed on their way into the
+    workspace, so a dead row never returns whatever the filter says.  How many rows a query allows is known on the device only,
+    so nothing raises for a short one: a row with fewer than k allowed (and live) documents ends in -inf / -1.  A PrefilteredCorpus
+    is searched on the plain fp32 path, as for live=.  A query whose filter keeps a small fraction of the rows overflows its
+    candidate list (include/gdr_hip.h, NARROW FILTERS) and is re-run exhaustively with its bitmap: exact, and slower."""
     prefilter = isinstance(D, PrefilteredCorpus)
     if prefilter:
         P, D = D, D.D
-        if (live is not None or Q.shape[0] < PREFILTER_MIN_BATCH or D.shape[1] % 8 or D.shape[1] > 1024 or (flags & _ffi.SIM_EXHAUSTIVE) or k > PREFILTER_MAX_K
+        if (live is not None or allowed is not None or Q.shape[0] < PREFILTER_MIN_BATCH or D.shape[1] % 8 or D.shape[1] > 1024 or (flags & _ffi.SIM_EXHAUSTIVE) or k > PREFILTER_MAX_K
                 or not P.dnorm_max > 0.0):                               # an all-zero corpus has no band: the fp32 path serves it
             prefilter = False
     _need_cuda(Q, D)
@@ -283,12 +383,15 @@ def sim_topk(Q, D, k, idx_offset=0, workspace=None, return_status=False, exact_o
     if live is not None:
         if not isinstance(live, LiveRows) or live.n != D.shape[0] or live.device != D.device:
             raise _ffi.GdrError(f"sim_topk: live must be an ops.LiveRows over the {D.shape[0]} rows of D, on its device")
-        if k > live.count:
+        if k > live.count and allowed is None:
             raise RuntimeError("selected index k out of range")      # as torch.topk over the live rows would
+    if allowed is not None:
+        if not isinstance(allowed, QueryRows) or allowed.B != Q.shape[0] or allowed.n != D.shape[0] or allowed.device != D.device:
+            raise _ffi.GdrError(f"sim_topk: allowed must be an ops.QueryRows of {Q.shape[0]} queries over the {D.shape[0]} rows of D, on its device")
     if prefilter:
         vals, idx, status = _sim_topk_prefilter_raw(Q, P, k, idx_offset, workspace)
     else:
-        vals, idx, status = _sim_topk_raw(Q, D, k, idx_offset, workspace, flags, live)
+        vals, idx, status = _sim_topk_raw(Q, D, k, idx_offset, workspace, flags, live, allowed)
     if exact_on_overflow:
         bad = torch.nonzero(status).flatten()
         _ffi.check_device_fault("sim_topk")                              # nonzero() synchronised
@@ -296,7 +399,8 @@ def sim_topk(Q, D, k, idx_offset=0, workspace=None, return_status=False, exact_o
             for lo in range(0, bad.numel(), 64):                     # bounded workspace: 64 queries * N * 8 B
                 rows = bad[lo:lo + 64]
                 v2, i2, _ = _sim_topk_raw(Q[rows].contiguous(), D, k, idx_offset, None,
-                                          _ffi.SIM_EXHAUSTIVE | (flags & _ffi.SIM_NO_STREAM), live)   # the core the caller chose
+                                          _ffi.SIM_EXHAUSTIVE | (flags & _ffi.SIM_NO_STREAM), live,   # the core the caller chose
+                                          allowed.rows(rows) if allowed is not None else None)
                 vals[rows], idx[rows] = v2, i2
             status = torch.zeros_like(status)
     return (vals, idx, status) if return_status else (vals, idx)

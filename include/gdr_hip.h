@@ -289,10 +289,27 @@ int gdr_t5_encoder_forward_bf16(const GdrT5EncoderWeights* w, const int64_t* ids
  *   GDR_SIM_EXHAUSTIVE | GDR_SIM_LIVE_MASK.  With the flag clear nothing changes: layout, launches and results are as before.
  *   gdr_sim_topk_prefilter takes no flags and stays UNMASKED: a masked search over such a corpus is gdr_sim_topk's (the same fp32
  *   answer by that entry point's own contract).
+ * GDR_SIM_QUERY_MASK (gdr_sim_topk, gdr_sim_topk_bf16): a row filter PER QUERY.  The first B * M bytes of `workspace` (M as above) are
+ *   then the caller's input: B bitmaps in GDR_SIM_LIVE_MASK's format, bitmap q at byte q * M; bit r % 32 of its int32 word r / 32 set =
+ *   row r of D may be returned for query q.  Bits past N and the padding up to M are ignored, the library only reads the region, its
+ *   scratch starts behind it, and gdr_sim_topk_workspace_bytes(.., flags | GDR_SIM_QUERY_MASK) = the size for `flags` + B * M (a smaller
+ *   workspace is GDR_ENOSPC before any launch).  Row q of the result is the top-k over the rows bitmap q allows: scores, tie rule and
+ *   ids are those of the unflagged call, the tail of a list with fewer than k allowed rows is -inf / -1, status[q] speaks for query q
+ *   alone.  It is GDR_SIM_LIVE_MASK's sequence with bitmap q read for list q, and the count of allowed sample rows taken per query:
+ *   a query with fewer than k of them loses its own threshold only.  Both flags in one call are GDR_EINVAL (two layouts; the size asked for the pair is 0): AND the live
+ *   rows into the per-query bitmaps and pass this flag alone.  GDR_SIM_EXHAUSTIVE and GDR_SIM_NO_STREAM combine with it as with the live mask.
+ *   NARROW FILTERS: a disallowed row that reaches the threshold still takes a slot of the candidate list until the second mask pass
+ *   drops it, and the list holds 4 x the survivors expected of an unfiltered query.  A query whose filter keeps a small fraction of
+ *   the rows therefore overflows: status[q] = 1, and the re-run with GDR_SIM_EXHAUSTIVE | GDR_SIM_QUERY_MASK is exact and slower.
+ *   Measured at N = 320 000, d = 768, k = 100 with independent random filters (tools/bench_query_mask.py,
+ *   profiles/r22_query_mask_bench.jsonl): no query of 512 overflows with 50 % of the rows kept, 1 with 30 %, 33 with 25 %, 313 with
+ *   20 %, 509 with 15 %, all with 10 % — overflow begins where a filter keeps less than about 30 % of the rows and is the rule below
+ *   20 %.  The fraction moves with the plan (k, N): it is where k N / (f n_sample) passes the list's 4 k N / n_sample + 4096 slots.
  * ---------------------------------------------------------------------------------------------- */
 #define GDR_SIM_EXHAUSTIVE 1
 #define GDR_SIM_NO_STREAM 2   /* force the tiled GEMM core even at B <= 32 (A/B testing of the latency-mode kernel) */
 #define GDR_SIM_LIVE_MASK 4   /* workspace starts with a live-row bitmap; rank the live rows only */
+#define GDR_SIM_QUERY_MASK 8  /* workspace starts with one row bitmap per query; rank query q's allowed rows only */
 size_t gdr_sim_topk_workspace_bytes(int B, int64_t N, int d, int k, int flags);
 int gdr_sim_topk(const float* Q, int B, const float* D, int64_t N, int d, int k, int32_t idx_offset,
                  float* out_val, int32_t* out_idx, int32_t* status, int flags, void* workspace,
