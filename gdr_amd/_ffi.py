@@ -18,6 +18,15 @@ SIM_EXHAUSTIVE = 1
 SIM_NO_STREAM = 2
 SIM_LIVE_MASK = 4                # the workspace starts with a live-row bitmap (ops.LiveRows): rank the live rows only
 SIM_QUERY_MASK = 8               # the workspace starts with one row bitmap per query (ops.QueryRows): rank query q's allowed rows only
+SIM_ROW_GATHER = 16              # with SIM_QUERY_MASK: score only the rows bitmap q allows (the mode for narrow filters)
+
+
+def sim_gather_chunks(c):
+    """GDR_SIM_GATHER_CHUNKS(c): bits 8..16 of gdr_sim_topk's flags, the per-query list capacity of SIM_ROW_GATHER in chunks of 4096
+    rows (1 .. 256; 0 reads as 2)."""
+    return int(c) << 8
+
+
 EPI_NONE, EPI_RESIDUAL, EPI_RELU, EPI_BIAS, EPI_BIAS_RELU, EPI_BIAS_RESIDUAL, EPI_BIAS_GELU = range(7)
 # gdr_linear_f32_form (include/gdr_hip.h GDR_F32_FORM_*): the kernel form of a dense fp32 linear; 0 = a shape the linear refuses
 (F32_FORM_TILES, F32_FORM_PERSISTENT, F32_FORM_SMALL, F32_FORM_SMALL_SPLITK, F32_FORM_SPLITK, F32_FORM_STREAMK_256,

@@ -182,6 +182,11 @@ int launch_cast_f32_bf16(const float* in, void* out_bf16, int64_t n, hipStream_t
 bool sim_stream_supported(int B, int d, bool bf16);
 int launch_sim_stream(const void* D, int64_t N, const void* Q, int B, int d, const SimEpilogue& ep, bool bf16, hipStream_t stream);
 
+// gather top-k for narrow per-query filters (sim_rows.hip; GDR_SIM_ROW_GATHER): the layout behind the B bitmaps, and the launches
+size_t sim_rows_workspace_bytes(int B, int64_t cap, int k);
+int launch_sim_rows(const void* Q, int B, const void* D, int64_t N, int d, int k, int32_t idx_offset, float* out_val, int32_t* out_idx,
+                    int32_t* status, const uint32_t* bitmaps, int64_t qstride, int64_t cap, void* ws, bool bf16, hipStream_t stream);
+
 // Sums / maxima over the 64 lanes as the xor butterfly 32, 16, 8, 4, 2, 1 (every lane ends with the total).  The four steps
 // inside a row of 16 lanes are DPP row rotations: after the xor-16 step the values have period 16, so "rotate by 8" pairs lane i
 // with lane i ^ 8 exactly; the values then have period 8 inside the row, so "rotate by 4" meets the partner "xor 4" would

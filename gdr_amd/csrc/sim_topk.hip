@@ -640,6 +640,15 @@ static size_t live_mask_bytes(int64_t N) {
   return align_up((size_t)((N + 31) / 32) * sizeof(uint32_t), 256);
 }
 
+// GDR_SIM_ROW_GATHER (sim_rows.hip): bits 8..16 of flags hold the per-query list capacity in chunks of SEL_CHUNK rows, 0 reads as 2.
+constexpr int SIM_GATHER_CHUNK_BITS = 0x1FF << 8, SIM_GATHER_MAX_CHUNKS = 256;
+// rows per query of a gather call; 0 = no such call (a field above 256 chunks, or a field without the flag)
+static int64_t sim_gather_cap(int flags) {
+  const int c = (flags & SIM_GATHER_CHUNK_BITS) >> 8;
+  if (!(flags & GDR_SIM_ROW_GATHER) || c > SIM_GATHER_MAX_CHUNKS) return 0;
+  return (int64_t)SEL_CHUNK * (c ? c : 2);
+}
+
 constexpr int MASK_THREADS = 256;
 // GDR_SIM_QUERY_MASK is the same sequence with a bitmap PER QUERY: B bitmaps of live_mask_bytes(N) each in front of the plan, bitmap
 // q at word q * qstride.  The mask pass reads list q against bitmap q (qstride = 0: the one bitmap of GDR_SIM_LIVE_MASK, the special
@@ -740,6 +749,13 @@ extern "C" size_t gdr_sim_topk_workspace_bytes(int B, int64_t N, int d, int k, i
   (void)d;
   if (B <= 0 || N <= 0 || k <= 0) return 0;
   const bool exhaustive = (flags & GDR_SIM_EXHAUSTIVE) != 0;
+  if (flags & (GDR_SIM_ROW_GATHER | gdr::SIM_GATHER_CHUNK_BITS)) {  // the B bitmaps, then the gather layout: no N, no d behind them
+    const int64_t cap = gdr::sim_gather_cap(flags);
+    if (cap == 0 || (flags & (GDR_SIM_QUERY_MASK | GDR_SIM_LIVE_MASK | GDR_SIM_EXHAUSTIVE)) != GDR_SIM_QUERY_MASK ||
+        (cap > 2 * gdr::SEL_CHUNK && k > gdr::SIM_ONE_WAVE_MAX_K))
+      return 0;  // no such call: gdr_sim_topk refuses it
+    return (size_t)B * gdr::live_mask_bytes(N) + gdr::sim_rows_workspace_bytes(B, cap, k);
+  }
   if ((flags & GDR_SIM_LIVE_MASK) && (flags & GDR_SIM_QUERY_MASK)) return 0;  // no such call: gdr_sim_topk refuses the pair
   if (flags & GDR_SIM_QUERY_MASK)  // one row bitmap per query in front of the same plan
     return gdr_sim_topk_workspace_bytes(B, N, d, k, flags & ~GDR_SIM_QUERY_MASK) + (size_t)B * gdr::live_mask_bytes(N);
@@ -830,6 +846,28 @@ int gdr::sim_topk_impl(const void* Q, int B, const void* D, int64_t N, int d, in
   GDR_CHECK_ARG((flags & (GDR_SIM_LIVE_MASK | GDR_SIM_QUERY_MASK)) != (GDR_SIM_LIVE_MASK | GDR_SIM_QUERY_MASK),
                 "sim_topk: GDR_SIM_LIVE_MASK and GDR_SIM_QUERY_MASK name two workspace layouts: AND the live rows into the per-query "
                 "bitmaps on the caller's side and pass GDR_SIM_QUERY_MASK alone");
+  // GDR_SIM_ROW_GATHER: score only the rows bitmap q allows (sim_rows.hip).  No GEMM core runs, so GDR_SIM_NO_STREAM means nothing here.
+  if (flags & (GDR_SIM_ROW_GATHER | SIM_GATHER_CHUNK_BITS)) {
+    const int chunks = (flags & SIM_GATHER_CHUNK_BITS) >> 8;
+    GDR_CHECK_ARG(flags & GDR_SIM_ROW_GATHER, "sim_topk: GDR_SIM_GATHER_CHUNKS(%d) without GDR_SIM_ROW_GATHER: bits 8..16 of flags belong to that mode", chunks);
+    GDR_CHECK_ARG(!(flags & GDR_SIM_LIVE_MASK), "sim_topk: GDR_SIM_ROW_GATHER with GDR_SIM_LIVE_MASK: AND the live rows into the per-query bitmaps and "
+                  "pass GDR_SIM_QUERY_MASK | GDR_SIM_ROW_GATHER");
+    GDR_CHECK_ARG(flags & GDR_SIM_QUERY_MASK, "sim_topk: GDR_SIM_ROW_GATHER needs GDR_SIM_QUERY_MASK: the rows it scores are the ones the per-query bitmaps allow");
+    GDR_CHECK_ARG(!(flags & GDR_SIM_EXHAUSTIVE), "sim_topk: GDR_SIM_ROW_GATHER with GDR_SIM_EXHAUSTIVE: the gather list is already every allowed row; "
+                  "the exhaustive re-run of a query that allows more than its capacity is GDR_SIM_EXHAUSTIVE | GDR_SIM_QUERY_MASK");
+    GDR_CHECK_ARG(chunks <= SIM_GATHER_MAX_CHUNKS, "sim_topk: GDR_SIM_ROW_GATHER: GDR_SIM_GATHER_CHUNKS(%d) must be in [0, %d] (0 = 2)", chunks, SIM_GATHER_MAX_CHUNKS);
+    const int64_t cap = sim_gather_cap(flags);
+    GDR_CHECK_ARG(cap <= 2 * SEL_CHUNK || k <= SIM_ONE_WAVE_MAX_K, "sim_topk: GDR_SIM_ROW_GATHER: k=%d must be <= %d with GDR_SIM_GATHER_CHUNKS(%d) > 2 "
+                  "(chunks plus merge rounds; one LDS sort serves any k at 1 or 2 chunks)", k, SIM_ONE_WAVE_MAX_K, chunks);
+    GDR_CHECK_ARG((int64_t)B * (cap / 16) <= 0x7fffffffLL, "sim_topk: GDR_SIM_ROW_GATHER: B=%d x %lld rows per query leaves the int32 unit list", B, (long long)cap);
+    const size_t head = (size_t)B * live_mask_bytes(N), required = head + sim_rows_workspace_bytes(B, cap, k);
+    if (workspace_bytes < required) {
+      set_error("sim_topk: workspace %zu < required %zu", workspace_bytes, required);
+      return GDR_ENOSPC;
+    }
+    return launch_sim_rows(Q, B, D, N, d, k, idx_offset, out_val, out_idx, status, static_cast<const uint32_t*>(workspace),
+                           (int64_t)(live_mask_bytes(N) / sizeof(uint32_t)), cap, static_cast<char*>(workspace) + head, bf16, stream);
+  }
   // GDR_SIM_LIVE_MASK: the first live_mask_bytes(N) bytes of the workspace are the caller's row bitmap (read only); the plan sits behind it.
   // GDR_SIM_QUERY_MASK: B such bitmaps, query q's at byte q * live_mask_bytes(N).
   const bool per_query = (flags & GDR_SIM_QUERY_MASK) != 0;

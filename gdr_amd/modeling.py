@@ -297,16 +297,19 @@ class DenseModel:
 
     forward = __call__
 
-    def search(self, q_reps, p_reps, k, live=None, allowed=None):
+    def search(self, q_reps, p_reps, k, live=None, allowed=None, gather=None):
         """compute_similarity + topk(k) fused (never writes the score matrix). Returns (values, int64 indices).
         live: an ops.LiveRows over the rows of p_reps — rank its live rows only (k <= live.count); ids stay row numbers.
         allowed: an ops.QueryRows — a row filter per query (ANDed with live); a query with fewer than k allowed rows ends in -inf / -1.
+        gather: ops.sim_topk's, for a call with allowed=: None (default) routes by the filters' row counts ("auto": queries that allow
+        at most ops.GATHER_MAX_ROWS rows are scored over those rows only), False is the dense masked call, an int forces the gather mode.
         p_reps: the passage embeddings [N,d] (fp32, or bf16 = the C5 precision mode), or an ops.PrefilteredCorpus built from them once
         (the same fp32 top-k through the bf16 pre-filter, gdr_sim_topk_prefilter).  1 <= k <= min(ops.SIM_TOPK_MAX_K, N); past
         ops.PREFILTER_MAX_K a PrefilteredCorpus is searched on the plain fp32 path (the same list)."""
         if self._ws is None:
             self._ws = ops.Workspace(q_reps.device)
-        v, i = ops.sim_topk(q_reps.contiguous(), p_reps, k, workspace=self._ws, exact_on_overflow=True, live=live, allowed=allowed)
+        v, i = ops.sim_topk(q_reps.contiguous(), p_reps, k, workspace=self._ws, exact_on_overflow=True, live=live, allowed=allowed,
+                            gather="auto" if gather is None and allowed is not None else gather)
         return v, i.to(torch.int64)
 
 
@@ -438,16 +441,17 @@ class GDRRetriever:
         return self._live
 
     @torch.no_grad()
-    def search(self, q_reps, k, allowed=None):
+    def search(self, q_reps, k, allowed=None, gather=None):
         """The dense top-k of q_reps [B, d] over the LIVE documents (DenseModel.search with live_rows): a document withdrawn by
         remove_documents never comes back, one restored by update_documents does, ids are rows of doc_embed.  Returns (values,
         int64 ids); k <= the number of live documents.  allowed: an ops.QueryRows over doc_embed's rows — a filter per query, ANDed
         with live_rows (a removed document never returns, whatever the filter says); a query left with fewer than k documents ends
-        in -inf / -1.  Raises GdrError for a sharded retriever."""
+        in -inf / -1.  gather: as DenseModel.search's (None routes narrow filters to the gather mode).  Raises GdrError for a sharded retriever."""
         live = self.live_rows
         if getattr(self, "_search_ws", None) is None:
             self._search_ws = ops.Workspace(self.doc_embed.device)
-        v, i = ops.sim_topk(q_reps.contiguous(), self.doc_embed, k, workspace=self._search_ws, live=live, allowed=allowed)
+        v, i = ops.sim_topk(q_reps.contiguous(), self.doc_embed, k, workspace=self._search_ws, live=live, allowed=allowed,
+                            gather="auto" if gather is None and allowed is not None else gather)
         return v, i.to(torch.int64)
 
     @torch.no_grad()

@@ -346,7 +346,51 @@ def _sim_topk_raw(Q, D, k, idx_offset, workspace, flags, live=None, allowed=None
     return vals, idx, status
 
 
-def sim_topk(Q, D, k, idx_offset=0, workspace=None, return_status=False, exact_on_overflow=True, flags=0, live=None, allowed=None):
+GATHER_MAX_ROWS = 32768          # gather="auto": a query that allows at most this many rows goes to the gather mode (SIM_ROW_GATHER).  Measured
+                                 # (tools/bench_query_gather.py; N = 320 000, d = 768, k = 100): the largest count at which the
+                                 # gather call beats the dense masked call with its exhaustive re-run at 512 and 32 queries, fp32 and bf16
+                                 # (at 65 536 rows the 512-query calls lose)
+GATHER_CHUNK_ROWS = 4096         # GDR_SIM_GATHER_CHUNKS counts list capacity in chunks of this many rows
+GATHER_MAX_CHUNKS = 256
+GATHER_ONE_SORT_ROWS = 8192      # up to two chunks one LDS sort ranks the list (any k); longer lists take chunks + merge rounds, k <= 1024
+GATHER_CHUNKED_MAX_K = 1024
+
+
+def gather_chunks(rows):
+    """The chunk field for a per-query capacity of `rows` rows: ceil(rows / 4096), at least 1."""
+    return max(1, -(-int(rows) // GATHER_CHUNK_ROWS))
+
+
+def gather_route(counts, k, max_rows):
+    """Which queries of a filtered call go to the gather mode.  counts: how many rows each query's bitmap allows (host ints, after
+    the AND with live=).  Returns (narrow query indices, chunks): the queries with count <= max_rows, in order, and the chunk field
+    that holds the largest of their counts (0 when there is none).  A list of more than 8192 rows is ranked by chunks + merge
+    rounds, which stop at k = 1024: such a query stays on the dense route when k is larger.  Host only."""
+    counts = [int(c) for c in counts]
+    limit = min(int(max_rows), GATHER_CHUNK_ROWS * GATHER_MAX_CHUNKS)
+    if k > GATHER_CHUNKED_MAX_K:
+        limit = min(limit, GATHER_ONE_SORT_ROWS)
+    narrow = [q for q, c in enumerate(counts) if c <= limit]
+    return narrow, (gather_chunks(max(counts[q] for q in narrow)) if narrow else 0)
+
+
+def _sim_topk_exact(Q, D, k, idx_offset, status, vals, idx, flags, live, allowed):
+    """exact_on_overflow: reads the status back (one sync) and re-runs the flagged queries exhaustively, in place.  Returns the status."""
+    bad = torch.nonzero(status).flatten()
+    _ffi.check_device_fault("sim_topk")                              # nonzero() synchronised
+    if bad.numel():
+        for lo in range(0, bad.numel(), 64):                     # bounded workspace: 64 queries * N * 8 B
+            rows = bad[lo:lo + 64]
+            v2, i2, _ = _sim_topk_raw(Q[rows].contiguous(), D, k, idx_offset, None,
+                                      _ffi.SIM_EXHAUSTIVE | (flags & _ffi.SIM_NO_STREAM), live,   # the core the caller chose
+                                      allowed.rows(rows) if allowed is not None else None)
+            vals[rows], idx[rows] = v2, i2
+        status = torch.zeros_like(status)
+    return status
+
+
+def sim_topk(Q, D, k, idx_offset=0, workspace=None, return_status=False, exact_on_overflow=True, flags=0, live=None, allowed=None,
+             gather=None):
     """Fused Q·Dᵀ + per-row top-k — gdr_sim_topk.  Returns (values fp32[B,k], indices int32[B,k]), 1 <= k <= min(SIM_TOPK_MAX_K, N).
     D may be an fp32 or bf16 tensor, or a PrefilteredCorpus: the pre-filter serves k <= PREFILTER_MAX_K, a deeper list is the
     plain fp32 call over its rows (the same answer: both return the top-k of the fp32 scores for every input).
@@ -363,7 +407,18 @@ def sim_topk(Q, D, k, idx_offset=0, workspace=None, return_status=False, exact_o
     workspace, so a dead row never returns whatever the filter says.  How many rows a query allows is known on the device only,
     so nothing raises for a short one: a row with fewer than k allowed (and live) documents ends in -inf / -1.  A PrefilteredCorpus
     is searched on the plain fp32 path, as for live=.  A query whose filter keeps a small fraction of the rows overflows its
-    candidate list (include/gdr_hip.h, NARROW FILTERS) and is re-run exhaustively with its bitmap: exact, and slower."""
+    candidate list (include/gdr_hip.h, NARROW FILTERS) and is re-run exhaustively with its bitmap — unless the gather mode takes it:
+    gather (with allowed=; GDR_SIM_ROW_GATHER): how narrow filters are served.
+      None / False  the dense masked call and its exhaustive re-run, launch for launch what the call did before the mode existed.
+      an int rows   every query goes through the gather mode with a capacity of ceil(rows / 4096) chunks: only the rows a bitmap
+                    allows are scored.  No read-back, so it is usable with exact_on_overflow=False; status[q] = 1 where query q allows
+                    more rows than the capacity (exact_on_overflow=True re-runs those exhaustively, as any overflow).
+      "auto"        (needs exact_on_overflow=True, which synchronises anyway; otherwise it is False) reads back the per-query counts
+                    of the bitmaps as they will be used — after the AND with live= — one more sync, before the launches.  Queries
+                    that allow at most GATHER_MAX_ROWS rows (gather_route) go to ONE gather call sized for the largest of them, the
+                    rest to the dense masked call as before; an all-narrow batch launches no dense pass.
+    DenseModel.search and GDRRetriever.search pass "auto" by default; here the default is None, so that a direct caller's lists stay
+    bit for bit the dense call's (the gather pass sums a row in another order than the GEMM core)."""
     prefilter = isinstance(D, PrefilteredCorpus)
     if prefilter:
         P, D = D, D.D
@@ -388,21 +443,44 @@ def sim_topk(Q, D, k, idx_offset=0, workspace=None, return_status=False, exact_o
     if allowed is not None:
         if not isinstance(allowed, QueryRows) or allowed.B != Q.shape[0] or allowed.n != D.shape[0] or allowed.device != D.device:
             raise _ffi.GdrError(f"sim_topk: allowed must be an ops.QueryRows of {Q.shape[0]} queries over the {D.shape[0]} rows of D, on its device")
+    if gather is None or gather is False or (isinstance(gather, str) and gather == "auto" and (allowed is None or not exact_on_overflow)):
+        gather = None
+    elif allowed is None or (flags & _ffi.SIM_EXHAUSTIVE):
+        raise _ffi.GdrError("sim_topk: gather= ranks the rows a QueryRows allows: it needs allowed= and no SIM_EXHAUSTIVE flag")
+    elif gather is True or not (gather == "auto" or (isinstance(gather, int) and 1 <= gather <= GATHER_CHUNK_ROWS * GATHER_MAX_CHUNKS)):
+        raise _ffi.GdrError(f'sim_topk: gather must be None, False, "auto" or a row capacity in [1, {GATHER_CHUNK_ROWS * GATHER_MAX_CHUNKS}], not {gather!r}')
+    if gather is not None:
+        gflags = (flags & _ffi.SIM_NO_STREAM) | _ffi.SIM_ROW_GATHER
+        if gather != "auto":                                         # every query through the gather mode, no read-back
+            vals, idx, status = _sim_topk_raw(Q, D, k, idx_offset, workspace, gflags | _ffi.sim_gather_chunks(gather_chunks(gather)), live, allowed)
+            if exact_on_overflow:
+                status = _sim_topk_exact(Q, D, k, idx_offset, status, vals, idx, flags, live, allowed)
+            return (vals, idx, status) if return_status else (vals, idx)
+        eff = allowed if live is None else allowed.rows(torch.arange(allowed.B, device=allowed.device)).and_(live)   # a copy: the caller's stays
+        narrow, chunks = gather_route(eff.counts().tolist(), k, GATHER_MAX_ROWS)     # the one extra sync
+        if narrow:
+            B = Q.shape[0]
+            if len(narrow) == B:
+                vals, idx, status = _sim_topk_raw(Q, D, k, idx_offset, workspace, gflags | _ffi.sim_gather_chunks(chunks), None, eff)
+                return (vals, idx, status) if return_status else (vals, idx)     # the capacity holds every count: status is 0
+            wide = sorted(set(range(B)) - set(narrow))
+            nt, wt = (torch.tensor(x, dtype=torch.int64, device=Q.device) for x in (narrow, wide))
+            vals = torch.empty((B, k), dtype=torch.float32, device=Q.device)
+            idx = torch.empty((B, k), dtype=torch.int32, device=Q.device)
+            status = torch.zeros((B,), dtype=torch.int32, device=Q.device)
+            vals[nt], idx[nt], _ = _sim_topk_raw(Q[nt].contiguous(), D, k, idx_offset, workspace, gflags | _ffi.sim_gather_chunks(chunks),
+                                                 None, eff.rows(nt))
+            Qw, aw = Q[wt].contiguous(), eff.rows(wt)
+            v2, i2, s2 = _sim_topk_raw(Qw, D, k, idx_offset, workspace, flags, None, aw)
+            _sim_topk_exact(Qw, D, k, idx_offset, s2, v2, i2, flags, None, aw)
+            vals[wt], idx[wt] = v2, i2
+            return (vals, idx, status) if return_status else (vals, idx)
     if prefilter:
         vals, idx, status = _sim_topk_prefilter_raw(Q, P, k, idx_offset, workspace)
     else:
         vals, idx, status = _sim_topk_raw(Q, D, k, idx_offset, workspace, flags, live, allowed)
     if exact_on_overflow:
-        bad = torch.nonzero(status).flatten()
-        _ffi.check_device_fault("sim_topk")                              # nonzero() synchronised
-        if bad.numel():
-            for lo in range(0, bad.numel(), 64):                     # bounded workspace: 64 queries * N * 8 B
-                rows = bad[lo:lo + 64]
-                v2, i2, _ = _sim_topk_raw(Q[rows].contiguous(), D, k, idx_offset, None,
-                                          _ffi.SIM_EXHAUSTIVE | (flags & _ffi.SIM_NO_STREAM), live,   # the core the caller chose
-                                          allowed.rows(rows) if allowed is not None else None)
-                vals[rows], idx[rows] = v2, i2
-            status = torch.zeros_like(status)
+        status = _sim_topk_exact(Q, D, k, idx_offset, status, vals, idx, flags, live, allowed)
     return (vals, idx, status) if return_status else (vals, idx)
 
 

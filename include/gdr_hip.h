@@ -300,16 +300,40 @@ int gdr_t5_encoder_forward_bf16(const GdrT5EncoderWeights* w, const int64_t* ids
  *   rows into the per-query bitmaps and pass this flag alone.  GDR_SIM_EXHAUSTIVE and GDR_SIM_NO_STREAM combine with it as with the live mask.
  *   NARROW FILTERS: a disallowed row that reaches the threshold still takes a slot of the candidate list until the second mask pass
  *   drops it, and the list holds 4 x the survivors expected of an unfiltered query.  A query whose filter keeps a small fraction of
- *   the rows therefore overflows: status[q] = 1, and the re-run with GDR_SIM_EXHAUSTIVE | GDR_SIM_QUERY_MASK is exact and slower.
+ *   the rows therefore overflows: status[q] = 1.  Such a query is served by GDR_SIM_ROW_GATHER below, which scores its allowed rows
+ *   only; the re-run with GDR_SIM_EXHAUSTIVE | GDR_SIM_QUERY_MASK stays exact for every filter and is a second pass over the corpus.
  *   Measured at N = 320 000, d = 768, k = 100 with independent random filters (tools/bench_query_mask.py,
  *   profiles/r22_query_mask_bench.jsonl): no query of 512 overflows with 50 % of the rows kept, 1 with 30 %, 33 with 25 %, 313 with
  *   20 %, 509 with 15 %, all with 10 % — overflow begins where a filter keeps less than about 30 % of the rows and is the rule below
  *   20 %.  The fraction moves with the plan (k, N): it is where k N / (f n_sample) passes the list's 4 k N / n_sample + 4096 slots.
+ * GDR_SIM_ROW_GATHER (with GDR_SIM_QUERY_MASK; gdr_sim_topk, gdr_sim_topk_bf16): the mode for NARROW filters.  Input: GDR_SIM_QUERY_MASK's
+ *   B bitmaps at the head of `workspace` (bitmap q at byte q * M, bits past N and the padding ignored, only read).  Bitmap q is
+ *   compacted into its allowed row ids in ascending order (popcounts, a scan, ordered placement: no atomics), only those rows are
+ *   read and scored (a wave per 4 rows, 16 bytes per lane, fp32 fmaf chain in ascending column order; a bf16 corpus is widened
+ *   exactly), and keys (score, row) are sorted: row q of the result is the top-k over the rows bitmap q allows, higher score first in
+ *   the total order of the fp32 bits, then the lower id; ids = row + idx_offset; a -inf / -1 tail where fewer than k rows are allowed,
+ *   the empty bitmap included.  The score of (query, row) depends on the two vectors and d alone.
+ *   Capacity: GDR_SIM_GATHER_CHUNKS(c) in bits 8..16 of flags sets cap = 4096 c rows per query, c in 1 .. 256, 0 reads as 2.  A query
+ *   that allows more than cap rows gets status[q] = 1 and the top-k of its FIRST cap allowed rows in ascending row order (deterministic;
+ *   the top-k of a subset, as every status 1): re-run it with a larger c or with GDR_SIM_EXHAUSTIVE | GDR_SIM_QUERY_MASK.  No other
+ *   query is affected.  c <= 2: one LDS sort per query, any k <= min(N, 8192).  c > 2: chunks of 4096 list positions keep their first k
+ *   and merge rounds join them (k <= 1024, as the long rerank) — the same list bit for bit.
+ *   gdr_sim_topk_workspace_bytes(.., flags) = B * M + the gather layout for (B, cap, k): row ids and scores [B][cap], counts, the scan
+ *   scratch and, for c > 2, two partial-list buffers; it does not depend on N or d and never shrinks when c or k grows.  A smaller
+ *   workspace is GDR_ENOSPC.  GDR_EINVAL before any launch: the flag without GDR_SIM_QUERY_MASK, with GDR_SIM_LIVE_MASK or with
+ *   GDR_SIM_EXHAUSTIVE, a chunk field above 256 or without the flag, k > 1024 with c > 2 (the size asked for any of them is 0).
+ *   GDR_SIM_NO_STREAM is accepted and means nothing: no GEMM core runs.  Stream-ordered and capturable, no host synchronisation.
+ *   Measured at N = 320 000, d = 768, k = 100 (tools/bench_query_gather.py, profiles/r23_query_gather_bench.jsonl): 512 fp32 queries that
+ *   keep 3 200 rows each take 0.87 ms here against 15.4 ms for the dense masked call with its exhaustive re-run; the mode wins at 512 and
+ *   32 queries, fp32 and bf16, up to 32 768 rows per query and loses at 65 536 (gdr_amd.ops.GATHER_MAX_ROWS = 32768 routes by that).
+ *   With bit 16 and bits 8..16 of flags clear, every layout, launch and result is what it was.
  * ---------------------------------------------------------------------------------------------- */
 #define GDR_SIM_EXHAUSTIVE 1
 #define GDR_SIM_NO_STREAM 2   /* force the tiled GEMM core even at B <= 32 (A/B testing of the latency-mode kernel) */
 #define GDR_SIM_LIVE_MASK 4   /* workspace starts with a live-row bitmap; rank the live rows only */
 #define GDR_SIM_QUERY_MASK 8  /* workspace starts with one row bitmap per query; rank query q's allowed rows only */
+#define GDR_SIM_ROW_GATHER 16                 /* with GDR_SIM_QUERY_MASK: score only the rows bitmap q allows */
+#define GDR_SIM_GATHER_CHUNKS(c) ((c) << 8)   /* bits 8..16 of flags: per-query list capacity in chunks of 4096 rows, 1..256; 0 = 2 */
 size_t gdr_sim_topk_workspace_bytes(int B, int64_t N, int d, int k, int flags);
 int gdr_sim_topk(const float* Q, int B, const float* D, int64_t N, int d, int k, int32_t idx_offset,
                  float* out_val, int32_t* out_idx, int32_t* status, int flags, void* workspace,
