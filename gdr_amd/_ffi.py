@@ -183,6 +183,14 @@ SIGNATURES = {
     "gdr_beam_search_table": (_i, [_vp, _i, _i, _i, _i, C.c_double, _i, C.POINTER(GdrTrie), _vp, _vp, _vp, _vp, _sz,
                                    _vp]),
 }
+# name -> (restype, argtypes); every symbol declared in include/gdr_hip_prefilter_mask.h (which gdr_hip.h includes): the masked
+# pre-filter and the row-wise upkeep of the bf16 image.  A table of its own, as the header is a file of its own: SIGNATURES is the
+# main header's, entry for entry.
+PREFILTER_MASK_SIGNATURES = {
+    "gdr_sim_topk_prefilter_masked_workspace_bytes": (_sz, [_i, _i64, _i, _i, _i]),
+    "gdr_sim_topk_prefilter_masked": (_i, [_vp, _i, _vp, _vp, C.c_float, _i64, _i, _i, C.c_int32, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
+    "gdr_prefilter_update_rows": (_i, [_vp, _vp, _i, _vp, _i64, _vp, _vp]),
+}
 
 _lib = None
 
@@ -203,7 +211,7 @@ def lib():
             # GDR_FFI_NO_TORCH: it never touches a GPU.)
             import torch  # noqa: F401
         l = C.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in list(SIGNATURES.items()) + list(PREFILTER_MASK_SIGNATURES.items()):
             fn = getattr(l, name)            # AttributeError if the .so lacks a declared symbol
             fn.restype, fn.argtypes = res, args
         got = l.gdr_abi_version()

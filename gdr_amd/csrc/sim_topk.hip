@@ -19,6 +19,10 @@
 // n_sample ≈ sqrt(k·N) balances list length against survivors.  Small corpora take steps 1, 2, 4 only.
 #include <stdlib.h>
 
+#include <map>
+#include <mutex>
+#include <tuple>
+
 #include "select.h"
 
 namespace gdr {
@@ -964,6 +968,14 @@ namespace gdr {
 //   * the sample threshold L (k-th largest s~ over the sample) is <= t~_k, so the filter pass keeps s~ >= L - 2 eps_q, a superset.
 // Lists that overflow (the candidate list of the bf16 pass, or more than cap2 docs inside the 2-eps band) are flagged in status[q] like
 // gdr_sim_topk's; ops.sim_topk recomputes such a query on the fp32 path.
+// MASKED (gdr_sim_topk_prefilter_masked: a live-row bitmap, or one bitmap per query): the argument holds verbatim with "docs" read as
+// "allowed docs" — t~_k and T_k are then the k-th largest s~ / s over the rows query q's bitmap allows, eps_q needs max ||d|| over
+// those rows only (any upper bound widens the band, never breaks it), and the sample threshold L is the k-th largest ALLOWED sample
+// score, which is <= the k-th largest allowed s~.  L taken over all sample rows would not do: with a query's best rows disallowed it
+// lies above t~_k - 2 eps_q of the allowed rows, and the filter pass would drop docs of the answer.  So the bitmap is applied where
+// gdr_sim_topk's GDR_SIM_LIVE_MASK applies it — sim_live_mask_kernel over the sample block before the threshold, over the survivors
+// behind the filter pass, sim_live_thr_fixup_kernel where fewer than k allowed sample rows leave no threshold — and the tail below
+// runs unchanged: radix_kth_key ignores -inf scores, the band gather skips id < 0, so a masked entry is padding to it.
 __global__ __launch_bounds__(256) void sim_qprep_kernel(const float* __restrict__ Q, int d, float dnorm_max, __bf16* __restrict__ Q16,
                                                         float* __restrict__ eps2) {
   __shared__ float red[4];
@@ -1167,9 +1179,10 @@ static double prefilter_survivor_factor(int64_t N, int d, int k) {
   const double f = 0.5 * Qf(zl - dz) / tail;
   return f > 1.0 ? f : 1.0;
 }
-static PrefilterPlan make_prefilter_plan(int B, int64_t N, int d, int k) {
+// base: bytes in front of the plan (the caller's bitmaps of gdr_sim_topk_prefilter_masked), as make_plan's
+static PrefilterPlan make_prefilter_plan(int B, int64_t N, int d, int k, size_t base = 0) {
   PrefilterPlan pp{};
-  pp.p = make_plan(B, N, k, false, prefilter_survivor_factor(N, d, k));
+  pp.p = make_plan(B, N, k, false, prefilter_survivor_factor(N, d, k), base);
   pp.cap2 = prefilter_cap2(k);
   size_t o = pp.p.total;
   pp.off_q16 = o, o += align_up((size_t)B * d * 2, 256);
@@ -1183,9 +1196,39 @@ extern "C" size_t gdr_sim_topk_prefilter_workspace_bytes(int B, int64_t N, int d
   if (B <= 0 || N <= 0 || k <= 0 || d <= 0) return 0;
   // never below what gdr_sim_topk is told for the same call (its answer is the largest plan up to k, see there) plus the bf16 queries
   // and the bands this entry point keeps beside the list
-  const size_t own = gdr::make_prefilter_plan(B, N, d, k).total;
+  // Nor below its own answer for any k' <= k: like make_plan, make_prefilter_plan dips (up to 2.8 % at N = 320 000, d = 768) each time a
+  // larger k lowers the sample stride by one.  With the sample tile count ts fixed the list only grows with k — the survivor term is
+  // max(4 k N / n_sample, 2 N Q(z_L - dz)) with z_L falling as k grows — so the maximum sits at the last k of a ts value, found as in
+  // gdr_sim_topk_workspace_bytes.  Every candidate costs a bisection of erfc, several hundred of them a millisecond, and ops.sim_topk
+  // asks on every call: the answers are kept (a few shapes per process).
+  static std::mutex mu;
+  static std::map<std::tuple<int, int64_t, int, int>, size_t> memo;
+  const auto key = std::make_tuple(B, N, d, k);
+  {
+    std::lock_guard<std::mutex> lock(mu);
+    const auto it = memo.find(key);
+    if (it != memo.end()) return it->second;
+  }
+  size_t own = gdr::make_prefilter_plan(B, N, d, k).total;
+  double target = sqrt((double)k * (double)N);
+  if (target < k) target = k;
+  const int64_t ts_k = (int64_t)((target + gdr::TILE - 1) / gdr::TILE);
+  for (int64_t ts = 1; ts <= ts_k; ++ts) {
+    const double edge = (double)(ts * gdr::TILE);
+    const int64_t ends[2] = {(int64_t)(edge * edge / (double)N), ts * gdr::TILE};
+    for (const int64_t e : ends)
+      for (int64_t kk = e - 1; kk <= e + 1; ++kk)
+        if (kk >= 1 && kk < k) {
+          const size_t t = gdr::make_prefilter_plan(B, N, d, (int)kk).total;
+          if (t > own) own = t;
+        }
+  }
   const size_t plain = gdr_sim_topk_workspace_bytes(B, N, d, k, 0) + gdr::align_up((size_t)B * d * 2, 256) + gdr::align_up((size_t)B * 4, 256);
-  return own > plain ? own : plain;
+  const size_t best = own > plain ? own : plain;
+  std::lock_guard<std::mutex> lock(mu);
+  if (memo.size() >= 4096) memo.clear();
+  memo[key] = best;
+  return best;
 }
 
 extern "C" int gdr_row_norm2_max(const float* D, int64_t N, int d, float* out_dev, void* stream_) {
@@ -1203,11 +1246,12 @@ extern "C" int gdr_row_norm2_max(const float* D, int64_t N, int d, float* out_de
   return GDR_OK;
 }
 
-extern "C" int gdr_sim_topk_prefilter(const float* Q, int B, const float* D, const void* D_bf16, float dnorm_max, int64_t N, int d, int k,
-                                      int32_t idx_offset, float* out_val, int32_t* out_idx, int32_t* status, void* workspace,
-                                      size_t workspace_bytes, void* stream_) {
-  using namespace gdr;
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
+namespace gdr {
+// gdr_sim_topk_prefilter (flags = 0) and gdr_sim_topk_prefilter_masked (flags = GDR_SIM_LIVE_MASK or GDR_SIM_QUERY_MASK: the bitmap(s) at
+// the head of the workspace, the plan behind them).  With flags = 0 the launches are what they were before the masked form existed.
+static int prefilter_impl(const float* Q, int B, const float* D, const void* D_bf16, float dnorm_max, int64_t N, int d, int k,
+                          int32_t idx_offset, float* out_val, int32_t* out_idx, int32_t* status, int flags, void* workspace,
+                          size_t workspace_bytes, hipStream_t stream) {
   if (B == 0) return GDR_OK;
   GDR_CHECK_ARG(Q && D && D_bf16 && out_val && out_idx && workspace, "sim_topk_prefilter: null pointer");
   GDR_CHECK_ARG(B > 0 && N > 0 && d > 0 && d % 8 == 0 && d <= 1024, "sim_topk_prefilter: bad shape B=%d N=%lld d=%d (d %% 8 == 0, d <= 1024)", B,
@@ -1220,13 +1264,19 @@ extern "C" int gdr_sim_topk_prefilter(const float* Q, int B, const float* D, con
   GDR_CHECK_ARG(dnorm_max > 0.f && dnorm_max < INFINITY, "sim_topk_prefilter: dnorm_max must be the largest row norm of D (> 0, finite)");
   GDR_CHECK_ARG(((uintptr_t)Q & 15) == 0 && ((uintptr_t)D & 15) == 0 && ((uintptr_t)D_bf16 & 15) == 0 && ((uintptr_t)workspace & 255) == 0,
                 "sim_topk_prefilter: Q, D, D_bf16 must be 16-byte and workspace 256-byte aligned");
-  const PrefilterPlan pp = make_prefilter_plan(B, N, d, k);
+  const bool per_query = flags == GDR_SIM_QUERY_MASK, masked = flags != 0;
+  const size_t head = masked ? (per_query ? (size_t)B : 1) * live_mask_bytes(N) : 0;
+  const int64_t qstride = per_query ? (int64_t)(live_mask_bytes(N) / sizeof(uint32_t)) : 0;  // words between two queries' bitmaps
+  const PrefilterPlan pp = make_prefilter_plan(B, N, d, k, head);
   const SimPlan& p = pp.p;
-  if (workspace_bytes < pp.total) {
-    set_error("sim_topk_prefilter: workspace %zu < required %zu", workspace_bytes, pp.total);
+  // a masked call is held to the size its caller was told (the bitmaps + the unmasked answer, never below this k's own layout)
+  const size_t required = masked ? gdr_sim_topk_prefilter_masked_workspace_bytes(B, N, d, k, flags) : pp.total;
+  if (workspace_bytes < required) {
+    set_error("sim_topk_prefilter: workspace %zu < required %zu", workspace_bytes, required);
     return GDR_ENOSPC;
   }
   char* ws = static_cast<char*>(workspace);
+  const uint32_t* live = masked ? reinterpret_cast<const uint32_t*>(ws) : nullptr;
   SimEpilogue ep{};
   ep.cand_val = reinterpret_cast<float*>(ws + p.off_val);
   ep.cand_idx = reinterpret_cast<int32_t*>(ws + p.off_idx);
@@ -1240,14 +1290,21 @@ extern "C" int gdr_sim_topk_prefilter(const float* Q, int B, const float* D, con
   const bool stream_mode = sim_stream_supported(B, d, true);  // B <= 32: the HBM-bound stream over the bf16 image
   int rc = stream_mode ? launch_sim_stream(D_bf16, N, Q16, B, d, ep, true, stream) : launch_sim_gemm(D_bf16, N, Q16, B, d, ep, true, stream);
   if (rc) return rc;
+  if (masked) GDR_TRY(launch_live_mask(ep, p, B, 0, p.n_slots, live, qstride, N, stream));  // the threshold sees allowed sample scores only
   // L - 2 eps: the filter pass keeps a superset of the band around the (yet unknown) k-th largest bf16 score
   hipLaunchKernelGGL(sim_threshold_kernel, dim3(B), dim3(1024), 0, stream, ep.cand_val, p.cap, (int)p.n_slots, k, thr, ep.cand_cnt,
                      (const float*)eps2);
   GDR_CHECK_LAUNCH("sim_threshold_kernel");
   if (p.stride > 1) {
+    if (masked) {  // fewer than k allowed sample rows (per query: of query q's bitmap): thr[q] = -inf (sim_live_thr_fixup_kernel)
+      hipLaunchKernelGGL(sim_live_thr_fixup_kernel, dim3(per_query ? B : 1), dim3(256), 0, stream, live, qstride, N, p.n_sample_tiles,
+                         p.stride, k, thr, B);
+      GDR_CHECK_LAUNCH("sim_live_thr_fixup_kernel");
+    }
     ep.mode = 2;
     rc = stream_mode ? launch_sim_stream(D_bf16, N, Q16, B, d, ep, true, stream) : launch_sim_gemm(D_bf16, N, Q16, B, d, ep, true, stream);
     if (rc) return rc;
+    if (masked) GDR_TRY(launch_live_mask(ep, p, B, p.n_slots, -1, live, qstride, N, stream));  // the survivors, disallowed rows among them
   }
   // the tail in one launch: k-th largest bf16-operand score, the band around it, fp32 scores of the band, exact select
   const int cap2p = sel_pow2(pp.cap2, 1024);
@@ -1256,6 +1313,79 @@ extern "C" int gdr_sim_topk_prefilter(const float* Q, int B, const float* D, con
                      (const int32_t*)ep.cand_idx, (const int32_t*)ep.cand_cnt, p.cap, k, pp.cap2, cap2p, (const float*)eps2, Q, D, d,
                      idx_offset, out_val, out_idx, status);
   GDR_CHECK_LAUNCH("prefilter_tail_kernel");
+  return GDR_OK;
+}
+
+// One wave per listed row: the row's bf16 image (the bits cast_f32_bf16_kernel gives) and its squared norm in row_norm2_max_kernel's
+// order (the same fmaf chain per lane, the same shuffle tree), joined by atomicMax on the bits.  A row listed twice is written twice
+// with the same bits.  Plain vector stores only.
+__global__ __launch_bounds__(256) void prefilter_update_rows_kernel(const float* __restrict__ D, __bf16* __restrict__ D16, int d,
+                                                                    const int32_t* __restrict__ rows, int64_t n_rows,
+                                                                    unsigned* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  float best = 0.f;
+  for (int64_t j = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); j < n_rows; j += (int64_t)gridDim.x * 4) {
+    const int64_t r = rows[j];
+    if (r < 0) continue;  // no row: the upper end is the caller's to keep (the call is not told N)
+    const float* row = D + r * d;
+    float ss = 0.f;
+    for (int c = lane * 4; c < d; c += 256) {
+      const float4 v = *reinterpret_cast<const float4*>(row + c);
+      ss = fmaf(v.x, v.x, fmaf(v.y, v.y, fmaf(v.z, v.z, fmaf(v.w, v.w, ss))));
+      union {
+        __bf16 h[4];
+        uint2 u;
+      } o;
+      o.h[0] = (__bf16)v.x, o.h[1] = (__bf16)v.y, o.h[2] = (__bf16)v.z, o.h[3] = (__bf16)v.w;
+      *reinterpret_cast<uint2*>(D16 + r * d + c) = o.u;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) ss += __shfl_xor(ss, off);
+    best = fmaxf(best, ss);
+  }
+  if (lane == 0) atomicMax(out, __float_as_uint(best));
+}
+}  // namespace gdr
+
+extern "C" int gdr_sim_topk_prefilter(const float* Q, int B, const float* D, const void* D_bf16, float dnorm_max, int64_t N, int d, int k,
+                                      int32_t idx_offset, float* out_val, int32_t* out_idx, int32_t* status, void* workspace,
+                                      size_t workspace_bytes, void* stream_) {
+  return gdr::prefilter_impl(Q, B, D, D_bf16, dnorm_max, N, d, k, idx_offset, out_val, out_idx, status, 0, workspace, workspace_bytes,
+                             static_cast<hipStream_t>(stream_));
+}
+
+extern "C" size_t gdr_sim_topk_prefilter_masked_workspace_bytes(int B, int64_t N, int d, int k, int flags) {
+  if (flags != GDR_SIM_LIVE_MASK && flags != GDR_SIM_QUERY_MASK) return 0;  // no such call: gdr_sim_topk_prefilter_masked refuses it
+  const size_t own = gdr_sim_topk_prefilter_workspace_bytes(B, N, d, k);
+  if (own == 0) return 0;
+  return (flags == GDR_SIM_QUERY_MASK ? (size_t)B : 1) * gdr::live_mask_bytes(N) + own;
+}
+
+extern "C" int gdr_sim_topk_prefilter_masked(const float* Q, int B, const float* D, const void* D_bf16, float dnorm_max, int64_t N, int d,
+                                             int k, int32_t idx_offset, float* out_val, int32_t* out_idx, int32_t* status, int flags,
+                                             void* workspace, size_t workspace_bytes, void* stream_) {
+  using namespace gdr;
+  GDR_CHECK_ARG(flags == GDR_SIM_LIVE_MASK || flags == GDR_SIM_QUERY_MASK,
+                "sim_topk_prefilter_masked: flags=%d must be exactly GDR_SIM_LIVE_MASK (one row bitmap at the head of the workspace) or "
+                "GDR_SIM_QUERY_MASK (one per query): AND the live rows into the per-query bitmaps for both; the exhaustive re-run and the "
+                "gather mode are gdr_sim_topk's", flags);
+  return prefilter_impl(Q, B, D, D_bf16, dnorm_max, N, d, k, idx_offset, out_val, out_idx, status, flags, workspace, workspace_bytes,
+                        static_cast<hipStream_t>(stream_));
+}
+
+extern "C" int gdr_prefilter_update_rows(const float* D, void* D_bf16, int d, const int32_t* rows, int64_t n_rows, float* norm2_max_inout,
+                                         void* stream_) {
+  using namespace gdr;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  GDR_CHECK_ARG(d > 0 && d % 8 == 0 && n_rows >= 0, "prefilter_update_rows: bad shape d=%d (d %% 8 == 0) n_rows=%lld", d, (long long)n_rows);
+  if (n_rows == 0) return GDR_OK;
+  GDR_CHECK_ARG(D && D_bf16 && rows && norm2_max_inout, "prefilter_update_rows: null pointer");
+  GDR_CHECK_ARG(((uintptr_t)D & 15) == 0 && ((uintptr_t)D_bf16 & 15) == 0 && ((uintptr_t)rows & 3) == 0 && ((uintptr_t)norm2_max_inout & 3) == 0,
+                "prefilter_update_rows: D, D_bf16 must be 16-byte aligned");
+  const int64_t blocks = (n_rows + 3) / 4;
+  hipLaunchKernelGGL(prefilter_update_rows_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, stream, D,
+                     static_cast<__bf16*>(D_bf16), d, rows, n_rows, reinterpret_cast<unsigned*>(norm2_max_inout));
+  GDR_CHECK_LAUNCH("prefilter_update_rows_kernel");
   return GDR_OK;
 }
 

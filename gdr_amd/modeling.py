@@ -397,7 +397,7 @@ class GDRRetriever:
                                 "which returns no scores for validation_step_i to unpack (main_models.py:1400)")
 
     def __init__(self, model: GDRModel, doc_embed, cluster_index: codec.ClusterIndex, args, doc_tower=None,
-                 doc_tokens=None, device_candidates=True, sharded=None):
+                 doc_tokens=None, device_candidates=True, sharded=None, search_prefilter=False):
         """doc_embed: fp32 (or, in the C5 precision mode, bf16) [N, d] resident on the GPU (the reference's `self.doc_embed`).
         doc_tower + doc_tokens=(input_ids int64[N,Lp], attention_mask) enable the stage-2 re-encode path of
         main_models.py:1445-1455 (`epoch > train_encoder_epoch`): candidate docs are embedded on the fly by the
@@ -408,7 +408,11 @@ class GDRRetriever:
         per-GPU launch is: Data_process/NQ_dataset/bert/bert_NQ.sh:5-12), and stage 2 is `sharded.rerank_own` — one
         all-gather of the queries + candidate blocks, per-shard scoring, one all-to-all, merge: the lists are bit-identical
         to the unsharded rerank.  Every rank must call validation_step_i the same number of times with the same batch size
-        (the collectives are fixed-size); `cluster_index` is the index of the WHOLE corpus on every rank."""
+        (the collectives are fixed-size); `cluster_index` is the index of the WHOLE corpus on every rank.
+        search_prefilter: True = search() goes through the bf16 pre-filter over the live rows (ops.PrefilteredCorpus(doc_embed,
+        masks=True), built on the first search: +50 % of doc_embed's memory; the same documents, values the same dot products in
+        another summation order) and add_documents / update_documents keep the image current.  Needs the fp32 doc_embed of an
+        unsharded retriever (GdrError otherwise).  The default leaves search() what it was."""
         self._need_beams(args)
         # the stage-2 query vector: the encoder CLS row, or per hypothesis the decoder's EOS state / masked mean
         self.query_form, why = stage2_query_form(args, sharded=sharded is not None)
@@ -424,6 +428,12 @@ class GDRRetriever:
         # device_candidates: decoded rows -> clusters -> candidate CSR on the GPU (gdr_cluster_candidates); False keeps the
         # host form (decode_token strings + ClusterIndex.candidates) — same lists, one D2H / H2D round trip more per step
         self.device_candidates = bool(device_candidates)
+        self.search_prefilter = bool(search_prefilter)
+        if self.search_prefilter:
+            if sharded is not None:
+                raise _ffi.GdrError("GDRRetriever(search_prefilter=True): a sharded retriever has no dense search() to pre-filter")
+            if self.doc_embed is None or self.doc_embed.dtype != torch.float32:
+                raise _ffi.GdrError("GDRRetriever(search_prefilter=True) needs the fp32 doc_embed (a bf16 corpus is its own image)")
 
     @property
     def live_rows(self):
@@ -450,7 +460,12 @@ class GDRRetriever:
         live = self.live_rows
         if getattr(self, "_search_ws", None) is None:
             self._search_ws = ops.Workspace(self.doc_embed.device)
-        v, i = ops.sim_topk(q_reps.contiguous(), self.doc_embed, k, workspace=self._search_ws, live=live, allowed=allowed,
+        corpus = self.doc_embed
+        if self.search_prefilter:                                    # the image is made here, once, and kept current from then on
+            if getattr(self, "_prefiltered", None) is None:
+                self._prefiltered = ops.PrefilteredCorpus(self.doc_embed, masks=True)
+            corpus = self._prefiltered
+        v, i = ops.sim_topk(q_reps.contiguous(), corpus, k, workspace=self._search_ws, live=live, allowed=allowed,
                             gather="auto" if gather is None and allowed is not None else gather)
         return v, i.to(torch.int64)
 
@@ -505,6 +520,8 @@ class GDRRetriever:
         self.index = self.index.with_csr(csr[:C_ + 1], csr[C_ + 1:])
         if getattr(self, "_live", None) is not None:
             self._live.grow(N + n).set(ids)
+        if getattr(self, "_prefiltered", None) is not None:
+            self._prefiltered.rebind(self.doc_embed)                 # the new rows' image; the old rows keep theirs
         return np.arange(N, N + n, dtype=np.int64), fc.cmap[tgt.long()].cpu().numpy()
 
     def _document_rows(self, what, embeds, tokens):
@@ -633,6 +650,8 @@ class GDRRetriever:
         self._edit_csr(ids32, insert=ids32, targets=tgt)
         if getattr(self, "_live", None) is not None:
             self._live.set(rows)
+        if getattr(self, "_prefiltered", None) is not None:
+            self._prefiltered.update_rows(rows)                      # (remove_documents needs nothing: a withdrawn row is masked)
         out = np.empty(ids.size, np.int32)
         out[order] = fc.cmap[tgt.long()].cpu().numpy()
         return out

@@ -401,12 +401,14 @@ def sim_topk(Q, D, k, idx_offset=0, workspace=None, return_status=False, exact_o
     and the device status tensor (1 = that row is the top-k of a subset) is theirs to act on.  flags: _ffi.SIM_* bits.
     live: a LiveRows over the N rows of D — the top-k over its live rows only (GDR_SIM_LIVE_MASK; k <= live.count): the list the
     call would return for the matrix of the live rows, with their ids in D.  A PrefilteredCorpus is then searched on the plain fp32
-    path (the pre-filter has no mask; the same answer), and the overflow re-run carries the mask.
+    path — unless it was built with masks=True: then the masked pre-filter serves the call (gdr_sim_topk_prefilter_masked; the same
+    answer, see PrefilteredCorpus) —, and the overflow re-run carries the mask.
     allowed: a QueryRows (allowed.B == B, allowed.n == N, on D's device) — row q is the top-k over the rows query q's own bitmap
     allows (GDR_SIM_QUERY_MASK): a filter per query in ONE call.  With live= as well the two are ANDed on their way into the
     workspace, so a dead row never returns whatever the filter says.  How many rows a query allows is known on the device only,
     so nothing raises for a short one: a row with fewer than k allowed (and live) documents ends in -inf / -1.  A PrefilteredCorpus
-    is searched on the plain fp32 path, as for live=.  A query whose filter keeps a small fraction of the rows overflows its
+    is searched on the plain fp32 path, as for live= (masks=True: the masked pre-filter, which with gather="auto" takes the wide
+    remainder of the batch only).  A query whose filter keeps a small fraction of the rows overflows its
     candidate list (include/gdr_hip.h, NARROW FILTERS) and is re-run exhaustively with its bitmap — unless the gather mode takes it:
     gather (with allowed=; GDR_SIM_ROW_GATHER): how narrow filters are served.
       None / False  the dense masked call and its exhaustive re-run, launch for launch what the call did before the mode existed.
@@ -422,9 +424,7 @@ def sim_topk(Q, D, k, idx_offset=0, workspace=None, return_status=False, exact_o
     prefilter = isinstance(D, PrefilteredCorpus)
     if prefilter:
         P, D = D, D.D
-        if (live is not None or allowed is not None or Q.shape[0] < PREFILTER_MIN_BATCH or D.shape[1] % 8 or D.shape[1] > 1024 or (flags & _ffi.SIM_EXHAUSTIVE) or k > PREFILTER_MAX_K
-                or not P.dnorm_max > 0.0):                               # an all-zero corpus has no band: the fp32 path serves it
-            prefilter = False
+        prefilter = prefilter_route(Q.shape[0], D.shape[1], k, flags, P.dnorm_max, live is not None or allowed is not None, P.masks)
     _need_cuda(Q, D)
     if D.dtype == torch.bfloat16:                                    # bf16 corpus: queries are cast on the device
         Q = (Q if Q.dtype == torch.bfloat16 else to_bf16(Q)).contiguous()
@@ -471,12 +471,15 @@ def sim_topk(Q, D, k, idx_offset=0, workspace=None, return_status=False, exact_o
             vals[nt], idx[nt], _ = _sim_topk_raw(Q[nt].contiguous(), D, k, idx_offset, workspace, gflags | _ffi.sim_gather_chunks(chunks),
                                                  None, eff.rows(nt))
             Qw, aw = Q[wt].contiguous(), eff.rows(wt)
-            v2, i2, s2 = _sim_topk_raw(Qw, D, k, idx_offset, workspace, flags, None, aw)
+            if prefilter:                                            # PrefilteredCorpus(masks=True): the wide remainder through the bf16 pre-filter
+                v2, i2, s2 = _sim_topk_prefilter_raw(Qw, P, k, idx_offset, workspace, None, aw)
+            else:
+                v2, i2, s2 = _sim_topk_raw(Qw, D, k, idx_offset, workspace, flags, None, aw)
             _sim_topk_exact(Qw, D, k, idx_offset, s2, v2, i2, flags, None, aw)
             vals[wt], idx[wt] = v2, i2
             return (vals, idx, status) if return_status else (vals, idx)
     if prefilter:
-        vals, idx, status = _sim_topk_prefilter_raw(Q, P, k, idx_offset, workspace)
+        vals, idx, status = _sim_topk_prefilter_raw(Q, P, k, idx_offset, workspace, live, allowed)
     else:
         vals, idx, status = _sim_topk_raw(Q, D, k, idx_offset, workspace, flags, live, allowed)
     if exact_on_overflow:
@@ -489,23 +492,81 @@ class PrefilteredCorpus:
     row norm, both made once on the device.  ops.sim_topk(Q, PrefilteredCorpus(D), k) returns the top-k of the FP32 scores (the
     bf16 pass only decides which few hundred docs per query get one: include/gdr_hip.h).
     The image and the norm bound are SNAPSHOTS of D: after any in-place update of D (an index refresh) call refresh() before the
-    next search — a stale image can drop docs from the band, a stale norm bound can make the band too narrow.  `.D` is the raw
-    fp32 tensor for everything that is not a search (rerank, gathers).  An all-zero corpus (dnorm_max = 0) is served by the
-    fp32 path."""
+    next search — or update_rows(ids) when only those rows changed —: a stale image can drop docs from the band, a stale norm bound
+    can make the band too narrow.  `.D` is the raw fp32 tensor for everything that is not a search (rerank, gathers).  An all-zero
+    corpus (dnorm_max = 0) is served by the fp32 path.
+    masks=True: ops.sim_topk(Q, P, k, live=... / allowed=...) goes through the masked pre-filter (gdr_sim_topk_prefilter_masked:
+    the exact fp32 top-k over the live / allowed rows) wherever the unmasked call would take the pre-filter.  The
+    default is False and then a masked call takes the plain fp32 path, launch for launch as before the masked form existed: the
+    two paths return the same documents, but the pre-filter's values are the same dot products summed in another order, and the
+    bits of the default object's masked lists are pinned (tests/test_gpu_live_search.py, test_gpu_query_mask.py,
+    test_gpu_query_gather.py).  So the masked route is chosen here, where the +50 % memory of the image is chosen."""
 
-    def __init__(self, D):
+    def __init__(self, D, masks=False):
         _need_cuda(D)
-        self.D = _f32c(D)
-        self.shape, self.dtype, self.device = self.D.shape, self.D.dtype, self.D.device
-        self.D16 = torch.empty(self.D.shape, dtype=torch.bfloat16, device=self.D.device)
+        self.masks = bool(masks)
+        self._norm2 = torch.zeros(1, dtype=torch.float32, device=D.device)
+        self._bind(_f32c(D))
+        self._D16_buf = torch.empty(self.D.shape, dtype=torch.bfloat16, device=self.D.device)
         self.refresh()
+
+    def _bind(self, D):
+        self.D = D
+        self.shape, self.dtype, self.device = D.shape, D.dtype, D.device
+
+    @property
+    def D16(self):
+        """bf16 [N, d]: the image of D (a view of the backing buffer, which rebind() grows geometrically)."""
+        return self._D16_buf[:self.D.shape[0]]
+
+    def _read_norm(self):
+        self.dnorm_max = float(self._norm2.item()) ** 0.5 * (1.0 + 1e-6)   # the squared norm is itself rounded
 
     def refresh(self):
         """Re-derive the bf16 image and the largest row norm from the current contents of D (one sync)."""
-        check(lib().gdr_cast_f32_bf16(ptr(self.D), ptr(self.D16), self.D.numel(), stream_ptr()), "gdr_cast_f32_bf16")
-        m = torch.empty(1, dtype=torch.float32, device=self.D.device)
-        check(lib().gdr_row_norm2_max(ptr(self.D), self.D.shape[0], self.D.shape[1], ptr(m), stream_ptr()), "gdr_row_norm2_max")
-        self.dnorm_max = float(m.item()) ** 0.5 * (1.0 + 1e-6)       # the squared norm is itself rounded
+        check(lib().gdr_cast_f32_bf16(ptr(self.D), ptr(self._D16_buf), self.D.numel(), stream_ptr()), "gdr_cast_f32_bf16")
+        check(lib().gdr_row_norm2_max(ptr(self.D), self.D.shape[0], self.D.shape[1], ptr(self._norm2), stream_ptr()), "gdr_row_norm2_max")
+        self._read_norm()
+        return self
+
+    def update_rows(self, ids):
+        """Rows `ids` of D were rewritten: their rows of the image are re-derived (the bits refresh() would give) and dnorm_max is
+        raised to their largest norm if that is larger — ONE gdr_prefilter_update_rows call and a 4-byte read-back.  dnorm_max only
+        grows until refresh() is called (a bound that is too large costs band width, never exactness).  ids: row ids in [0, N), any
+        integer tensor / list, repeats allowed; checked where they are (host ids: no sync; device ids: one more)."""
+        ids = torch.as_tensor(ids).reshape(-1)
+        if ids.numel() == 0:
+            return self
+        if ids.dtype.is_floating_point or ids.dtype == torch.bool:
+            raise _ffi.GdrError(f"PrefilteredCorpus.update_rows: ids must be integers, got {ids.dtype}")
+        N, d = self.D.shape
+        if int(ids.min()) < 0 or int(ids.max()) >= N:
+            raise _ffi.GdrError(f"PrefilteredCorpus.update_rows: row ids must lie in [0, {N})")
+        if d % 8:
+            return self.refresh()                                    # no image the pre-filter could use: keep the snapshot whole
+        rows = ids.to(device=self.D.device, dtype=torch.int32).contiguous()
+        check(lib().gdr_prefilter_update_rows(ptr(self.D), ptr(self._D16_buf), d, ptr(rows), rows.numel(), ptr(self._norm2), stream_ptr()),
+              "gdr_prefilter_update_rows")
+        self._read_norm()
+        return self
+
+    def rebind(self, D_new):
+        """The corpus grew: D_new is fp32 [N' >= N, d] whose first N rows hold the data D held (GDRRetriever's geometrically grown
+        buffer, reallocated or not).  The image keeps its first N rows — its buffer grows geometrically when N' does not fit — and
+        rows N .. N'-1 are derived by update_rows."""
+        _need_cuda(D_new)
+        N, d = self.D.shape
+        if D_new.dtype != torch.float32 or D_new.dim() != 2 or D_new.shape[1] != d or D_new.shape[0] < N or D_new.device != self.D.device:
+            raise _ffi.GdrError(f"PrefilteredCorpus.rebind: an fp32 [N' >= {N}, {d}] tensor on {self.D.device}, not {D_new.dtype} {tuple(D_new.shape)}")
+        D_new = _f32c(D_new)
+        N2 = D_new.shape[0]
+        if N2 > self._D16_buf.shape[0]:
+            buf = torch.empty((max(N2, N + N // 2 + 64), d), dtype=torch.bfloat16, device=self.D.device)
+            buf[:N].copy_(self._D16_buf[:N])
+            self._D16_buf = buf
+        self._bind(D_new)
+        if N2 > N:
+            self.update_rows(torch.arange(N, N2, dtype=torch.int32, device=self.D.device))
         return self
 
 
@@ -513,16 +574,44 @@ PREFILTER_MIN_BATCH = 1           # the pre-filter serves every batch size: at B
                                   # the bf16 image (half the bytes of the fp32 stream): 0.205 vs 0.241 ms at B = 1
 
 
-def _sim_topk_prefilter_raw(Q, P, k, idx_offset, workspace):
+def prefilter_route(B, d, k, flags, dnorm_max, masked, masks):
+    """Whether ops.sim_topk serves a call over a PrefilteredCorpus through the bf16 pre-filter (host only).  The unmasked conditions:
+    B >= PREFILTER_MIN_BATCH, d % 8 == 0, d <= 1024, k <= PREFILTER_MAX_K, no SIM_EXHAUSTIVE, dnorm_max > 0 (an all-zero corpus has no
+    band: the fp32 path serves it).  masked: the call has live= or allowed=; it takes the (masked) pre-filter only when the corpus
+    was built with masks=True."""
+    if masked and not masks:
+        return False
+    return not (B < PREFILTER_MIN_BATCH or d % 8 or d > 1024 or (flags & _ffi.SIM_EXHAUSTIVE) or k > PREFILTER_MAX_K or not dnorm_max > 0.0)
+
+
+def _sim_topk_prefilter_raw(Q, P, k, idx_offset, workspace, live=None, allowed=None):
     B, d = Q.shape
     N = P.D.shape[0]
-    need = lib().gdr_sim_topk_prefilter_workspace_bytes(B, N, d, k)
-    ws = (workspace or Workspace(Q.device)).get(need)
     vals = torch.empty((B, k), dtype=torch.float32, device=Q.device)
     idx = torch.empty((B, k), dtype=torch.int32, device=Q.device)
     status = torch.empty((B,), dtype=torch.int32, device=Q.device)
-    check(lib().gdr_sim_topk_prefilter(ptr(Q), B, ptr(P.D), ptr(P.D16), P.dnorm_max, N, d, k, idx_offset, ptr(vals), ptr(idx),
-                                       ptr(status), ptr(ws), ws.numel(), stream_ptr()), "gdr_sim_topk_prefilter")
+    if live is None and allowed is None:
+        need = lib().gdr_sim_topk_prefilter_workspace_bytes(B, N, d, k)
+        ws = (workspace or Workspace(Q.device)).get(need)
+        check(lib().gdr_sim_topk_prefilter(ptr(Q), B, ptr(P.D), ptr(P.D16), P.dnorm_max, N, d, k, idx_offset, ptr(vals), ptr(idx),
+                                           ptr(status), ptr(ws), ws.numel(), stream_ptr()), "gdr_sim_topk_prefilter")
+        return vals, idx, status
+    flags = _ffi.SIM_QUERY_MASK if allowed is not None else _ffi.SIM_LIVE_MASK   # one layout per call: live is ANDed in below
+    need = lib().gdr_sim_topk_prefilter_masked_workspace_bytes(B, N, d, k, flags)
+    ws = (workspace or Workspace(Q.device)).get(need)
+    if allowed is not None:                                          # B bitmaps, M bytes apart, are the head of the workspace
+        words = allowed.words
+        M = (4 * words.shape[1] + 255) // 256 * 256
+        slots = ws[:B * M].view(torch.int32).view(B, M // 4)[:, :words.shape[1]]   # the padding up to M is ignored: left as it is
+        if live is not None:
+            torch.bitwise_and(words, live.words, out=slots)
+        else:
+            slots.copy_(words)
+    else:                                                            # the bitmap is the head of the workspace (stream-ordered copy)
+        words = live.words
+        ws[:words.numel() * 4].view(torch.int32).copy_(words)
+    check(lib().gdr_sim_topk_prefilter_masked(ptr(Q), B, ptr(P.D), ptr(P.D16), P.dnorm_max, N, d, k, idx_offset, ptr(vals), ptr(idx),
+                                              ptr(status), flags, ptr(ws), ws.numel(), stream_ptr()), "gdr_sim_topk_prefilter_masked")
     return vals, idx, status
 
 

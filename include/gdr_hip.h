@@ -288,7 +288,8 @@ int gdr_t5_encoder_forward_bf16(const GdrT5EncoderWeights* w, const int64_t* ids
  *   filter pass then keeps every row and the list either holds the whole corpus (exact) or overflows: status[q] = 1, and the re-run is
  *   GDR_SIM_EXHAUSTIVE | GDR_SIM_LIVE_MASK.  With the flag clear nothing changes: layout, launches and results are as before.
  *   gdr_sim_topk_prefilter takes no flags and stays UNMASKED: a masked search over such a corpus is gdr_sim_topk's (the same fp32
- *   answer by that entry point's own contract).
+ *   answer by that entry point's own contract), or gdr_sim_topk_prefilter_masked's (gdr_hip_prefilter_mask.h, included below: the same
+ *   answer through the bf16 pre-filter, for the live mask and for per-query bitmaps).
  * GDR_SIM_QUERY_MASK (gdr_sim_topk, gdr_sim_topk_bf16): a row filter PER QUERY.  The first B * M bytes of `workspace` (M as above) are
  *   then the caller's input: B bitmaps in GDR_SIM_LIVE_MASK's format, bitmap q at byte q * M; bit r % 32 of its int32 word r / 32 set =
  *   row r of D may be returned for query q.  Bits past N and the padding up to M are ignored, the library only reads the region, its
@@ -357,7 +358,8 @@ int gdr_sim_topk_bf16(const void* Q, int B, const void* D, int64_t N, int d, int
  * tail sorts 4k band keys in one workgroup's LDS and rescores them in fp32; a deeper list is gdr_sim_topk's: the same answer).
  * The workspace depends on d beyond the bf16 queries it holds: the filter pass keeps every doc above the sample threshold MINUS 2 eps_q,
  * and 2 eps_q measured in deviations of a query's scores grows like sqrt(d), so the candidate list is sized for that lowered threshold
- * (never smaller than gdr_sim_topk's list for the same B, N, k; non-decreasing in d).  The sizing is an expectation for scores that are
+ * (never smaller than gdr_sim_topk's list for the same B, N, k; non-decreasing in d, and in k: the answer is the largest layout of any
+ * k' <= k, as gdr_sim_topk_workspace_bytes').  The sizing is an expectation for scores that are
  * roughly Gaussian and row norms within 1.25 of their rms; other corpora are served by the status contract above. */
 size_t gdr_sim_topk_prefilter_workspace_bytes(int B, int64_t N, int d, int k);
 int gdr_sim_topk_prefilter(const float* Q, int B, const float* D, const void* D_bf16, float dnorm_max, int64_t N, int d, int k,
@@ -856,4 +858,8 @@ int gdr_beam_search_table(const float* table, int B, int out_vocab, int num_beam
 #ifdef __cplusplus
 }
 #endif
+
+/* The pre-filtered search over live rows / per-query filters and the row-wise upkeep of the bf16 image: declared in a header of their own. */
+#include "gdr_hip_prefilter_mask.h"
+
 #endif /* GDR_HIP_H */
