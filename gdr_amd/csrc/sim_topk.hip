@@ -17,6 +17,11 @@
 //               lower doc id" — then bitonic-sorts them in LDS and writes values + ids.
 //
 // n_sample ≈ sqrt(k·N) balances list length against survivors.  Small corpora take steps 1, 2, 4 only.
+//
+// Steps 1 - 3, with the row mask of GDR_SIM_LIVE_MASK / GDR_SIM_QUERY_MASK between them, are written once: run_candidate_passes.
+// gdr_sim_topk[_bf16] (sim_topk_impl) puts step 4 behind it; the bf16 pre-filter (prefilter_impl) puts the query prep in front and its
+// rescoring tail behind.  The bitmaps at the head of a workspace are described once too (MaskHead), as are the argument checks
+// (check_search_args), the "largest plan up to k" of the workspace questions (largest_plan_up_to) and the select launch (launch_select).
 #include <stdlib.h>
 
 #include <map>
@@ -77,6 +82,33 @@ static SimPlan make_plan(int B, int64_t N, int k, bool exhaustive, double surviv
 }
 
 // (the orderable keys, their 64-bit pack and the bitonic sorts: select.h)
+
+// Four fp32 -> four bf16, stored as 8 bytes (v_cvt_pk_bf16_f32: RNE, NaN-safe): THE bf16 image of a corpus row or a query, wherever it
+// is made.
+__device__ __forceinline__ void store_bf16x4(uint2* dst, const float4& v) {
+  union {
+    __bf16 h[4];
+    uint2 u;
+  } o;
+  o.h[0] = (__bf16)v.x, o.h[1] = (__bf16)v.y, o.h[2] = (__bf16)v.z, o.h[3] = (__bf16)v.w;
+  *dst = o.u;
+}
+
+// ||row||^2 by one wave, in every lane: a lane's fmaf chain over its 16-byte pieces (lane, lane + 64, ...), then the shuffle tree.
+// each(c, v) sees every piece.  The bits are a contract between row_norm2_max_kernel and prefilter_update_rows_kernel
+// (include/gdr_hip.h at gdr_prefilter_update_rows): both call this.
+template <class Each>
+__device__ __forceinline__ float wave_row_norm2(const float* __restrict__ row, int d, int lane, Each each) {
+  float ss = 0.f;
+  for (int c = lane * 4; c < d; c += 256) {
+    const float4 v = *reinterpret_cast<const float4*>(row + c);
+    ss = fmaf(v.x, v.x, fmaf(v.y, v.y, fmaf(v.z, v.z, fmaf(v.w, v.w, ss))));
+    each(c, v);
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) ss += __shfl_xor(ss, off);
+  return ss;
+}
 
 // Given hist[256] (LDS) find the highest bin b with  sum(hist[b..255]) >= need.
 // Returns b and the count strictly above it through *above.  Every thread of the block calls it (blockDim >= 256).
@@ -614,20 +646,29 @@ static int sliced_ns(int64_t len, int kpad) {
 // pre-filter stops where its one-workgroup tail does (it sorts 4k band keys in LDS and rescores them in fp32).
 constexpr int SIM_TOPK_MAX_K = SEL_SORT_MAX, SIM_ONE_WAVE_MAX_K = 1024, PREFILTER_MAX_K = 1024;
 
-// topk_select_kernel<MERGE, DEEP = true> for 1024 < k <= SIM_TOPK_MAX_K: kpad = 2048 .. 8192 keys of dynamic LDS, one workgroup of
-// DEEP_THREADS per query.  The merge form runs 256 threads at k <= 1024; here 1024 won: 0.056 / 0.106 / 0.187 ms at 1024 / 512 / 256
-// threads for (G, B, k) = (8, 64, 2048), 0.303 / 0.413 / 0.757 ms at k = 8192 (16 384 keys fit 1024 threads' register cache, and the
-// sort has 16 waves).  kpad is a multiple of 2 x 16 waves, as bitonic_desc asks.
+// The one launch of topk_select_kernel<MERGE>, one workgroup per query.  k <= 1024: the one-wave sort, `threads` lanes (the caller's:
+// 1024 for a candidate list, SEL_THREADS for a merge), kpad = sel_pow2(k, 1).  1024 < k <= SIM_TOPK_MAX_K: DEEP = true, kpad = 2048 ..
+// 8192 keys of dynamic LDS, DEEP_THREADS lanes whatever the caller runs below.  The merge form runs 256 threads at k <= 1024; here
+// 1024 won: 0.056 / 0.106 / 0.187 ms at 1024 / 512 / 256 threads for (G, B, k) = (8, 64, 2048), 0.303 / 0.413 / 0.757 ms at k = 8192
+// (16 384 keys fit 1024 threads' register cache, and the sort has 16 waves).  kpad is a multiple of 2 x 16 waves, as bitonic_desc asks.
+// what / what_deep: the kernel's name in a launch error of the two forms.
 constexpr int DEEP_THREADS = 1024;
 template <bool MERGE>
-static int launch_select_deep(const float* vals, const int32_t* idxs, const int32_t* cnt, int64_t cap, int G, int B, int k,
-                              int32_t idx_offset, const float* thr, float* out_val, int32_t* out_idx, int32_t* status, int rs, int es,
-                              const char* what, hipStream_t stream) {
-  const int kpad = sel_pow2(k, 2048);
-  auto* kern = topk_select_kernel<MERGE, true>;
-  if (int rc = ensure_dyn_lds(reinterpret_cast<const void*>(kern), SEL_SORT_MAX * 8, what)) return rc;
-  hipLaunchKernelGGL(kern, dim3(B), dim3(DEEP_THREADS), (size_t)kpad * sizeof(unsigned long long), stream, vals, idxs, cnt, cap, G, B, k,
-                     kpad, idx_offset, thr, out_val, out_idx, status, rs, es);
+static int launch_select(const float* vals, const int32_t* idxs, const int32_t* cnt, int64_t cap, int G, int B, int k, int32_t idx_offset,
+                         const float* thr, float* out_val, int32_t* out_idx, int32_t* status, int rs, int es, int threads, const char* what,
+                         const char* what_deep, hipStream_t stream) {
+  if (k > SIM_ONE_WAVE_MAX_K) {
+    const int kpad = sel_pow2(k, 2048);
+    auto* kern = topk_select_kernel<MERGE, true>;
+    if (int rc = ensure_dyn_lds(reinterpret_cast<const void*>(kern), SEL_SORT_MAX * 8, what_deep)) return rc;
+    hipLaunchKernelGGL(kern, dim3(B), dim3(DEEP_THREADS), (size_t)kpad * sizeof(unsigned long long), stream, vals, idxs, cnt, cap, G, B, k,
+                       kpad, idx_offset, thr, out_val, out_idx, status, rs, es);
+    GDR_CHECK_LAUNCH(what_deep);
+    return GDR_OK;
+  }
+  const int kpad = sel_pow2(k, 1);
+  hipLaunchKernelGGL(topk_select_kernel<MERGE>, dim3(B), dim3(threads), kpad * sizeof(unsigned long long), stream, vals, idxs, cnt, cap, G,
+                     B, k, kpad, idx_offset, thr, out_val, out_idx, status, rs, es);
   GDR_CHECK_LAUNCH(what);
   return GDR_OK;
 }
@@ -642,6 +683,22 @@ static int launch_select_deep(const float* vals, const int32_t* idxs, const int3
 // them, and a list they overflow is reported through status like any other.
 static size_t live_mask_bytes(int64_t N) {
   return align_up((size_t)((N + 31) / 32) * sizeof(uint32_t), 256);
+}
+// The bitmaps at the head of a workspace, from the call's flags: one of live_mask_bytes(N) (GDR_SIM_LIVE_MASK, read by every query:
+// qstride 0) or B of them (GDR_SIM_QUERY_MASK, the gather mode included: query q's at word q * qstride).  Everything else the call
+// lays out — make_plan's `base`, the gather layout — starts `bytes` in.
+struct MaskHead {
+  size_t bytes;     // 0 without either flag
+  int64_t qstride;  // 32-bit words between two queries' bitmaps
+  bool masked;
+};
+static MaskHead mask_head(int flags, int B, int64_t N) {
+  const bool per_query = (flags & GDR_SIM_QUERY_MASK) != 0;
+  MaskHead h{};
+  h.masked = per_query || (flags & GDR_SIM_LIVE_MASK) != 0;
+  h.bytes = h.masked ? (per_query ? (size_t)B : 1) * live_mask_bytes(N) : 0;
+  h.qstride = per_query ? (int64_t)(live_mask_bytes(N) / sizeof(uint32_t)) : 0;
+  return h;
 }
 
 // GDR_SIM_ROW_GATHER (sim_rows.hip): bits 8..16 of flags hold the per-query list capacity in chunks of SEL_CHUNK rows, 0 reads as 2.
@@ -741,6 +798,103 @@ static int launch_live_mask(const SimEpilogue& ep, const SimPlan& p, int B, int6
   return GDR_OK;
 }
 
+// ---- THE candidate-pass sequence: steps 1 - 3 of the top of this file, with the row mask between them ----------------------------
+//   sample -> [mask [0, n_slots)] -> threshold -> ( [fix-up] -> filter -> [mask [n_slots, cnt)] )   (...) where p.stride > 1, [...] where
+// head.masked.  Every top-k entry point over a corpus runs it, once, and differs only in what it hands in and in the tail it puts behind:
+//   sim_topk_impl    D, Q as given (fp32 or bf16), stream_mode by the shape and GDR_SIM_NO_STREAM; sub = null; the sliced threshold where
+//                    the stream kernels ran; then its select.
+//   prefilter_impl   the bf16 image and the bf16 queries of sim_qprep_kernel; sub = eps2 (the filter pass keeps s~ >= L - 2 eps_q);
+//                    never sliced; then prefilter_tail_kernel.
+// ws: the workspace (the bitmaps of `head` at its start, the plan p laid out behind head.bytes).  ns_thr: the slices of the threshold, 0 =
+// sim_threshold_kernel with one 1024-thread workgroup per query; sa (needed with ns_thr > 0, filled here with the lists in any case): the
+// caller's SlicedArgs, its k / kpad and output side set.  ep, thr: the lists and thresholds the passes left, for the caller's tail.
+static int run_candidate_passes(const void* D, const void* Q, bool bf16, bool stream_mode, int B, int64_t N, int d, const SimPlan& p,
+                                const MaskHead& head, char* ws, int k, const float* sub, int ns_thr, SlicedArgs* sa, hipStream_t stream,
+                                SimEpilogue& ep, float*& thr) {
+  const uint32_t* live = head.masked ? reinterpret_cast<const uint32_t*>(ws) : nullptr;
+  ep = SimEpilogue{};
+  ep.cand_val = reinterpret_cast<float*>(ws + p.off_val);
+  ep.cand_idx = reinterpret_cast<int32_t*>(ws + p.off_idx);
+  ep.cand_cnt = reinterpret_cast<int32_t*>(ws + p.off_cnt);
+  thr = reinterpret_cast<float*>(ws + p.off_thr);
+  ep.thr = thr;
+  ep.status = nullptr;  // overflow is reported per query by the caller's tail (cnt > cap)
+  ep.cap = (int32_t)p.cap;
+  ep.tile_stride = p.stride;
+  const auto core_pass = [&](int mode) {
+    ep.mode = mode;
+    return stream_mode ? launch_sim_stream(D, N, Q, B, d, ep, bf16, stream) : launch_sim_gemm(D, N, Q, B, d, ep, bf16, stream);
+  };
+  GDR_TRY(core_pass(1));
+  if (head.masked) GDR_TRY(launch_live_mask(ep, p, B, 0, p.n_slots, live, head.qstride, N, stream));  // the threshold sees allowed sample scores only
+  if (sa) {
+    sa->vals = ep.cand_val, sa->idxs = ep.cand_idx, sa->cnt = ep.cand_cnt, sa->cap = p.cap, sa->n_slots = (int)p.n_slots, sa->k = k;
+    sa->thr = thr, sa->sub = sub, sa->part = reinterpret_cast<unsigned long long*>(ws + p.off_part);
+  }
+  if (ns_thr) {
+    sa->NS = ns_thr;
+    ProfScope prof(PROF_SELECT, 0.0, stream);
+    hipLaunchKernelGGL(sim_sliced_select_kernel<true>, dim3(B * ns_thr), dim3(SL_THREADS), 0, stream, *sa);
+    GDR_CHECK_LAUNCH("sim_sliced_select_kernel(threshold)");
+  } else {
+    // 1024 lanes per query: measured faster than 512 with twice the entries per lane (26.7 vs 37.7 us at 32 queries)
+    hipLaunchKernelGGL(sim_threshold_kernel, dim3(B), dim3(1024), 0, stream, ep.cand_val, p.cap, (int)p.n_slots, k, thr, ep.cand_cnt, sub);
+    GDR_CHECK_LAUNCH("sim_threshold_kernel");
+  }
+  if (p.stride > 1) {
+    if (head.masked) {  // fewer than k allowed sample rows (per query: of query q's bitmap): thr[q] = -inf (sim_live_thr_fixup_kernel)
+      hipLaunchKernelGGL(sim_live_thr_fixup_kernel, dim3(head.qstride ? B : 1), dim3(256), 0, stream, live, head.qstride, N,
+                         p.n_sample_tiles, p.stride, k, thr, B);
+      GDR_CHECK_LAUNCH("sim_live_thr_fixup_kernel");
+    }
+    GDR_TRY(core_pass(2));
+    if (head.masked) GDR_TRY(launch_live_mask(ep, p, B, p.n_slots, -1, live, head.qstride, N, stream));  // the survivors, disallowed rows among them
+  }
+  return GDR_OK;
+}
+
+// What gdr_sim_topk[_bf16] and the two pre-filter entry points check alike, in one order (a call with several faults is refused for
+// the first).  who: the message prefix.  pre (the pre-filter): D_bf16 and dnorm_max are arguments too, d % 8 == 0 and d <= 1024, k stops
+// at PREFILTER_MAX_K.  d8: the rows are bf16 (d % 8 == 0 for 16-byte pieces).
+static int check_search_args(const char* who, bool pre, bool d8, const void* Q, int B, const void* D, const void* D_bf16, float dnorm_max,
+                             int64_t N, int d, int k, int32_t idx_offset, const float* out_val, const int32_t* out_idx,
+                             const void* workspace) {
+  GDR_CHECK_ARG(Q && D && (!pre || D_bf16) && out_val && out_idx && workspace, "%s: null pointer", who);
+  GDR_CHECK_ARG(B > 0 && N > 0 && d > 0 && d % (d8 ? 8 : 4) == 0 && (!pre || d <= 1024), "%s: bad shape B=%d N=%lld d=%d%s", who, B,
+                (long long)N, d, pre ? " (d % 8 == 0, d <= 1024)" : "");
+  const int k_max = pre ? PREFILTER_MAX_K : SIM_TOPK_MAX_K;
+  GDR_CHECK_ARG(k >= 1 && k <= k_max && k <= N, "%s: k=%d must be in [1, min(%d, N)]", who, k, k_max);
+  GDR_CHECK_ARG(N < 0x7fffffffLL - 256, "%s: shard too large for int32 doc ids", who);
+  GDR_CHECK_ARG((int64_t)idx_offset + N <= 0x7fffffffLL,
+                "%s: idx_offset=%d + N=%lld leaves int32 doc ids (the largest id, idx_offset + N - 1, must be < 2^31 - 1)", who,
+                (int)idx_offset, (long long)N);
+  if (pre) GDR_CHECK_ARG(dnorm_max > 0.f && dnorm_max < INFINITY, "%s: dnorm_max must be the largest row norm of D (> 0, finite)", who);
+  GDR_CHECK_ARG(((uintptr_t)Q & 15) == 0 && ((uintptr_t)D & 15) == 0 && (!pre || ((uintptr_t)D_bf16 & 15) == 0) && ((uintptr_t)workspace & 255) == 0,
+                "%s: Q, D%s must be 16-byte and workspace 256-byte aligned", who, pre ? ", D_bf16" : "");
+  return GDR_OK;
+}
+
+// The largest total(k') over k' <= k, where total(k') is the bytes of a plan of depth k' (make_plan's, or one built on it): what the
+// workspace questions answer (see gdr_sim_topk_workspace_bytes for why, and for where the candidates sit).
+template <class Total>
+static size_t largest_plan_up_to(int64_t N, int k, Total total) {
+  size_t best = total(k);
+  double target = sqrt((double)k * (double)N);
+  if (target < k) target = k;
+  const int64_t ts_k = (int64_t)((target + TILE - 1) / TILE);
+  for (int64_t ts = 1; ts <= ts_k; ++ts) {
+    const double edge = (double)(ts * TILE);
+    const int64_t ends[2] = {(int64_t)(edge * edge / (double)N), ts * TILE};
+    for (const int64_t e : ends)
+      for (int64_t kk = e - 1; kk <= e + 1; ++kk)
+        if (kk >= 1 && kk < k) {
+          const size_t t = total((int)kk);
+          if (t > best) best = t;
+        }
+  }
+  return best;
+}
+
 }  // namespace gdr
 
 // The size a caller is told: the largest plan of any k' <= k, so that the answer never shrinks when k grows and a buffer sized for
@@ -758,29 +912,14 @@ extern "C" size_t gdr_sim_topk_workspace_bytes(int B, int64_t N, int d, int k, i
     if (cap == 0 || (flags & (GDR_SIM_QUERY_MASK | GDR_SIM_LIVE_MASK | GDR_SIM_EXHAUSTIVE)) != GDR_SIM_QUERY_MASK ||
         (cap > 2 * gdr::SEL_CHUNK && k > gdr::SIM_ONE_WAVE_MAX_K))
       return 0;  // no such call: gdr_sim_topk refuses it
-    return (size_t)B * gdr::live_mask_bytes(N) + gdr::sim_rows_workspace_bytes(B, cap, k);
+    return gdr::mask_head(flags, B, N).bytes + gdr::sim_rows_workspace_bytes(B, cap, k);
   }
   if ((flags & GDR_SIM_LIVE_MASK) && (flags & GDR_SIM_QUERY_MASK)) return 0;  // no such call: gdr_sim_topk refuses the pair
-  if (flags & GDR_SIM_QUERY_MASK)  // one row bitmap per query in front of the same plan
-    return gdr_sim_topk_workspace_bytes(B, N, d, k, flags & ~GDR_SIM_QUERY_MASK) + (size_t)B * gdr::live_mask_bytes(N);
-  if (flags & GDR_SIM_LIVE_MASK)  // the caller's row bitmap in front of the same plan
-    return gdr_sim_topk_workspace_bytes(B, N, d, k, flags & ~GDR_SIM_LIVE_MASK) + gdr::live_mask_bytes(N);
-  size_t best = gdr::make_plan(B, N, k, exhaustive).total;
-  if (exhaustive) return best;  // stride 1 whatever k: the plan does not depend on k
-  double target = sqrt((double)k * (double)N);
-  if (target < k) target = k;
-  const int64_t ts_k = (int64_t)((target + gdr::TILE - 1) / gdr::TILE);
-  for (int64_t ts = 1; ts <= ts_k; ++ts) {
-    const double edge = (double)(ts * gdr::TILE);
-    const int64_t ends[2] = {(int64_t)(edge * edge / (double)N), ts * gdr::TILE};
-    for (const int64_t e : ends)
-      for (int64_t kk = e - 1; kk <= e + 1; ++kk)
-        if (kk >= 1 && kk < k) {
-          const size_t t = gdr::make_plan(B, N, (int)kk, false).total;
-          if (t > best) best = t;
-        }
-  }
-  return best;
+  const gdr::MaskHead head = gdr::mask_head(flags, B, N);
+  if (head.masked)  // the caller's row bitmap, or one per query, in front of the same plan
+    return gdr_sim_topk_workspace_bytes(B, N, d, k, flags & ~(GDR_SIM_LIVE_MASK | GDR_SIM_QUERY_MASK)) + head.bytes;
+  if (exhaustive) return gdr::make_plan(B, N, k, true).total;  // stride 1 whatever k: the plan does not depend on k
+  return gdr::largest_plan_up_to(N, k, [&](int kk) { return gdr::make_plan(B, N, kk, false).total; });
 }
 
 namespace gdr {
@@ -789,12 +928,7 @@ __global__ __launch_bounds__(256) void cast_f32_bf16_kernel(const float4* __rest
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n4) return;
   const float4 v = in[i];
-  union {
-    __bf16 h[4];
-    uint2 u;
-  } o;
-  o.h[0] = (__bf16)v.x, o.h[1] = (__bf16)v.y, o.h[2] = (__bf16)v.z, o.h[3] = (__bf16)v.w;  // v_cvt_pk_bf16_f32: RNE, NaN-safe
-  out[i] = o.u;
+  store_bf16x4(out + i, v);
 }
 
 static int sim_topk_impl(const void* Q, int B, const void* D, int64_t N, int d, int k, int32_t idx_offset, float* out_val,
@@ -837,16 +971,7 @@ int gdr::sim_topk_impl(const void* Q, int B, const void* D, int64_t N, int d, in
                        float* out_val, int32_t* out_idx, int32_t* status, int flags, void* workspace,
                        size_t workspace_bytes, bool bf16, hipStream_t stream) {
   if (B == 0) return GDR_OK;  // empty query batch
-  GDR_CHECK_ARG(Q && D && out_val && out_idx && workspace, "sim_topk: null pointer");
-  GDR_CHECK_ARG(B > 0 && N > 0 && d > 0 && d % (bf16 ? 8 : 4) == 0, "sim_topk: bad shape B=%d N=%lld d=%d", B,
-                (long long)N, d);
-  GDR_CHECK_ARG(k >= 1 && k <= SIM_TOPK_MAX_K && k <= N, "sim_topk: k=%d must be in [1, min(%d, N)]", k, SIM_TOPK_MAX_K);
-  GDR_CHECK_ARG(N < 0x7fffffffLL - 256, "sim_topk: shard too large for int32 doc ids");
-  GDR_CHECK_ARG((int64_t)idx_offset + N <= 0x7fffffffLL,
-                "sim_topk: idx_offset=%d + N=%lld leaves int32 doc ids (the largest id, idx_offset + N - 1, must be < 2^31 - 1)", (int)idx_offset,
-                (long long)N);
-  GDR_CHECK_ARG(((uintptr_t)Q & 15) == 0 && ((uintptr_t)D & 15) == 0 && ((uintptr_t)workspace & 255) == 0,
-                "sim_topk: Q, D must be 16-byte and workspace 256-byte aligned");
+  GDR_TRY(check_search_args("sim_topk", false, bf16, Q, B, D, nullptr, 0.f, N, d, k, idx_offset, out_val, out_idx, workspace));
   GDR_CHECK_ARG((flags & (GDR_SIM_LIVE_MASK | GDR_SIM_QUERY_MASK)) != (GDR_SIM_LIVE_MASK | GDR_SIM_QUERY_MASK),
                 "sim_topk: GDR_SIM_LIVE_MASK and GDR_SIM_QUERY_MASK name two workspace layouts: AND the live rows into the per-query "
                 "bitmaps on the caller's side and pass GDR_SIM_QUERY_MASK alone");
@@ -864,77 +989,38 @@ int gdr::sim_topk_impl(const void* Q, int B, const void* D, int64_t N, int d, in
     GDR_CHECK_ARG(cap <= 2 * SEL_CHUNK || k <= SIM_ONE_WAVE_MAX_K, "sim_topk: GDR_SIM_ROW_GATHER: k=%d must be <= %d with GDR_SIM_GATHER_CHUNKS(%d) > 2 "
                   "(chunks plus merge rounds; one LDS sort serves any k at 1 or 2 chunks)", k, SIM_ONE_WAVE_MAX_K, chunks);
     GDR_CHECK_ARG((int64_t)B * (cap / 16) <= 0x7fffffffLL, "sim_topk: GDR_SIM_ROW_GATHER: B=%d x %lld rows per query leaves the int32 unit list", B, (long long)cap);
-    const size_t head = (size_t)B * live_mask_bytes(N), required = head + sim_rows_workspace_bytes(B, cap, k);
+    const MaskHead head = mask_head(flags, B, N);  // the B bitmaps
+    const size_t required = head.bytes + sim_rows_workspace_bytes(B, cap, k);
     if (workspace_bytes < required) {
       set_error("sim_topk: workspace %zu < required %zu", workspace_bytes, required);
       return GDR_ENOSPC;
     }
-    return launch_sim_rows(Q, B, D, N, d, k, idx_offset, out_val, out_idx, status, static_cast<const uint32_t*>(workspace),
-                           (int64_t)(live_mask_bytes(N) / sizeof(uint32_t)), cap, static_cast<char*>(workspace) + head, bf16, stream);
+    return launch_sim_rows(Q, B, D, N, d, k, idx_offset, out_val, out_idx, status, static_cast<const uint32_t*>(workspace), head.qstride, cap,
+                           static_cast<char*>(workspace) + head.bytes, bf16, stream);
   }
   // GDR_SIM_LIVE_MASK: the first live_mask_bytes(N) bytes of the workspace are the caller's row bitmap (read only); the plan sits behind it.
   // GDR_SIM_QUERY_MASK: B such bitmaps, query q's at byte q * live_mask_bytes(N).
-  const bool per_query = (flags & GDR_SIM_QUERY_MASK) != 0;
-  const bool masked = per_query || (flags & GDR_SIM_LIVE_MASK) != 0;
-  const int64_t qstride = per_query ? (int64_t)(live_mask_bytes(N) / sizeof(uint32_t)) : 0;  // words between two queries' bitmaps
-  const SimPlan p = make_plan(B, N, k, (flags & GDR_SIM_EXHAUSTIVE) != 0, 1.0, masked ? (per_query ? (size_t)B : 1) * live_mask_bytes(N) : 0);
+  const MaskHead head = mask_head(flags, B, N);
+  const SimPlan p = make_plan(B, N, k, (flags & GDR_SIM_EXHAUSTIVE) != 0, 1.0, head.bytes);
   // A masked call is held to the size its caller was told, not to this k's own layout (which may dip below the unflagged answer,
   // see gdr_sim_topk_workspace_bytes): a buffer sized without the flag — no room reserved for the bitmap — is refused at every shape.
-  const size_t required = masked ? gdr_sim_topk_workspace_bytes(B, N, d, k, flags) : p.total;
+  const size_t required = head.masked ? gdr_sim_topk_workspace_bytes(B, N, d, k, flags) : p.total;
   if (workspace_bytes < required) {
     set_error("sim_topk: workspace %zu < required %zu", workspace_bytes, required);
     return GDR_ENOSPC;
   }
-  char* ws = static_cast<char*>(workspace);
-  const uint32_t* live = masked ? reinterpret_cast<const uint32_t*>(ws) : nullptr;
-  SimEpilogue ep{};
-  ep.cand_val = reinterpret_cast<float*>(ws + p.off_val);
-  ep.cand_idx = reinterpret_cast<int32_t*>(ws + p.off_idx);
-  ep.cand_cnt = reinterpret_cast<int32_t*>(ws + p.off_cnt);
-  float* thr = reinterpret_cast<float*>(ws + p.off_thr);
-  ep.thr = thr;
-  ep.status = nullptr;  // overflow is reported per query by the select kernel (cnt > cap)
-  ep.cap = (int32_t)p.cap;
-  ep.tile_stride = p.stride;
-  ep.mode = 1;
   const bool stream_mode = sim_stream_supported(B, d, bf16) && !(flags & GDR_SIM_NO_STREAM);
-  int rc = stream_mode ? launch_sim_stream(D, N, Q, B, d, ep, bf16, stream) : launch_sim_gemm(D, N, Q, B, d, ep, bf16, stream);
-  if (rc) return rc;
-  if (masked) GDR_TRY(launch_live_mask(ep, p, B, 0, p.n_slots, live, qstride, N, stream));  // the threshold sees live sample scores only
-  const int sel_threads = 1024;  // 1024 lanes per query: measured faster than 512 with twice the entries per lane (26.7 vs 37.7 us at 32 queries)
-  const int kpad = sel_pow2(k, 1);
-  static const bool sliced_on = [] {
-    const char* e = getenv("GDR_SIM_SLICED");  // A/B knob: 0 = one workgroup per query for the threshold / select tails (the r05 form)
-    return e ? atoi(e) != 0 : true;
-  }();
+  static const bool sliced_on = env_flag("GDR_SIM_SLICED", true);  // A/B knob: 0 = one workgroup per query for the threshold / select tails (the r05 form)
   // the stream kernels' sample pass zeroes the tickets: only their calls may take the sliced tails
-  SlicedArgs sa{};
-  sa.vals = ep.cand_val, sa.idxs = ep.cand_idx, sa.cnt = ep.cand_cnt, sa.cap = p.cap, sa.n_slots = (int)p.n_slots, sa.k = k, sa.kpad = kpad;
-  sa.idx_offset = idx_offset, sa.thr = thr, sa.sub = nullptr, sa.part = reinterpret_cast<unsigned long long*>(ws + p.off_part);
-  sa.out_val = out_val, sa.out_idx = out_idx, sa.status = status;
-  const int ns_thr = (stream_mode && sliced_on && B <= 32) ? sliced_ns(p.n_slots, kpad) : 0;
-  const int ns_sel = (stream_mode && sliced_on && B <= 32) ? sliced_ns(p.cap, kpad) : 0;
-  if (ns_thr) {
-    sa.NS = ns_thr;
-    ProfScope prof(PROF_SELECT, 0.0, stream);
-    hipLaunchKernelGGL(sim_sliced_select_kernel<true>, dim3(B * ns_thr), dim3(SL_THREADS), 0, stream, sa);
-    GDR_CHECK_LAUNCH("sim_sliced_select_kernel(threshold)");
-  } else {
-    hipLaunchKernelGGL(sim_threshold_kernel, dim3(B), dim3(sel_threads), 0, stream, ep.cand_val, p.cap, (int)p.n_slots,
-                       k, thr, ep.cand_cnt, (const float*)nullptr);
-    GDR_CHECK_LAUNCH("sim_threshold_kernel");
-  }
-  if (p.stride > 1) {
-    if (masked) {  // fewer than k live sample rows (per query: of query q's bitmap): thr[q] = -inf (sim_live_thr_fixup_kernel)
-      hipLaunchKernelGGL(sim_live_thr_fixup_kernel, dim3(per_query ? B : 1), dim3(256), 0, stream, live, qstride, N, p.n_sample_tiles,
-                         p.stride, k, thr, B);
-      GDR_CHECK_LAUNCH("sim_live_thr_fixup_kernel");
-    }
-    ep.mode = 2;
-    rc = stream_mode ? launch_sim_stream(D, N, Q, B, d, ep, bf16, stream) : launch_sim_gemm(D, N, Q, B, d, ep, bf16, stream);
-    if (rc) return rc;
-    if (masked) GDR_TRY(launch_live_mask(ep, p, B, p.n_slots, -1, live, qstride, N, stream));  // the survivors, dead rows among them
-  }
+  const bool sliced = stream_mode && sliced_on && B <= 32;
+  const int kpad = sel_pow2(k, 1);
+  const int ns_thr = sliced ? sliced_ns(p.n_slots, kpad) : 0, ns_sel = sliced ? sliced_ns(p.cap, kpad) : 0;
+  SlicedArgs sa{};  // the output side; run_candidate_passes adds the lists
+  sa.kpad = kpad, sa.idx_offset = idx_offset, sa.out_val = out_val, sa.out_idx = out_idx, sa.status = status;
+  SimEpilogue ep;
+  float* thr;
+  GDR_TRY(run_candidate_passes(D, Q, bf16, stream_mode, B, N, d, p, head, static_cast<char*>(workspace), k, nullptr, ns_thr, &sa, stream, ep, thr));
+  // step 4: the exact top-k of every list, overflow (cnt > cap) to status
   if (ns_sel) {
     sa.NS = ns_sel;
     ProfScope prof(PROF_SELECT, 0.0, stream);
@@ -942,14 +1028,8 @@ int gdr::sim_topk_impl(const void* Q, int B, const void* D, int64_t N, int d, in
     GDR_CHECK_LAUNCH("sim_sliced_select_kernel(select)");
     return GDR_OK;
   }
-  if (k > SIM_ONE_WAVE_MAX_K)
-    return launch_select_deep<false>(ep.cand_val, ep.cand_idx, ep.cand_cnt, p.cap, 1, B, k, idx_offset, thr, out_val, out_idx,
-                                     status, 0, 1, "topk_select_kernel<deep>", stream);
-  hipLaunchKernelGGL(topk_select_kernel<false>, dim3(B), dim3(sel_threads), kpad * sizeof(unsigned long long), stream,
-                     ep.cand_val, ep.cand_idx, ep.cand_cnt, p.cap, 1, B, k, kpad, idx_offset, (const float*)thr, out_val,
-                     out_idx, status, 0, 1);
-  GDR_CHECK_LAUNCH("topk_select_kernel");
-  return GDR_OK;
+  return launch_select<false>(ep.cand_val, ep.cand_idx, ep.cand_cnt, p.cap, 1, B, k, idx_offset, thr, out_val, out_idx, status, 0, 1, 1024,
+                              "topk_select_kernel", "topk_select_kernel<deep>", stream);
 }
 
 namespace gdr {
@@ -973,9 +1053,10 @@ namespace gdr {
 // those rows only (any upper bound widens the band, never breaks it), and the sample threshold L is the k-th largest ALLOWED sample
 // score, which is <= the k-th largest allowed s~.  L taken over all sample rows would not do: with a query's best rows disallowed it
 // lies above t~_k - 2 eps_q of the allowed rows, and the filter pass would drop docs of the answer.  So the bitmap is applied where
-// gdr_sim_topk's GDR_SIM_LIVE_MASK applies it — sim_live_mask_kernel over the sample block before the threshold, over the survivors
-// behind the filter pass, sim_live_thr_fixup_kernel where fewer than k allowed sample rows leave no threshold — and the tail below
-// runs unchanged: radix_kth_key ignores -inf scores, the band gather skips id < 0, so a masked entry is padding to it.
+// gdr_sim_topk's GDR_SIM_LIVE_MASK applies it, by the same code: run_candidate_passes, which both entry points call (the mask over the
+// sample block before the threshold and over the survivors behind the filter pass, the fix-up where fewer than k allowed sample rows
+// leave no threshold) — and the tail below runs unchanged: radix_kth_key ignores -inf scores, the band gather skips id < 0, so a
+// masked entry is padding to it.
 __global__ __launch_bounds__(256) void sim_qprep_kernel(const float* __restrict__ Q, int d, float dnorm_max, __bf16* __restrict__ Q16,
                                                         float* __restrict__ eps2) {
   __shared__ float red[4];
@@ -985,12 +1066,7 @@ __global__ __launch_bounds__(256) void sim_qprep_kernel(const float* __restrict_
   for (int c = threadIdx.x * 4; c < d; c += 1024) {
     const float4 v = *reinterpret_cast<const float4*>(row + c);
     ss = fmaf(v.x, v.x, fmaf(v.y, v.y, fmaf(v.z, v.z, fmaf(v.w, v.w, ss))));
-    union {
-      __bf16 h[4];
-      uint2 u;
-    } o;
-    o.h[0] = (__bf16)v.x, o.h[1] = (__bf16)v.y, o.h[2] = (__bf16)v.z, o.h[3] = (__bf16)v.w;
-    *reinterpret_cast<uint2*>(Q16 + (int64_t)q * d + c) = o.u;
+    store_bf16x4(reinterpret_cast<uint2*>(Q16 + (int64_t)q * d + c), v);
   }
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) ss += __shfl_xor(ss, off);
@@ -1008,15 +1084,7 @@ __global__ __launch_bounds__(256) void row_norm2_max_kernel(const float* __restr
   const int lane = threadIdx.x & 63;
   float best = 0.f;
   for (int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); r < N; r += (int64_t)gridDim.x * 4) {
-    const float* row = D + r * d;
-    float ss = 0.f;
-    for (int c = lane * 4; c < d; c += 256) {
-      const float4 v = *reinterpret_cast<const float4*>(row + c);
-      ss = fmaf(v.x, v.x, fmaf(v.y, v.y, fmaf(v.z, v.z, fmaf(v.w, v.w, ss))));
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) ss += __shfl_xor(ss, off);
-    best = fmaxf(best, ss);
+    best = fmaxf(best, wave_row_norm2(D + r * d, d, lane, [](int, const float4&) {}));
   }
   if (lane == 0) atomicMax(out, __float_as_uint(best));
 }
@@ -1209,20 +1277,7 @@ extern "C" size_t gdr_sim_topk_prefilter_workspace_bytes(int B, int64_t N, int d
     const auto it = memo.find(key);
     if (it != memo.end()) return it->second;
   }
-  size_t own = gdr::make_prefilter_plan(B, N, d, k).total;
-  double target = sqrt((double)k * (double)N);
-  if (target < k) target = k;
-  const int64_t ts_k = (int64_t)((target + gdr::TILE - 1) / gdr::TILE);
-  for (int64_t ts = 1; ts <= ts_k; ++ts) {
-    const double edge = (double)(ts * gdr::TILE);
-    const int64_t ends[2] = {(int64_t)(edge * edge / (double)N), ts * gdr::TILE};
-    for (const int64_t e : ends)
-      for (int64_t kk = e - 1; kk <= e + 1; ++kk)
-        if (kk >= 1 && kk < k) {
-          const size_t t = gdr::make_prefilter_plan(B, N, d, (int)kk).total;
-          if (t > own) own = t;
-        }
-  }
+  const size_t own = gdr::largest_plan_up_to(N, k, [&](int kk) { return gdr::make_prefilter_plan(B, N, d, kk).total; });
   const size_t plain = gdr_sim_topk_workspace_bytes(B, N, d, k, 0) + gdr::align_up((size_t)B * d * 2, 256) + gdr::align_up((size_t)B * 4, 256);
   const size_t best = own > plain ? own : plain;
   std::lock_guard<std::mutex> lock(mu);
@@ -1253,59 +1308,26 @@ static int prefilter_impl(const float* Q, int B, const float* D, const void* D_b
                           int32_t idx_offset, float* out_val, int32_t* out_idx, int32_t* status, int flags, void* workspace,
                           size_t workspace_bytes, hipStream_t stream) {
   if (B == 0) return GDR_OK;
-  GDR_CHECK_ARG(Q && D && D_bf16 && out_val && out_idx && workspace, "sim_topk_prefilter: null pointer");
-  GDR_CHECK_ARG(B > 0 && N > 0 && d > 0 && d % 8 == 0 && d <= 1024, "sim_topk_prefilter: bad shape B=%d N=%lld d=%d (d %% 8 == 0, d <= 1024)", B,
-                (long long)N, d);
-  GDR_CHECK_ARG(k >= 1 && k <= PREFILTER_MAX_K && k <= N, "sim_topk_prefilter: k=%d must be in [1, min(1024, N)]", k);
-  GDR_CHECK_ARG(N < 0x7fffffffLL - 256, "sim_topk_prefilter: shard too large for int32 doc ids");
-  GDR_CHECK_ARG((int64_t)idx_offset + N <= 0x7fffffffLL,
-                "sim_topk_prefilter: idx_offset=%d + N=%lld leaves int32 doc ids (the largest id, idx_offset + N - 1, must be < 2^31 - 1)",
-                (int)idx_offset, (long long)N);
-  GDR_CHECK_ARG(dnorm_max > 0.f && dnorm_max < INFINITY, "sim_topk_prefilter: dnorm_max must be the largest row norm of D (> 0, finite)");
-  GDR_CHECK_ARG(((uintptr_t)Q & 15) == 0 && ((uintptr_t)D & 15) == 0 && ((uintptr_t)D_bf16 & 15) == 0 && ((uintptr_t)workspace & 255) == 0,
-                "sim_topk_prefilter: Q, D, D_bf16 must be 16-byte and workspace 256-byte aligned");
-  const bool per_query = flags == GDR_SIM_QUERY_MASK, masked = flags != 0;
-  const size_t head = masked ? (per_query ? (size_t)B : 1) * live_mask_bytes(N) : 0;
-  const int64_t qstride = per_query ? (int64_t)(live_mask_bytes(N) / sizeof(uint32_t)) : 0;  // words between two queries' bitmaps
-  const PrefilterPlan pp = make_prefilter_plan(B, N, d, k, head);
+  GDR_TRY(check_search_args("sim_topk_prefilter", true, true, Q, B, D, D_bf16, dnorm_max, N, d, k, idx_offset, out_val, out_idx, workspace));
+  const MaskHead head = mask_head(flags, B, N);
+  const PrefilterPlan pp = make_prefilter_plan(B, N, d, k, head.bytes);
   const SimPlan& p = pp.p;
   // a masked call is held to the size its caller was told (the bitmaps + the unmasked answer, never below this k's own layout)
-  const size_t required = masked ? gdr_sim_topk_prefilter_masked_workspace_bytes(B, N, d, k, flags) : pp.total;
+  const size_t required = head.masked ? gdr_sim_topk_prefilter_masked_workspace_bytes(B, N, d, k, flags) : pp.total;
   if (workspace_bytes < required) {
     set_error("sim_topk_prefilter: workspace %zu < required %zu", workspace_bytes, required);
     return GDR_ENOSPC;
   }
   char* ws = static_cast<char*>(workspace);
-  const uint32_t* live = masked ? reinterpret_cast<const uint32_t*>(ws) : nullptr;
-  SimEpilogue ep{};
-  ep.cand_val = reinterpret_cast<float*>(ws + p.off_val);
-  ep.cand_idx = reinterpret_cast<int32_t*>(ws + p.off_idx);
-  ep.cand_cnt = reinterpret_cast<int32_t*>(ws + p.off_cnt);
-  float* thr = reinterpret_cast<float*>(ws + p.off_thr);
-  ep.thr = thr, ep.status = nullptr, ep.cap = (int32_t)p.cap, ep.tile_stride = p.stride, ep.mode = 1;
   __bf16* Q16 = reinterpret_cast<__bf16*>(ws + pp.off_q16);
   float* eps2 = reinterpret_cast<float*>(ws + pp.off_eps);
   hipLaunchKernelGGL(sim_qprep_kernel, dim3(B), dim3(256), 0, stream, Q, d, dnorm_max, Q16, eps2);
   GDR_CHECK_LAUNCH("sim_qprep_kernel");
-  const bool stream_mode = sim_stream_supported(B, d, true);  // B <= 32: the HBM-bound stream over the bf16 image
-  int rc = stream_mode ? launch_sim_stream(D_bf16, N, Q16, B, d, ep, true, stream) : launch_sim_gemm(D_bf16, N, Q16, B, d, ep, true, stream);
-  if (rc) return rc;
-  if (masked) GDR_TRY(launch_live_mask(ep, p, B, 0, p.n_slots, live, qstride, N, stream));  // the threshold sees allowed sample scores only
-  // L - 2 eps: the filter pass keeps a superset of the band around the (yet unknown) k-th largest bf16 score
-  hipLaunchKernelGGL(sim_threshold_kernel, dim3(B), dim3(1024), 0, stream, ep.cand_val, p.cap, (int)p.n_slots, k, thr, ep.cand_cnt,
-                     (const float*)eps2);
-  GDR_CHECK_LAUNCH("sim_threshold_kernel");
-  if (p.stride > 1) {
-    if (masked) {  // fewer than k allowed sample rows (per query: of query q's bitmap): thr[q] = -inf (sim_live_thr_fixup_kernel)
-      hipLaunchKernelGGL(sim_live_thr_fixup_kernel, dim3(per_query ? B : 1), dim3(256), 0, stream, live, qstride, N, p.n_sample_tiles,
-                         p.stride, k, thr, B);
-      GDR_CHECK_LAUNCH("sim_live_thr_fixup_kernel");
-    }
-    ep.mode = 2;
-    rc = stream_mode ? launch_sim_stream(D_bf16, N, Q16, B, d, ep, true, stream) : launch_sim_gemm(D_bf16, N, Q16, B, d, ep, true, stream);
-    if (rc) return rc;
-    if (masked) GDR_TRY(launch_live_mask(ep, p, B, p.n_slots, -1, live, qstride, N, stream));  // the survivors, disallowed rows among them
-  }
+  // the passes over the bf16 image (B <= 32: the HBM-bound stream), the threshold lowered to L - 2 eps: the filter pass keeps a superset
+  // of the band around the (yet unknown) k-th largest bf16 score
+  SimEpilogue ep;
+  float* thr;
+  GDR_TRY(run_candidate_passes(D_bf16, Q16, true, sim_stream_supported(B, d, true), B, N, d, p, head, ws, k, eps2, 0, nullptr, stream, ep, thr));
   // the tail in one launch: k-th largest bf16-operand score, the band around it, fp32 scores of the band, exact select
   const int cap2p = sel_pow2(pp.cap2, 1024);
   if (int rc__ = ensure_dyn_lds(reinterpret_cast<const void*>(prefilter_tail_kernel<16>), cap2p * 8, "sim_topk_prefilter")) return rc__;
@@ -1316,8 +1338,8 @@ static int prefilter_impl(const float* Q, int B, const float* D, const void* D_b
   return GDR_OK;
 }
 
-// One wave per listed row: the row's bf16 image (the bits cast_f32_bf16_kernel gives) and its squared norm in row_norm2_max_kernel's
-// order (the same fmaf chain per lane, the same shuffle tree), joined by atomicMax on the bits.  A row listed twice is written twice
+// One wave per listed row: the row's bf16 image (the bits cast_f32_bf16_kernel gives: store_bf16x4) and its squared norm in
+// row_norm2_max_kernel's order (wave_row_norm2, which both call), joined by atomicMax on the bits.  A row listed twice is written twice
 // with the same bits.  Plain vector stores only.
 __global__ __launch_bounds__(256) void prefilter_update_rows_kernel(const float* __restrict__ D, __bf16* __restrict__ D16, int d,
                                                                     const int32_t* __restrict__ rows, int64_t n_rows,
@@ -1327,20 +1349,9 @@ __global__ __launch_bounds__(256) void prefilter_update_rows_kernel(const float*
   for (int64_t j = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); j < n_rows; j += (int64_t)gridDim.x * 4) {
     const int64_t r = rows[j];
     if (r < 0) continue;  // no row: the upper end is the caller's to keep (the call is not told N)
-    const float* row = D + r * d;
-    float ss = 0.f;
-    for (int c = lane * 4; c < d; c += 256) {
-      const float4 v = *reinterpret_cast<const float4*>(row + c);
-      ss = fmaf(v.x, v.x, fmaf(v.y, v.y, fmaf(v.z, v.z, fmaf(v.w, v.w, ss))));
-      union {
-        __bf16 h[4];
-        uint2 u;
-      } o;
-      o.h[0] = (__bf16)v.x, o.h[1] = (__bf16)v.y, o.h[2] = (__bf16)v.z, o.h[3] = (__bf16)v.w;
-      *reinterpret_cast<uint2*>(D16 + r * d + c) = o.u;
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) ss += __shfl_xor(ss, off);
+    const float ss = wave_row_norm2(D + r * d, d, lane, [=](int c, const float4& v) {
+      store_bf16x4(reinterpret_cast<uint2*>(D16 + r * d + c), v);
+    });
     best = fmaxf(best, ss);
   }
   if (lane == 0) atomicMax(out, __float_as_uint(best));
@@ -1358,7 +1369,7 @@ extern "C" size_t gdr_sim_topk_prefilter_masked_workspace_bytes(int B, int64_t N
   if (flags != GDR_SIM_LIVE_MASK && flags != GDR_SIM_QUERY_MASK) return 0;  // no such call: gdr_sim_topk_prefilter_masked refuses it
   const size_t own = gdr_sim_topk_prefilter_workspace_bytes(B, N, d, k);
   if (own == 0) return 0;
-  return (flags == GDR_SIM_QUERY_MASK ? (size_t)B : 1) * gdr::live_mask_bytes(N) + own;
+  return gdr::mask_head(flags, B, N).bytes + own;
 }
 
 extern "C" int gdr_sim_topk_prefilter_masked(const float* Q, int B, const float* D, const void* D_bf16, float dnorm_max, int64_t N, int d,
@@ -1397,15 +1408,8 @@ extern "C" int gdr_topk_merge(const float* vals, const int32_t* idx, int G, int 
   GDR_CHECK_ARG(vals && idx && out_val && out_idx, "topk_merge: null pointer");
   GDR_CHECK_ARG(G > 0 && B > 0 && k >= 1 && k <= SIM_TOPK_MAX_K && (int64_t)G * k <= 0x7fffffffLL,
                 "topk_merge: bad shape G=%d B=%d k=%d (k in [1, %d], G * k < 2^31)", G, B, k, SIM_TOPK_MAX_K);
-  if (k > SIM_ONE_WAVE_MAX_K)
-    return launch_select_deep<true>(vals, idx, nullptr, 0, G, B, k, 0, nullptr, out_val, out_idx, nullptr, k, 1,
-                                    "topk_select_kernel<merge, deep>", stream);
-  const int kpad = sel_pow2(k, 1);
-  hipLaunchKernelGGL(topk_select_kernel<true>, dim3(B), dim3(SEL_THREADS), kpad * sizeof(unsigned long long), stream,
-                     vals, idx, (const int32_t*)nullptr, (int64_t)0, G, B, k, kpad, 0, (const float*)nullptr, out_val, out_idx,
-                     (int32_t*)nullptr, k, 1);
-  GDR_CHECK_LAUNCH("topk_select_kernel<merge>");
-  return GDR_OK;
+  return launch_select<true>(vals, idx, nullptr, 0, G, B, k, 0, nullptr, out_val, out_idx, nullptr, k, 1, SEL_THREADS,
+                             "topk_select_kernel<merge>", "topk_select_kernel<merge, deep>", stream);
 }
 
 namespace gdr {
@@ -1451,13 +1455,6 @@ extern "C" int gdr_topk_merge_packed(const void* pairs, int G, int B, int k, flo
                 "topk_merge_packed: bad shape G=%d B=%d k=%d (k in [1, %d], G * k < 2^31)", G, B, k, SIM_TOPK_MAX_K);
   const float* vals = static_cast<const float*>(pairs);
   const int32_t* idx = static_cast<const int32_t*>(pairs) + 1;
-  if (k > SIM_ONE_WAVE_MAX_K)
-    return launch_select_deep<true>(vals, idx, nullptr, 0, G, B, k, 0, nullptr, out_val, out_idx, out_status, k + 1, 2,
-                                    "topk_select_kernel<merge packed, deep>", stream);
-  const int kpad = sel_pow2(k, 1);
-  hipLaunchKernelGGL(topk_select_kernel<true>, dim3(B), dim3(SEL_THREADS), kpad * sizeof(unsigned long long), stream,
-                     vals, idx, (const int32_t*)nullptr, (int64_t)0, G, B, k, kpad, 0, (const float*)nullptr, out_val, out_idx,
-                     out_status, k + 1, 2);
-  GDR_CHECK_LAUNCH("topk_select_kernel<merge packed>");
-  return GDR_OK;
+  return launch_select<true>(vals, idx, nullptr, 0, G, B, k, 0, nullptr, out_val, out_idx, out_status, k + 1, 2, SEL_THREADS,
+                             "topk_select_kernel<merge packed>", "topk_select_kernel<merge packed, deep>", stream);
 }

@@ -317,16 +317,15 @@ class QueryRows:
         return out
 
 
-def _sim_topk_raw(Q, D, k, idx_offset, workspace, flags, live=None, allowed=None):
-    B, d = Q.shape
-    N = D.shape[0]
+# the workspace layout of a masked call — one per call: with allowed=, live= is ANDed into the per-query bitmaps (_place_bitmaps)
+def _mask_flag(live, allowed):
+    return _ffi.SIM_QUERY_MASK if allowed is not None else _ffi.SIM_LIVE_MASK if live is not None else 0
+
+
+def _place_bitmaps(ws, B, live, allowed):
+    """Writes the head of a masked call's workspace (stream-ordered): allowed's B bitmaps in slots M bytes apart, live ANDed in — or the
+    one bitmap of live.  Nothing without either."""
     if allowed is not None:
-        flags |= _ffi.SIM_QUERY_MASK                                 # one layout per call: live is ANDed in below
-    elif live is not None:
-        flags |= _ffi.SIM_LIVE_MASK
-    need = lib().gdr_sim_topk_workspace_bytes(B, N, d, k, flags)
-    ws = (workspace or Workspace(Q.device)).get(need)
-    if allowed is not None:                                          # B bitmaps, M bytes apart, are the head of the workspace
         words = allowed.words
         M = (4 * words.shape[1] + 255) // 256 * 256
         slots = ws[:B * M].view(torch.int32).view(B, M // 4)[:, :words.shape[1]]   # the padding up to M is ignored: left as it is
@@ -334,12 +333,25 @@ def _sim_topk_raw(Q, D, k, idx_offset, workspace, flags, live=None, allowed=None
             torch.bitwise_and(words, live.words, out=slots)
         else:
             slots.copy_(words)
-    elif live is not None:                                           # the bitmap is the head of the workspace (stream-ordered copy)
+    elif live is not None:
         words = live.words
         ws[:words.numel() * 4].view(torch.int32).copy_(words)
-    vals = torch.empty((B, k), dtype=torch.float32, device=Q.device)
-    idx = torch.empty((B, k), dtype=torch.int32, device=Q.device)
-    status = torch.empty((B,), dtype=torch.int32, device=Q.device)
+
+
+# (values fp32 [B, k], indices int32 [B, k], status int32 [B]), uninitialised: what every top-k entry point fills
+def _topk_out(B, k, device):
+    return (torch.empty((B, k), dtype=torch.float32, device=device), torch.empty((B, k), dtype=torch.int32, device=device),
+            torch.empty((B,), dtype=torch.int32, device=device))
+
+
+def _sim_topk_raw(Q, D, k, idx_offset, workspace, flags, live=None, allowed=None):
+    B, d = Q.shape
+    N = D.shape[0]
+    flags |= _mask_flag(live, allowed)
+    need = lib().gdr_sim_topk_workspace_bytes(B, N, d, k, flags)
+    ws = (workspace or Workspace(Q.device)).get(need)
+    _place_bitmaps(ws, B, live, allowed)
+    vals, idx, status = _topk_out(B, k, Q.device)
     fn = lib().gdr_sim_topk_bf16 if Q.dtype == torch.bfloat16 else lib().gdr_sim_topk
     check(fn(ptr(Q), B, ptr(D), N, d, k, idx_offset, ptr(vals), ptr(idx), ptr(status), flags, ptr(ws), ws.numel(),
              stream_ptr()), "gdr_sim_topk")
@@ -389,6 +401,44 @@ def _sim_topk_exact(Q, D, k, idx_offset, status, vals, idx, flags, live, allowed
     return status
 
 
+# sim_topk's three routes.  Each makes its library calls and returns (vals, idx, status); P is the PrefilteredCorpus where sim_topk chose
+# the pre-filter (prefilter_route), else None.
+# The dense call over every row — the one place that chooses between the (masked) pre-filter over P and the plain entry point:
+def _sim_topk_dense(Q, D, P, k, idx_offset, workspace, flags, live, allowed):
+    if P is not None:
+        return _sim_topk_prefilter_raw(Q, P, k, idx_offset, workspace, live, allowed)
+    return _sim_topk_raw(Q, D, k, idx_offset, workspace, flags, live, allowed)
+
+
+# every query through the gather mode at a capacity of `chunks` chunks, no read-back:
+def _sim_topk_gather(Q, D, k, idx_offset, workspace, flags, live, allowed, chunks):
+    gflags = (flags & _ffi.SIM_NO_STREAM) | _ffi.SIM_ROW_GATHER | _ffi.sim_gather_chunks(chunks)
+    return _sim_topk_raw(Q, D, k, idx_offset, workspace, gflags, live, allowed)
+
+
+def _sim_topk_auto(Q, D, P, k, idx_offset, workspace, flags, live, allowed):
+    """gather="auto": reads the counts back (the one extra sync), sends the narrow queries to ONE gather call and the wide rest to the
+    dense call, whose overflows it re-runs here — the result is exact as returned, status all 0.  None when no query is narrow: the
+    dense route serves the batch, as without gather=."""
+    eff = allowed if live is None else allowed.rows(torch.arange(allowed.B, device=allowed.device)).and_(live)   # a copy: the caller's stays
+    narrow, chunks = gather_route(eff.counts().tolist(), k, GATHER_MAX_ROWS)     # the one extra sync
+    if not narrow:
+        return None
+    B = Q.shape[0]
+    if len(narrow) == B:
+        return _sim_topk_gather(Q, D, k, idx_offset, workspace, flags, None, eff, chunks)   # the capacity holds every count: status is 0
+    wide = sorted(set(range(B)) - set(narrow))
+    nt, wt = (torch.tensor(x, dtype=torch.int64, device=Q.device) for x in (narrow, wide))
+    vals, idx, status = _topk_out(B, k, Q.device)
+    status.zero_()
+    vals[nt], idx[nt], _ = _sim_topk_gather(Q[nt].contiguous(), D, k, idx_offset, workspace, flags, None, eff.rows(nt), chunks)
+    Qw, aw = Q[wt].contiguous(), eff.rows(wt)
+    v2, i2, s2 = _sim_topk_dense(Qw, D, P, k, idx_offset, workspace, flags, None, aw)   # masks=True: the wide remainder through the bf16 pre-filter
+    _sim_topk_exact(Qw, D, k, idx_offset, s2, v2, i2, flags, None, aw)
+    vals[wt], idx[wt] = v2, i2
+    return vals, idx, status
+
+
 def sim_topk(Q, D, k, idx_offset=0, workspace=None, return_status=False, exact_on_overflow=True, flags=0, live=None, allowed=None,
              gather=None):
     """Fused Q·Dᵀ + per-row top-k — gdr_sim_topk.  Returns (values fp32[B,k], indices int32[B,k]), 1 <= k <= min(SIM_TOPK_MAX_K, N).
@@ -421,10 +471,11 @@ def sim_topk(Q, D, k, idx_offset=0, workspace=None, return_status=False, exact_o
                     rest to the dense masked call as before; an all-narrow batch launches no dense pass.
     DenseModel.search and GDRRetriever.search pass "auto" by default; here the default is None, so that a direct caller's lists stay
     bit for bit the dense call's (the gather pass sums a row in another order than the GEMM core)."""
-    prefilter = isinstance(D, PrefilteredCorpus)
-    if prefilter:
+    P = None
+    if isinstance(D, PrefilteredCorpus):
         P, D = D, D.D
-        prefilter = prefilter_route(Q.shape[0], D.shape[1], k, flags, P.dnorm_max, live is not None or allowed is not None, P.masks)
+        if not prefilter_route(Q.shape[0], D.shape[1], k, flags, P.dnorm_max, live is not None or allowed is not None, P.masks):
+            P = None
     _need_cuda(Q, D)
     if D.dtype == torch.bfloat16:                                    # bf16 corpus: queries are cast on the device
         Q = (Q if Q.dtype == torch.bfloat16 else to_bf16(Q)).contiguous()
@@ -449,41 +500,16 @@ def sim_topk(Q, D, k, idx_offset=0, workspace=None, return_status=False, exact_o
         raise _ffi.GdrError("sim_topk: gather= ranks the rows a QueryRows allows: it needs allowed= and no SIM_EXHAUSTIVE flag")
     elif gather is True or not (gather == "auto" or (isinstance(gather, int) and 1 <= gather <= GATHER_CHUNK_ROWS * GATHER_MAX_CHUNKS)):
         raise _ffi.GdrError(f'sim_topk: gather must be None, False, "auto" or a row capacity in [1, {GATHER_CHUNK_ROWS * GATHER_MAX_CHUNKS}], not {gather!r}')
-    if gather is not None:
-        gflags = (flags & _ffi.SIM_NO_STREAM) | _ffi.SIM_ROW_GATHER
-        if gather != "auto":                                         # every query through the gather mode, no read-back
-            vals, idx, status = _sim_topk_raw(Q, D, k, idx_offset, workspace, gflags | _ffi.sim_gather_chunks(gather_chunks(gather)), live, allowed)
-            if exact_on_overflow:
-                status = _sim_topk_exact(Q, D, k, idx_offset, status, vals, idx, flags, live, allowed)
-            return (vals, idx, status) if return_status else (vals, idx)
-        eff = allowed if live is None else allowed.rows(torch.arange(allowed.B, device=allowed.device)).and_(live)   # a copy: the caller's stays
-        narrow, chunks = gather_route(eff.counts().tolist(), k, GATHER_MAX_ROWS)     # the one extra sync
-        if narrow:
-            B = Q.shape[0]
-            if len(narrow) == B:
-                vals, idx, status = _sim_topk_raw(Q, D, k, idx_offset, workspace, gflags | _ffi.sim_gather_chunks(chunks), None, eff)
-                return (vals, idx, status) if return_status else (vals, idx)     # the capacity holds every count: status is 0
-            wide = sorted(set(range(B)) - set(narrow))
-            nt, wt = (torch.tensor(x, dtype=torch.int64, device=Q.device) for x in (narrow, wide))
-            vals = torch.empty((B, k), dtype=torch.float32, device=Q.device)
-            idx = torch.empty((B, k), dtype=torch.int32, device=Q.device)
-            status = torch.zeros((B,), dtype=torch.int32, device=Q.device)
-            vals[nt], idx[nt], _ = _sim_topk_raw(Q[nt].contiguous(), D, k, idx_offset, workspace, gflags | _ffi.sim_gather_chunks(chunks),
-                                                 None, eff.rows(nt))
-            Qw, aw = Q[wt].contiguous(), eff.rows(wt)
-            if prefilter:                                            # PrefilteredCorpus(masks=True): the wide remainder through the bf16 pre-filter
-                v2, i2, s2 = _sim_topk_prefilter_raw(Qw, P, k, idx_offset, workspace, None, aw)
-            else:
-                v2, i2, s2 = _sim_topk_raw(Qw, D, k, idx_offset, workspace, flags, None, aw)
-            _sim_topk_exact(Qw, D, k, idx_offset, s2, v2, i2, flags, None, aw)
-            vals[wt], idx[wt] = v2, i2
-            return (vals, idx, status) if return_status else (vals, idx)
-    if prefilter:
-        vals, idx, status = _sim_topk_prefilter_raw(Q, P, k, idx_offset, workspace, live, allowed)
+    out = _sim_topk_auto(Q, D, P, k, idx_offset, workspace, flags, live, allowed) if gather == "auto" else None
+    if out is not None:                                              # exact as it stands: its dense part re-ran its own overflows
+        vals, idx, status = out
     else:
-        vals, idx, status = _sim_topk_raw(Q, D, k, idx_offset, workspace, flags, live, allowed)
-    if exact_on_overflow:
-        status = _sim_topk_exact(Q, D, k, idx_offset, status, vals, idx, flags, live, allowed)
+        if gather is None or gather == "auto":                       # "auto" with no narrow query
+            vals, idx, status = _sim_topk_dense(Q, D, P, k, idx_offset, workspace, flags, live, allowed)
+        else:
+            vals, idx, status = _sim_topk_gather(Q, D, k, idx_offset, workspace, flags, live, allowed, gather_chunks(gather))
+        if exact_on_overflow:
+            status = _sim_topk_exact(Q, D, k, idx_offset, status, vals, idx, flags, live, allowed)
     return (vals, idx, status) if return_status else (vals, idx)
 
 
@@ -587,29 +613,17 @@ def prefilter_route(B, d, k, flags, dnorm_max, masked, masks):
 def _sim_topk_prefilter_raw(Q, P, k, idx_offset, workspace, live=None, allowed=None):
     B, d = Q.shape
     N = P.D.shape[0]
-    vals = torch.empty((B, k), dtype=torch.float32, device=Q.device)
-    idx = torch.empty((B, k), dtype=torch.int32, device=Q.device)
-    status = torch.empty((B,), dtype=torch.int32, device=Q.device)
-    if live is None and allowed is None:
+    vals, idx, status = _topk_out(B, k, Q.device)
+    flags = _mask_flag(live, allowed)
+    if not flags:
         need = lib().gdr_sim_topk_prefilter_workspace_bytes(B, N, d, k)
         ws = (workspace or Workspace(Q.device)).get(need)
         check(lib().gdr_sim_topk_prefilter(ptr(Q), B, ptr(P.D), ptr(P.D16), P.dnorm_max, N, d, k, idx_offset, ptr(vals), ptr(idx),
                                            ptr(status), ptr(ws), ws.numel(), stream_ptr()), "gdr_sim_topk_prefilter")
         return vals, idx, status
-    flags = _ffi.SIM_QUERY_MASK if allowed is not None else _ffi.SIM_LIVE_MASK   # one layout per call: live is ANDed in below
     need = lib().gdr_sim_topk_prefilter_masked_workspace_bytes(B, N, d, k, flags)
     ws = (workspace or Workspace(Q.device)).get(need)
-    if allowed is not None:                                          # B bitmaps, M bytes apart, are the head of the workspace
-        words = allowed.words
-        M = (4 * words.shape[1] + 255) // 256 * 256
-        slots = ws[:B * M].view(torch.int32).view(B, M // 4)[:, :words.shape[1]]   # the padding up to M is ignored: left as it is
-        if live is not None:
-            torch.bitwise_and(words, live.words, out=slots)
-        else:
-            slots.copy_(words)
-    else:                                                            # the bitmap is the head of the workspace (stream-ordered copy)
-        words = live.words
-        ws[:words.numel() * 4].view(torch.int32).copy_(words)
+    _place_bitmaps(ws, B, live, allowed)
     check(lib().gdr_sim_topk_prefilter_masked(ptr(Q), B, ptr(P.D), ptr(P.D16), P.dnorm_max, N, d, k, idx_offset, ptr(vals), ptr(idx),
                                               ptr(status), flags, ptr(ws), ws.numel(), stream_ptr()), "gdr_sim_topk_prefilter_masked")
     return vals, idx, status

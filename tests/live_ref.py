@@ -11,6 +11,22 @@ def pack(live):
     return (bits.reshape(-1, 32) << np.arange(32, dtype=np.uint32)).sum(1, dtype=np.uint64).astype(np.uint32).view(np.int32)
 
 
+def mask_bytes(N):
+    """Bytes of one row bitmap at the head of a masked call's workspace (csrc/sim_topk.hip live_mask_bytes): its words, up to 256."""
+    return (4 * ((N + 31) // 32) + 255) // 256 * 256
+
+
+class FixedWorkspace:
+    """An ops.Workspace stand-in that hands out one buffer of a fixed size: what a captured graph needs (no allocation on replay)."""
+
+    def __init__(self, buf):
+        self.buf = buf
+
+    def get(self, nbytes):
+        assert nbytes <= self.buf.numel()
+        return self.buf
+
+
 def scores(Q, D):
     """fp64 scores [B, N] of the operands as given (a bf16 corpus is passed in already rounded)."""
     return np.asarray(Q, np.float64) @ np.asarray(D, np.float64).T

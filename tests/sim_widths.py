@@ -106,26 +106,31 @@ def expected(d, N, k):
     return torch.from_numpy(v.astype(np.float32)), torch.from_numpy(i.astype(np.int32))
 
 
-def plan(N, k):
+def plan(N, k, exhaustive=False, survivors=1.0):
     """What one gdr_sim_topk call of depth k lays out (include/gdr_hip.h at gdr_sim_topk_workspace_bytes; csrc/sim_topk.hip make_plan):
     (sample stride in tiles of 128 rows, sample slots, list capacity per query).  A corpus of at most 16 384 rows, or of fewer than four
-    sample blocks, is its own sample (stride 1).  Otherwise about sqrt(k N) rows are sampled, and the list holds the sample block,
-    4 x the k N / n_sample survivors expected, and 4096.  N = 20 001, k = 10: (39, 640, 6016)."""
+    sample blocks, or a SIM_EXHAUSTIVE call, is its own sample (stride 1).  Otherwise about sqrt(k N) rows are sampled, and the list holds
+    the sample block, 4 x the k N / n_sample survivors expected (x `survivors`: the pre-filter's wider cut), and 4096.
+    N = 20 001, k = 10: (39, 640, 6016).  The one restatement of the rule in the tests: the search suites import it."""
     tiles = -(-N // TILE)
-    ts = max(1, int((max(math.sqrt(k * N), k) + TILE - 1) / TILE))
-    if N <= 16384 or tiles < 4 * ts:
+    ts = max(1, int((max(math.sqrt(float(k) * float(N)), float(k)) + TILE - 1) / TILE))
+    if exhaustive or N <= 16384 or tiles < 4 * ts:
         n = tiles * TILE
         return 1, n, n
     stride = tiles // ts
     slots = -(-tiles // stride) * TILE
-    cap = slots + int(4.0 * k * N / slots) + 4096
+    cap = slots + int(4.0 * (float(k) * float(N) / float(slots)) * survivors) + 4096
     return stride, slots, -(-cap // TILE) * TILE
+
+
+def in_sample_tile(N, stride):
+    """bool [N]: row r sits in a sample tile (tile index % stride == 0)"""
+    return (np.arange(N) // TILE) % stride == 0
 
 
 def sample_rows(N, stride):
     """the rows of the tiles t with t % stride == 0"""
-    r = np.arange(N)
-    return r[(r // TILE) % stride == 0]
+    return np.nonzero(in_sample_tile(N, stride))[0]
 
 
 def survivors(s, N, k):

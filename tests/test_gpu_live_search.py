@@ -8,7 +8,6 @@ form sim_topk_impl has, against two oracles —
       kernels, whose sample pass adds a row's dot product in another order than their filter pass —
 then the case the sample cannot serve (fewer than k live sample rows), fewer than k live rows in all, the memory contract of the
 mode (tests/abi_guard.py), determinism, GDRRetriever.search through the document lifecycle, and graph capture."""
-import math
 import types
 
 import numpy as np
@@ -18,6 +17,7 @@ import torch
 import expand_ref
 import lifecycle_ref
 import live_ref
+import sim_widths
 from abi_guard import guarded, guarded_input, poisoned_workspace
 from conftest import order_insensitive_topk_match
 from gdr_amd import _ffi, codec, ops, synth
@@ -27,7 +27,6 @@ pytestmark = pytest.mark.gpu
 
 TOL = 1e-4                         # oracle/parity_rules.py: |got - ref| <= 1e-4 + 1e-4 |ref|, ids exact beyond twice that
 LIVE, EXH, NOSTREAM = _ffi.SIM_LIVE_MASK, _ffi.SIM_EXHAUSTIVE, _ffi.SIM_NO_STREAM
-TILE = 128
 
 # form -> (B, N, d, k, flags, bf16).  d = 64: the tiled GEMM core at every B (the stream kernels need d % 128 == 0, bf16 d % 256 == 0)
 FORMS = {
@@ -38,7 +37,7 @@ FORMS = {
     "stream_sliced_B4": (4, 20_000, 128, 10, 0, False),             # latency mode: stream kernels, sliced threshold / select tails
     "no_stream_B4": (4, 20_000, 128, 10, NOSTREAM, False),          # the same shape forced onto the tiled core
     "ragged_B4": (4, 20_011, 64, 10, 0, False),
-    "deep_select_B4": (4, 20_000, 64, 1100, 0, False),              # k > 1024: launch_select_deep
+    "deep_select_B4": (4, 20_000, 64, 1100, 0, False),              # k > 1024: the deep form of launch_select
     "bf16_B40": (40, 20_000, 64, 10, 0, True),
     "bf16_stream_B4": (4, 20_000, 256, 10, 0, True),
     "exhaustive_B4": (4, 20_000, 64, 10, EXH, False),
@@ -58,17 +57,6 @@ def dev():
     assert torch.cuda.is_available()
     torch.set_grad_enabled(False)
     return torch.device("cuda:0")
-
-
-def _stride(N, k, exhaustive=False):
-    """make_plan's sample stride (csrc/sim_topk.hip): sample tiles are the 128-row tiles with index % stride == 0."""
-    tiles = -(-N // TILE)
-    ts = max(1, int((max(math.sqrt(k * N), k) + TILE - 1) // TILE))
-    return 1 if exhaustive or N <= 16384 or tiles < 4 * ts else tiles // ts
-
-
-def _in_sample_tile(N, stride):
-    return (np.arange(N) // TILE) % stride == 0
 
 
 _DATA = {}
@@ -92,7 +80,7 @@ def _data(form, dev):
         v0, i0, st0 = _raw(Qd, Dd, k, flags)
         assert int(st0.abs().sum()) == 0
         _DATA[form] = types.SimpleNamespace(form=form, B=B, N=N, d=d, k=k, flags=flags, bf16=bf16, S=S, Qd=Qd, Dd=Dd, v0=v0, i0=i0,
-                                            stride=_stride(N, k, bool(flags & EXH)))
+                                            stride=sim_widths.plan(N, k, bool(flags & EXH))[0])
     return _DATA[form]
 
 
@@ -141,7 +129,7 @@ def _check(s, live, v, i, what):
 def _mask(s, name):
     rng = np.random.default_rng(len(name) + s.N)
     live = np.ones(s.N, bool)
-    inside = _in_sample_tile(s.N, s.stride)
+    inside = sim_widths.in_sample_tile(s.N, s.stride)
     top = np.unique(s.i0.cpu().numpy())
     if name == "topk_union":
         live[top] = False
@@ -186,7 +174,7 @@ def test_fewer_than_k_live_sample_rows(dev, form):
     SIM_EXHAUSTIVE | SIM_LIVE_MASK and is exact."""
     s = _data(form, dev)
     assert s.stride == 39 and s.k == 10
-    inside = _in_sample_tile(s.N, s.stride)
+    inside = sim_widths.in_sample_tile(s.N, s.stride)
     live = ~inside
     best_inside = np.argsort(-np.where(inside, s.S[0], -np.inf))[:5]          # the five are query 0's best sample rows
     live[best_inside] = True
@@ -305,15 +293,6 @@ def test_two_runs_are_bit_identical(dev, form):
     assert all(torch.equal(x, y) for x, y in zip(a, b))
 
 
-class _FixedWorkspace:
-    def __init__(self, buf):
-        self.buf = buf
-
-    def get(self, nbytes):
-        assert nbytes <= self.buf.numel()
-        return self.buf
-
-
 @pytest.mark.parametrize("form", ["sampled_B40", "stream_sliced_B4"])
 def test_masked_call_in_a_captured_graph(dev, form):
     """One masked call captured in a graph — the copy of the bitmap into the workspace, the passes, the three mask launches —
@@ -322,7 +301,7 @@ def test_masked_call_in_a_captured_graph(dev, form):
     live = _mask(s, "topk_union")
     L = ops.LiveRows.from_bool(torch.from_numpy(live).to(dev))
     need = lib().gdr_sim_topk_workspace_bytes(s.B, s.N, s.d, s.k, s.flags | LIVE)
-    ws = _FixedWorkspace(torch.empty(need, dtype=torch.uint8, device=dev))
+    ws = live_ref.FixedWorkspace(torch.empty(need, dtype=torch.uint8, device=dev))
     call = lambda: ops.sim_topk(s.Qd, s.Dd, s.k, workspace=ws, flags=s.flags, live=L, exact_on_overflow=False, return_status=True)   # noqa: E731
     warm = torch.cuda.Stream(device=dev)
     warm.wait_stream(torch.cuda.current_stream())

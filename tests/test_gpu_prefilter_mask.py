@@ -23,10 +23,12 @@ from abi_guard import guarded, guarded_input, poisoned_workspace
 from conftest import order_insensitive_topk_match
 from gdr_amd import _ffi, codec, ops, synth
 from gdr_amd._ffi import lib, ptr, stream_ptr
+from live_ref import mask_bytes
+from sim_widths import in_sample_tile, plan
 
 TOL = 1e-4                         # oracle/parity_rules.py: |got - ref| <= 1e-4 + 1e-4 |ref|, ids exact beyond twice that
 LIVE, QM = _ffi.SIM_LIVE_MASK, _ffi.SIM_QUERY_MASK
-TILE, CNT_STRIDE = 128, 32
+CNT_STRIDE = 32
 
 # name -> (B, N, d, k).  d = 64: the tiled bf16 GEMM core at every B; d = 256 at B <= 32: the bf16 stream kernels
 SHAPES = {
@@ -49,23 +51,9 @@ def _up(n, a=256):
     return -(-n // a) * a
 
 
-def mask_bytes(N):
-    return _up(4 * ((N + 31) // 32))
-
-
 def make_plan(B, N, k, survivors=1.0):
-    """make_plan(B, N, k, exhaustive = false, survivors): sample stride, sample slots, list capacity, bytes."""
-    tiles = -(-N // TILE)
-    target = max(math.sqrt(float(k) * float(N)), float(k))
-    ts = max(1, int((target + TILE - 1) / TILE))
-    stride = 1 if N <= 16384 or tiles < 4 * ts else tiles // ts
-    n_sample_tiles = -(-tiles // stride)
-    n_slots = n_sample_tiles * TILE
-    if stride == 1:
-        cap = n_slots
-    else:
-        expect = float(k) * float(N) / float(n_slots)
-        cap = _up(n_slots + int(4.0 * expect * survivors) + 4096, TILE)
+    """make_plan(B, N, k, exhaustive = false, survivors): sample stride, sample slots, list capacity (sim_widths.plan), bytes."""
+    stride, n_slots, cap = plan(N, k, survivors=survivors)
     total = 2 * _up(B * cap * 4) + _up(B * CNT_STRIDE * 4) + _up(B * 4) + (_up(B * 16 * 128 * 8) if B <= 32 else 0)
     return types.SimpleNamespace(stride=stride, n_slots=n_slots, cap=cap, total=total)
 
@@ -104,10 +92,6 @@ def eps2(Q, dnorm_max, d):
     """sim_qprep_kernel's 2 eps_q per query (float64 here; the kernel's fp32 rounding is inside occupancy()'s slack)."""
     nq = np.linalg.norm(np.asarray(Q, np.float64), axis=1) * 1.0001
     return 2.0 * nq * float(dnorm_max) * (2.0 ** -7 + 2.0 ** -16 + d * 2.0 ** -22) * 1.01
-
-
-def in_sample_tile(N, stride):
-    return (np.arange(N) // TILE) % stride == 0
 
 
 def occupancy(S16, allowed, Q, dnorm_max, d, k):

@@ -67,10 +67,6 @@ def dev():
     return torch.device("cuda:0")
 
 
-def _mask_bytes(N):
-    return (4 * ((N + 31) // 32) + 255) // 256 * 256
-
-
 _HOST, _DATA = {}, {}
 
 
@@ -147,7 +143,7 @@ def _flags(c):
 
 
 def _fill_bitmaps(ws, allowed, N):
-    B, M, W = allowed.shape[0], _mask_bytes(N), (N + 31) // 32
+    B, M, W = allowed.shape[0], live_ref.mask_bytes(N), (N + 31) // 32
     words = torch.from_numpy(np.stack([live_ref.pack(a) for a in allowed])).to(ws.device)
     ws[:B * M].view(torch.int32).view(B, M // 4)[:, :W].copy_(words)
 
@@ -161,7 +157,7 @@ def _raw(Qd, Dd, k, allowed, c=None, idx_offset=0, flags=None, status=True):
         flags = _flags(c)
     need = lib().gdr_sim_topk_workspace_bytes(B, N, d, k, flags)
     if flags & RG:      # fails without the feature (the bits were ignored: the dense plan, which moves with N)
-        assert need - B * _mask_bytes(N) == lib().gdr_sim_topk_workspace_bytes(B, N + 40_960, d, k, flags) - B * _mask_bytes(N + 40_960) > 0, \
+        assert need - B * live_ref.mask_bytes(N) == lib().gdr_sim_topk_workspace_bytes(B, N + 40_960, d, k, flags) - B * live_ref.mask_bytes(N + 40_960) > 0, \
             "the gather layout behind the bitmaps does not depend on N"
     ws = torch.empty(need, dtype=torch.uint8, device=Qd.device)
     _fill_bitmaps(ws, allowed, N)
@@ -313,7 +309,7 @@ def test_memory_contract_of_the_mode(dev, form, c):
     s = _data(form, dev)
     cap = gather_ref.cap_of(c)
     a = _allowed(s, ("two_percent", "cap_plus_1", "ties", "row_last"), cap)
-    M, W = _mask_bytes(s.N), (s.N + 31) // 32
+    M, W = live_ref.mask_bytes(s.N), (s.N + 31) // 32
     need = lib().gdr_sim_topk_workspace_bytes(s.B, s.N, s.d, s.k, _flags(c))
     assert need >= s.B * M + 8 * s.B * cap
     words = np.stack([live_ref.pack(r) for r in a])
@@ -361,15 +357,6 @@ def test_memory_contract_of_the_mode(dev, form, c):
     assert all(torch.equal(x, y) for x, y in zip(plain, runs[0]))
 
 
-class _FixedWorkspace:
-    def __init__(self, buf):
-        self.buf = buf
-
-    def get(self, nbytes):
-        assert nbytes <= self.buf.numel()
-        return self.buf
-
-
 def test_gather_call_in_a_captured_graph(dev):
     """ops.sim_topk(gather=8192, exact_on_overflow=False) returns a status and never synchronises: it is captured in a graph (a
     synchronisation would fail the capture), replayed, and replayed again after the QueryRows changed in place."""
@@ -377,7 +364,7 @@ def test_gather_call_in_a_captured_graph(dev):
     a = _allowed(s, [f for f in FILTERS if f != "fifty_percent"], 8192)
     R = ops.QueryRows.from_bool(torch.from_numpy(a).to(dev))
     need = lib().gdr_sim_topk_workspace_bytes(s.B, s.N, s.d, s.k, _flags(2))
-    ws = _FixedWorkspace(torch.empty(need, dtype=torch.uint8, device=dev))
+    ws = live_ref.FixedWorkspace(torch.empty(need, dtype=torch.uint8, device=dev))
     call = lambda: ops.sim_topk(s.Qd, s.Dd, s.k, workspace=ws, allowed=R, gather=8192, exact_on_overflow=False, return_status=True)   # noqa: E731
     warm = torch.cuda.Stream(device=dev)
     warm.wait_stream(torch.cuda.current_stream())

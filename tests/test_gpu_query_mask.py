@@ -12,7 +12,6 @@ GDR_SIM_QUERY_MASK in every form sim_topk_impl has, against two oracles —
       seed: there the rule's own treatment of the last tie group applies (values within the tolerance, ids counted) —
 then the memory contract of the mode (tests/abi_guard.py), determinism, graph capture, live= with allowed=, and
 GDRRetriever.search(allowed=) after remove_documents."""
-import math
 import types
 
 import numpy as np
@@ -21,6 +20,7 @@ import torch
 
 import lifecycle_ref
 import live_ref
+import sim_widths
 from abi_guard import guarded, guarded_input, poisoned_workspace
 from conftest import order_insensitive_topk_match
 from gdr_amd import _ffi, codec, ops, synth
@@ -30,7 +30,6 @@ pytestmark = pytest.mark.gpu
 
 TOL = 1e-4                         # oracle/parity_rules.py: |got - ref| <= 1e-4 + 1e-4 |ref|, ids exact beyond twice that
 LIVE, QM, EXH, NOSTREAM = _ffi.SIM_LIVE_MASK, 8, _ffi.SIM_EXHAUSTIVE, _ffi.SIM_NO_STREAM
-TILE = 128
 
 # form -> (B, N, d, k, flags, bf16).  The fp32 stream kernels serve B <= 32 at d % 128 == 0 (bf16: d % 256 == 0), their small sample
 # pass is the split-K one; everything else is the tiled GEMM core.  A sampled plan needs N > 16 384.
@@ -41,7 +40,7 @@ FORMS = {
     "tiled_ragged_B4": (4, 20_001, 64, 10, 0, False),
     "tiled_B40": (40, 20_000, 64, 10, 0, False),
     "tiled_ragged_B40": (40, 20_001, 128, 10, 0, False),
-    "deep_select_B4": (4, 40_000, 64, 1100, 0, False),              # k > 1024: launch_select_deep
+    "deep_select_B4": (4, 40_000, 64, 1100, 0, False),              # k > 1024: the deep form of launch_select
     "bf16_B40": (40, 20_000, 64, 10, 0, True),
     "bf16_stream_B4": (4, 20_001, 256, 10, 0, True),
     "exhaustive_B4": (4, 20_000, 64, 10, EXH, False),
@@ -57,17 +56,6 @@ def dev():
     assert torch.cuda.is_available()
     torch.set_grad_enabled(False)
     return torch.device("cuda:0")
-
-
-def _stride(N, k, exhaustive=False):
-    """make_plan's sample stride (csrc/sim_topk.hip): sample tiles are the 128-row tiles with index % stride == 0."""
-    tiles = -(-N // TILE)
-    ts = max(1, int((max(math.sqrt(k * N), k) + TILE - 1) // TILE))
-    return 1 if exhaustive or N <= 16384 or tiles < 4 * ts else tiles // ts
-
-
-def _mask_bytes(N):
-    return (4 * ((N + 31) // 32) + 255) // 256 * 256
 
 
 _HOST, _DATA = {}, {}
@@ -88,7 +76,7 @@ def _host(form):
             Qt, Dt = Qt.bfloat16(), Dt.bfloat16()
         S = live_ref.scores(Qt.double().numpy(), Dt.double().numpy())
         _HOST[form] = types.SimpleNamespace(form=form, B=B, N=N, d=d, k=k, flags=flags, bf16=bf16, S=S, Qt=Qt, Dt=Dt,
-                                            stride=_stride(N, k, bool(flags & EXH)))
+                                            stride=sim_widths.plan(N, k, bool(flags & EXH))[0])
     return _HOST[form]
 
 
@@ -115,7 +103,7 @@ def _raw(Qd, Dd, k, flags, live=None, allowed=None, idx_offset=0):
         words = torch.from_numpy(live_ref.pack(live)).to(Qd.device)
         ws[:words.numel() * 4].view(torch.int32).copy_(words)
     if allowed is not None:
-        M, W = _mask_bytes(N), (N + 31) // 32
+        M, W = live_ref.mask_bytes(N), (N + 31) // 32
         words = torch.from_numpy(np.stack([live_ref.pack(a) for a in allowed])).to(Qd.device)
         ws[:B * M].view(torch.int32).view(B, M // 4)[:, :W].copy_(words)
     v = torch.empty((B, k), dtype=torch.float32, device=Qd.device)
@@ -125,10 +113,6 @@ def _raw(Qd, Dd, k, flags, live=None, allowed=None, idx_offset=0):
     rc = fn(ptr(Qd), B, ptr(Dd), N, d, k, idx_offset, ptr(v), ptr(i), ptr(st), flags, ptr(ws), need, stream_ptr())
     assert rc == 0, lib().gdr_last_error().decode()
     return v, i, st
-
-
-def _in_sample_tile(N, stride):
-    return (np.arange(N) // TILE) % stride == 0
 
 
 def _allowed(s, name, top):
@@ -152,7 +136,7 @@ def _allowed(s, name, top):
         a[1, [0, 31, 32, 4000, 4777, s.N - 2, s.N - 1]] = True
         flagged = {1}                                                         # 7 < k allowed sample rows: thr = -inf, the list overflows
     elif name == "outside_sample_tiles":                                      # query 2 allows no row of a sample tile
-        a[2] = ~_in_sample_tile(s.N, s.stride) if s.stride > 1 else rng.random(s.N) < 0.5
+        a[2] = ~sim_widths.in_sample_tile(s.N, s.stride) if s.stride > 1 else rng.random(s.N) < 0.5
         flagged = {2}
     elif name == "two_percent":                                               # query 3 allows 2 % beside unrestricted ones
         a[:] = True
@@ -250,7 +234,7 @@ def test_memory_contract_of_the_mode(dev, form):
     i0 = s.i0.cpu().numpy()
     for q in range(s.B):
         a[q, i0[q]] = False
-    M, W = _mask_bytes(s.N), (s.N + 31) // 32
+    M, W = live_ref.mask_bytes(s.N), (s.N + 31) // 32
     flags = s.flags | QM
     need = lib().gdr_sim_topk_workspace_bytes(s.B, s.N, s.d, s.k, flags)
     assert need == lib().gdr_sim_topk_workspace_bytes(s.B, s.N, s.d, s.k, s.flags) + s.B * M
@@ -302,15 +286,6 @@ def test_two_runs_are_bit_identical(dev, form):
     assert all(torch.equal(p, q) for p, q in zip(x, y))
 
 
-class _FixedWorkspace:
-    def __init__(self, buf):
-        self.buf = buf
-
-    def get(self, nbytes):
-        assert nbytes <= self.buf.numel()
-        return self.buf
-
-
 def test_filtered_call_in_a_captured_graph(dev):
     """One filtered call captured in a graph — the strided copy of the bitmaps into the workspace, the passes, the mask launches
     and the per-query fix-up — replayed; then the QueryRows changes in place, and the replay follows it."""
@@ -318,7 +293,7 @@ def test_filtered_call_in_a_captured_graph(dev):
     a, _ = _allowed(s, "halves", None)
     R = ops.QueryRows.from_bool(torch.from_numpy(a).to(dev))
     need = lib().gdr_sim_topk_workspace_bytes(s.B, s.N, s.d, s.k, s.flags | QM)
-    ws = _FixedWorkspace(torch.empty(need, dtype=torch.uint8, device=dev))
+    ws = live_ref.FixedWorkspace(torch.empty(need, dtype=torch.uint8, device=dev))
     call = lambda: ops.sim_topk(s.Qd, s.Dd, s.k, workspace=ws, flags=s.flags, allowed=R, exact_on_overflow=False, return_status=True)   # noqa: E731
     warm = torch.cuda.Stream(device=dev)
     warm.wait_stream(torch.cuda.current_stream())

@@ -19,10 +19,6 @@ PLAIN = {
 }
 
 
-def _mask_bytes(N):
-    return (4 * ((N + 31) // 32) + 255) // 256 * 256
-
-
 def test_flag_value_and_pinned_abi():
     assert _ffi.SIM_LIVE_MASK == 4 and _ffi.SIM_LIVE_MASK & (_ffi.SIM_EXHAUSTIVE | _ffi.SIM_NO_STREAM) == 0
     assert _ffi.lib().gdr_abi_version() == 9 == _ffi.ABI_VERSION
@@ -42,7 +38,7 @@ def test_workspace_is_the_plain_size_plus_the_bitmap(B, N, k):
             for more in (0, _ffi.SIM_NO_STREAM):
                 plain = l.gdr_sim_topk_workspace_bytes(B, N, d, k, extra | more)
                 assert plain == want, "the unflagged size moved"
-                assert l.gdr_sim_topk_workspace_bytes(B, N, d, k, extra | more | _ffi.SIM_LIVE_MASK) - plain == _mask_bytes(N)
+                assert l.gdr_sim_topk_workspace_bytes(B, N, d, k, extra | more | _ffi.SIM_LIVE_MASK) - plain == live_ref.mask_bytes(N)
     assert l.gdr_sim_topk_workspace_bytes(0, N, 64, k, _ffi.SIM_LIVE_MASK) == 0
 
 

@@ -16,10 +16,6 @@ QM, RG = 8, 16
 SHAPES = [(8, 70_001, 10), (512, 320_000, 100), (4, 1000, 10)]
 
 
-def _mask_bytes(N):
-    return (4 * ((N + 31) // 32) + 255) // 256 * 256
-
-
 def test_flag_and_field_values():
     assert _ffi.SIM_ROW_GATHER == RG
     assert RG & (_ffi.SIM_EXHAUSTIVE | _ffi.SIM_NO_STREAM | _ffi.SIM_LIVE_MASK | _ffi.SIM_QUERY_MASK) == 0
@@ -39,12 +35,12 @@ def test_workspace_holds_the_bitmaps_and_the_lists_and_grows_with_the_capacity(B
     for c in (1, 2, 3, 256):
         f = QM | RG | _ffi.sim_gather_chunks(c)
         need = l.gdr_sim_topk_workspace_bytes(B, N, 64, k, f)
-        assert need >= B * _mask_bytes(N) + 8 * B * 4096 * c
+        assert need >= B * live_ref.mask_bytes(N) + 8 * B * 4096 * c
         assert need == l.gdr_sim_topk_workspace_bytes(B, N, 768, k, f), "the size depends on d"
         assert need == l.gdr_sim_topk_workspace_bytes(B, N, 64, k, f | _ffi.SIM_NO_STREAM)
         # the layout behind the bitmaps does not depend on N
         other = l.gdr_sim_topk_workspace_bytes(B, 2 * N, 64, k, f)
-        assert need - B * _mask_bytes(N) == other - B * _mask_bytes(2 * N)
+        assert need - B * live_ref.mask_bytes(N) == other - B * live_ref.mask_bytes(2 * N)
         sizes.append(need)
     assert sizes == sorted(set(sizes)), "strictly increasing in c"
     assert l.gdr_sim_topk_workspace_bytes(B, N, 64, k, QM | RG) == sizes[1], "a chunk field of 0 reads as 2"
@@ -60,8 +56,8 @@ def test_sizes_without_the_new_bits_are_what_they_were(B, N, k):
     for d in (64, 768):
         assert l.gdr_sim_topk_workspace_bytes(B, N, d, k, 0) == PLAIN[(B, N, k)][0]
         assert l.gdr_sim_topk_workspace_bytes(B, N, d, k, _ffi.SIM_EXHAUSTIVE) == PLAIN[(B, N, k)][1]
-        assert l.gdr_sim_topk_workspace_bytes(B, N, d, k, QM) == PLAIN[(B, N, k)][0] + B * _mask_bytes(N)
-        assert l.gdr_sim_topk_workspace_bytes(B, N, d, k, _ffi.SIM_LIVE_MASK) == PLAIN[(B, N, k)][0] + _mask_bytes(N)
+        assert l.gdr_sim_topk_workspace_bytes(B, N, d, k, QM) == PLAIN[(B, N, k)][0] + B * live_ref.mask_bytes(N)
+        assert l.gdr_sim_topk_workspace_bytes(B, N, d, k, _ffi.SIM_LIVE_MASK) == PLAIN[(B, N, k)][0] + live_ref.mask_bytes(N)
 
 
 EINVAL_CASES = [

@@ -21,10 +21,6 @@ PLAIN = {
 QM = 8
 
 
-def _mask_bytes(N):
-    return (4 * ((N + 31) // 32) + 255) // 256 * 256
-
-
 def test_flag_value_and_pinned_abi():
     assert _ffi.SIM_QUERY_MASK == QM
     assert _ffi.SIM_QUERY_MASK & (_ffi.SIM_EXHAUSTIVE | _ffi.SIM_NO_STREAM | _ffi.SIM_LIVE_MASK) == 0
@@ -43,9 +39,9 @@ def test_workspace_is_the_size_for_the_other_flags_plus_one_bitmap_per_query(B, 
         for f in (0, _ffi.SIM_EXHAUSTIVE, _ffi.SIM_NO_STREAM):
             plain = l.gdr_sim_topk_workspace_bytes(B, N, d, k, f)
             assert plain == PLAIN[(B, N, k)][1 if f == _ffi.SIM_EXHAUSTIVE else 0], "the unflagged size moved"
-            assert l.gdr_sim_topk_workspace_bytes(B, N, d, k, f | QM) - plain == B * _mask_bytes(N)
+            assert l.gdr_sim_topk_workspace_bytes(B, N, d, k, f | QM) - plain == B * live_ref.mask_bytes(N)
         # the live mask's own size is what it was
-        assert l.gdr_sim_topk_workspace_bytes(B, N, d, k, _ffi.SIM_LIVE_MASK) - PLAIN[(B, N, k)][0] == _mask_bytes(N)
+        assert l.gdr_sim_topk_workspace_bytes(B, N, d, k, _ffi.SIM_LIVE_MASK) - PLAIN[(B, N, k)][0] == live_ref.mask_bytes(N)
     assert l.gdr_sim_topk_workspace_bytes(0, N, 64, k, QM) == 0
 
 
@@ -59,7 +55,7 @@ def test_flagged_call_refuses_a_short_workspace_before_any_launch():
                 flags = QM | more
                 plain = l.gdr_sim_topk_workspace_bytes(B, N, 64, k, more)
                 need = l.gdr_sim_topk_workspace_bytes(B, N, 64, k, flags)
-                assert need == plain + B * _mask_bytes(N)
+                assert need == plain + B * live_ref.mask_bytes(N)
                 for nbytes in (plain, need - 1):
                     assert fn(p, B, p, N, 64, k, 0, p, p, None, flags, ws, nbytes, None) == _ffi.GDR_ENOSPC, (B, N, k, flags, nbytes)
                     msg = l.gdr_last_error()
