@@ -192,6 +192,17 @@ PREFILTER_MASK_SIGNATURES = {
     "gdr_prefilter_update_rows": (_i, [_vp, _vp, _i, _vp, _i64, _vp, _vp]),
 }
 
+# name -> (restype, argtypes); every symbol declared in include/gdr_hip_compact.h (which gdr_hip.h includes): compacting a live
+# corpus — the plan, the row mover, the id remap and the per-query row-bitmap remap.  A table of its own, as the header is.
+COMPACT_SIGNATURES = {
+    "gdr_rows_compact_plan_workspace_bytes": (_sz, [_i64]),
+    "gdr_rows_compact_plan": (_i, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "gdr_rows_compact_workspace_bytes": (_sz, [_i64, _i64]),
+    "gdr_rows_compact": (_i, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _sz, _vp]),
+    "gdr_ids_remap": (_i, [_vp, _i64, _vp, _vp, _i64, _vp, _vp]),
+    "gdr_rowmask_compact": (_i, [_vp, _i64, _i, _i64, _vp, _i64, _vp, _i64, _vp]),
+}
+
 _lib = None
 
 
@@ -211,7 +222,7 @@ def lib():
             # GDR_FFI_NO_TORCH: it never touches a GPU.)
             import torch  # noqa: F401
         l = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(PREFILTER_MASK_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(PREFILTER_MASK_SIGNATURES.items()) + list(COMPACT_SIGNATURES.items()):
             fn = getattr(l, name)            # AttributeError if the .so lacks a declared symbol
             fn.restype, fn.argtypes = res, args
         got = l.gdr_abi_version()

@@ -656,6 +656,59 @@ class GDRRetriever:
         out[order] = fc.cmap[tgt.long()].cpu().numpy()
         return out
 
+    @torch.no_grad()
+    def compact_documents(self, chunk_rows=0):
+        """Reclaims the rows of the removed documents: the live rows (live_rows: the members of some cluster) move to the front of
+        doc_embed in their order and ARE the corpus from here on — doc ids are renumbered, old id r becomes plan.new_id[r].
+        Compacted in place on the device (ops.RowCompaction.rows; chunk_rows bounds the bounce buffer, 0 = the library default):
+        doc_embed in its backing buffer, which keeps its capacity while the view shrinks (the next add_documents appends behind
+        the live rows without a reallocation); both doc_tokens tables when configured; the pre-filter image when one was built
+        (its rows move, its norm bound is kept).  Renumbered: the device index's member list and the host ClusterIndex (one
+        read-back of the CSR, as the other lifecycle calls do; names and offsets unchanged).  live_rows becomes all-live over the
+        new rows.  The frozen centroids stay: the map is monotone, so every cluster's ascending member order and the member rows'
+        values are what they were, and centroids frozen after a compaction have the bits of centroids frozen before it.
+        Returns the ops.RowCompaction (new_id / old_id on the device; .ids() renumbers results a caller still holds).  With nothing
+        dead it is an identity plan and nothing was touched.
+        Must not run while validation_steps() has steps in flight.  Raises GdrError for a sharded retriever, a bf16 doc_embed
+        and a token table whose row is not a multiple of 4 bytes; nothing has changed then."""
+        import numpy as np
+        if self.sharded is not None:
+            raise _ffi.GdrError("compact_documents: a sharded retriever cannot change its documents (sharded removal is not supported)")
+        if self.doc_embed is None or self.doc_embed.dtype != torch.float32:
+            raise _ffi.GdrError("compact_documents needs the fp32 doc_embed (the bf16 precision mode is not supported)")
+        dev = self.doc_embed.device
+        plan = ops.compact_plan(self.live_rows)
+        if plan.identity:
+            return plan
+        # everything that can refuse comes first: the token tables' row size, and the member lists (a member that is no live row)
+        tables = [self.doc_embed] + list(self.doc_tokens if self.doc_tokens is not None else ())
+        tables = [t if t.is_contiguous() else t.contiguous() for t in tables]
+        for t in tables:
+            plan._row_bytes("doc_embed" if t is tables[0] else "a doc_tokens table", t)
+        dci = self._device_index()
+        C_ = len(self.index.names)
+        if dci is not None:
+            dci.compact(plan)
+            offs, mem = dci.offsets, dci.members[:dci.n_members]
+        else:
+            up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)   # noqa: E731
+            offs, mem = up(self.index.offsets), plan.ids(up(self.index.members))
+        csr = torch.cat([offs, mem]).cpu().numpy()                                  # one read-back of the renumbered CSR
+        self.index = self.index.with_csr(csr[:C_ + 1], csr[C_ + 1:])
+        # the rows: each table in place; a table that had no backing buffer yet becomes its own (capacity n_old for later adds)
+        if getattr(self, "_doc_buf", None) is None or self._doc_buf.data_ptr() != tables[0].data_ptr():
+            self._doc_buf = tables[0]
+        self.doc_embed = plan.rows(tables[0], chunk_rows=chunk_rows)
+        if self.doc_tokens is not None:
+            bt, bm = getattr(self, "_tok_buf", (None, None))
+            if bt is None or bt.data_ptr() != tables[1].data_ptr() or bm.data_ptr() != tables[2].data_ptr() or bt.shape[1] != tables[1].shape[1]:
+                self._tok_buf = (tables[1], tables[2])
+            self.doc_tokens = (plan.rows(tables[1], chunk_rows=chunk_rows), plan.rows(tables[2], chunk_rows=chunk_rows))
+        if getattr(self, "_prefiltered", None) is not None:
+            self._prefiltered.compact(plan, self.doc_embed)
+        self._live = plan.live_rows()
+        return plan
+
     def _overwrite_tokens(self, rows, tok, msk):
         """doc_tokens[rows] = (tok, msk), PAD 0 / mask 0 behind a shorter passage; a longer one widens the buffers first (one
         copy of the token table, as in _append_tokens)."""

@@ -317,6 +317,132 @@ class QueryRows:
         return out
 
 
+class RowCompaction:
+    """The renumbering that drops the dead rows of a corpus (compact_plan; include/gdr_hip_compact.h): n_old rows -> n_new live rows in
+    their old order.  new_id int32[n_old] (device): the new row of an old row, -1 for a dead one; old_id int32[n_new] (device): the
+    old row of a new row, ascending; identity: nothing was dead.  An identity plan makes every method a no-op that launches nothing
+    (it hands back what it was given)."""
+
+    def __init__(self, n_old, n_new, new_id, old_id):
+        self.n_old, self.n_new, self.new_id, self.old_id = int(n_old), int(n_new), new_id, old_id
+        self.device = new_id.device
+        self._ws = Workspace(self.device)
+
+    @property
+    def identity(self):
+        return self.n_new == self.n_old
+
+    def _row_bytes(self, what, t):
+        _need_cuda(t)
+        if t.dim() < 1 or t.shape[0] != self.n_old or not t.is_contiguous() or t.device != self.device:
+            raise _ffi.GdrError(f"RowCompaction.rows: {what} must be a contiguous [{self.n_old}, ...] tensor on {self.device}, got "
+                                f"{tuple(t.shape)} on {t.device}")
+        row_bytes = (t.numel() // max(self.n_old, 1)) * t.element_size()
+        if row_bytes == 0 or row_bytes % 4:
+            raise _ffi.GdrError(f"RowCompaction.rows: a row of {what} is {row_bytes} bytes; gdr_rows_compact moves multiples of 4 bytes")
+        return row_bytes
+
+    def rows(self, t, out=None, chunk_rows=0):
+        """Compacts the rows of t (contiguous [n_old, ...], any dtype whose row is a multiple of 4 bytes: fp32 / bf16 embeddings,
+        int64 token tables) — gdr_rows_compact.  out=None: in place, returns the view t[:n_new] of the same storage (rows >= n_new
+        keep what they held); chunk_rows bounds the bounce buffer (0 = the library default, 64 MiB whatever n_old is).  Otherwise
+        writes out[:n_new] (same dtype and row shape, not overlapping t) and returns it."""
+        row_bytes = self._row_bytes("t", t)
+        if out is not None:
+            _need_cuda(out)
+            if (out.dtype != t.dtype or out.dim() != t.dim() or out.shape[1:] != t.shape[1:] or out.shape[0] < self.n_new
+                    or not out.is_contiguous() or out.device != t.device):
+                raise _ffi.GdrError(f"RowCompaction.rows: out must be a contiguous {t.dtype} [>= {self.n_new}, ...] tensor with t's row shape")
+            if out.data_ptr() == t.data_ptr():
+                out = None
+        if self.identity:
+            if out is None:
+                return t
+            out[:self.n_new].copy_(t)                                 # nothing to compact: the rows as they are
+            return out[:self.n_new]
+        if self.n_new == 0:
+            return t[:0] if out is None else out[:0]
+        if out is not None:
+            check(lib().gdr_rows_compact(ptr(t), ptr(out), self.n_old, row_bytes, ptr(self.old_id), self.n_new, 0, None, 0, stream_ptr()),
+                  "gdr_rows_compact")
+            return out[:self.n_new]
+        chunk = int(chunk_rows)
+        if chunk < 0:
+            raise _ffi.GdrError(f"RowCompaction.rows: chunk_rows={chunk} must not be negative")
+        if chunk == 0:                                                # the library default, not beyond what this table needs
+            chunk = max((lib().gdr_rows_compact_workspace_bytes(row_bytes, 0) - 256) // row_bytes, 1)
+        chunk = min(chunk, self.n_new)
+        ws = self._ws.get(lib().gdr_rows_compact_workspace_bytes(row_bytes, chunk))
+        check(lib().gdr_rows_compact(ptr(t), ptr(t), self.n_old, row_bytes, ptr(self.old_id), self.n_new, chunk, ptr(ws), ws.numel(),
+                                     stream_ptr()), "gdr_rows_compact")
+        return t[:self.n_new]
+
+    def ids(self, t, strict=True):
+        """Remaps a tensor of doc ids (int32 or int64, any shape, on the device: stored search results, member lists) —
+        gdr_ids_remap: a negative id (the -1 padding of result lists) stays, a live row's id becomes its new one.  An id that was
+        dead or out of range raises GdrError (one read-back of the status word); strict=False returns -1 there instead and reads
+        nothing back.  Returns a new tensor of t's shape and dtype."""
+        _need_cuda(t)
+        if t.dtype not in (torch.int32, torch.int64) or t.device != self.device:
+            raise _ffi.GdrError(f"RowCompaction.ids: an int32 / int64 tensor on {self.device}, got {t.dtype} on {t.device}")
+        if self.identity or self.n_old == 0:
+            return t
+        flat = t.reshape(-1)
+        if t.dtype == torch.int64:                                   # doc ids are int32 values; anything larger is out of range
+            flat = torch.where((flat >= 2 ** 31) | (flat < -2 ** 31), torch.full_like(flat, 2 ** 31 - 1), flat)
+        src = flat.to(torch.int32).contiguous()
+        out = torch.empty_like(src)
+        status = torch.empty(1, dtype=torch.int32, device=self.device)
+        check(lib().gdr_ids_remap(ptr(self.new_id), self.n_old, ptr(src), ptr(out), src.numel(), ptr(status), stream_ptr()), "gdr_ids_remap")
+        if strict and int(status.item()):
+            raise _ffi.GdrError("RowCompaction.ids: an id names a dead row or lies outside the old corpus "
+                                f"[0, {self.n_old}) (strict=False maps such ids to -1)")
+        return out.to(t.dtype).view(t.shape)
+
+    def query_rows(self, qr):
+        """The QueryRows over the n_new rows that allows query q exactly the (surviving) rows qr allowed it — gdr_rowmask_compact."""
+        if not isinstance(qr, QueryRows) or qr.n != self.n_old or qr.device != self.device:
+            raise _ffi.GdrError(f"RowCompaction.query_rows: an ops.QueryRows over the {self.n_old} old rows, on {self.device}")
+        if self.identity:
+            return qr
+        out = QueryRows(qr.B, self.n_new, self.device)
+        if qr.B and self.n_new:
+            win = qr._words if qr._words.is_contiguous() else qr._words.contiguous()
+            _need_cuda(win)
+            check(lib().gdr_rowmask_compact(ptr(win), win.shape[1], qr.B, self.n_old, ptr(self.old_id), self.n_new, ptr(out._words),
+                                            out._words.shape[1], stream_ptr()), "gdr_rowmask_compact")
+        return out
+
+    def live_rows(self):
+        """The LiveRows of the compacted corpus: all n_new rows live."""
+        return LiveRows.from_bool(torch.ones(self.n_new, dtype=torch.bool, device=self.device))
+
+
+def compact_plan(live, workspace=None):
+    """LiveRows (on the GPU) -> RowCompaction — gdr_rows_compact_plan: popcounts, a multi-block scan and ordered placement on the
+    device.  Reads back exactly one number, the plan's status word: a LiveRows.count that is not the bitmap's popcount raises
+    GdrError."""
+    if not isinstance(live, LiveRows):
+        raise _ffi.GdrError("compact_plan: an ops.LiveRows")
+    _need_cuda(live.words)
+    dev, N, n_live = live.device, live.n, live.count
+    if N == 0:
+        z = torch.empty(0, dtype=torch.int32, device=dev)
+        return RowCompaction(0, 0, z, z)
+    if not 0 <= n_live <= N:
+        raise _ffi.GdrError(f"compact_plan: LiveRows.count = {n_live} for {N} rows")
+    new_id = torch.empty(N, dtype=torch.int32, device=dev)
+    old_id = torch.empty(n_live, dtype=torch.int32, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    words = live.words.contiguous()
+    ws = (workspace or Workspace(dev)).get(lib().gdr_rows_compact_plan_workspace_bytes(N))
+    check(lib().gdr_rows_compact_plan(ptr(words), N, n_live, ptr(new_id), ptr(old_id) if n_live else None, ptr(status), ptr(ws),
+                                      ws.numel(), stream_ptr()), "gdr_rows_compact_plan")
+    if int(status.item()):
+        raise _ffi.GdrError(f"compact_plan: LiveRows.count = {n_live} is not the number of set bits of the bitmap")
+    return RowCompaction(N, n_live, new_id, old_id)
+
+
 # the workspace layout of a masked call — one per call: with allowed=, live= is ANDed into the per-query bitmaps (_place_bitmaps)
 def _mask_flag(live, allowed):
     return _ffi.SIM_QUERY_MASK if allowed is not None else _ffi.SIM_LIVE_MASK if live is not None else 0
@@ -595,6 +721,24 @@ class PrefilteredCorpus:
             self.update_rows(torch.arange(N, N2, dtype=torch.int32, device=self.D.device))
         return self
 
+    def compact(self, plan, D_new):
+        """The corpus was compacted through `plan` (a RowCompaction over its N rows): D_new is the fp32 [n_new, d] matrix of the live
+        rows.  The image's rows MOVE (RowCompaction.rows, in place in the image's buffer), they are not recomputed: rounding is per
+        row, so the image equals a fresh image of D_new bit for bit.  dnorm_max is kept: the largest norm over a superset of the
+        rows is still an upper bound, which is all the band needs (include/gdr_hip_prefilter_mask.h)."""
+        _need_cuda(D_new)
+        N, d = self.D.shape
+        if not isinstance(plan, RowCompaction) or plan.n_old != N:
+            raise _ffi.GdrError(f"PrefilteredCorpus.compact: a RowCompaction over the corpus' {N} rows")
+        if D_new.dtype != torch.float32 or D_new.dim() != 2 or tuple(D_new.shape) != (plan.n_new, d) or D_new.device != self.D.device:
+            raise _ffi.GdrError(f"PrefilteredCorpus.compact: an fp32 [{plan.n_new}, {d}] tensor on {self.D.device}, not {D_new.dtype} "
+                                f"{tuple(D_new.shape)}")
+        self._bind(_f32c(D_new))
+        if d % 2:
+            return self.refresh()                                    # a bf16 row of odd d is no multiple of 4 bytes (and no image the pre-filter could use)
+        plan.rows(self._D16_buf[:N])
+        return self
+
 
 PREFILTER_MIN_BATCH = 1           # the pre-filter serves every batch size: at B <= 32 its corpus-wide pass is the HBM stream over
                                   # the bf16 image (half the bytes of the fp32 stream): 0.205 vs 0.241 ms at B = 1
@@ -852,6 +996,20 @@ class DeviceClusterIndex:
         self.n_members, self.max_cluster = int(mem.numel()), mx
         self._make_struct()
         return gone
+
+    def compact(self, plan):
+        """The corpus was compacted through `plan` (a RowCompaction): every member becomes its new id, in place in the device member
+        list (gdr_ids_remap); the offsets are untouched — the map is monotone, so every cluster keeps its members in their order.
+        A member that names a dead or unknown row raises GdrError (one read-back) and leaves the list as it was."""
+        if not isinstance(plan, RowCompaction):
+            raise _ffi.GdrError("DeviceClusterIndex.compact: an ops.RowCompaction")
+        if plan.identity or self.n_members == 0:
+            return
+        try:
+            mem = plan.ids(self.members[:self.n_members])
+        except _ffi.GdrError as e:
+            raise _ffi.GdrError(f"DeviceClusterIndex.compact: a cluster member is not a live row of the plan ({e})") from None
+        self.members[:self.n_members].copy_(mem)
 
     def candidates(self, out_ids, B, R):
         """out_ids int64[B*R, max_length] (device, untrimmed) -> (cluster_of int32[B*R], cand_offsets int32[B,R+1],

@@ -861,5 +861,7 @@ int gdr_beam_search_table(const float* table, int B, int out_vocab, int num_beam
 
 /* The pre-filtered search over live rows / per-query filters and the row-wise upkeep of the bf16 image: declared in a header of their own. */
 #include "gdr_hip_prefilter_mask.h"
+/* Compacting a live corpus (the plan, the row mover, the id and row-bitmap remaps): declared in a header of their own. */
+#include "gdr_hip_compact.h"
 
 #endif /* GDR_HIP_H */
