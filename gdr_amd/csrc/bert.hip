@@ -7,7 +7,12 @@
 //
 // Same kernels as the T5 path: the fp32 MFMA GEMM core with fused bias / residual / GeLU epilogues, the MFMA
 // attention kernel (no bias table, scale dh^-0.5), LayerNorm with 16-byte loads and wave reductions.
-#include "layers.h"
+//
+// Layout of this file.  Four forwards, each with its block body written out: gdr_bert_encoder_forward (padded fp32) and
+// bert_ragged_f32_blocks / bert_ragged_bf16_blocks / bert_ragged_f16x2_blocks (packed; bert_ragged_impl in front of them does the
+// checks, the pack plan, the padded fallback, the stream-K scratch and the embedding).  What stands around a body is tower.h's, shared
+// with encoder.hip; the workspace layouts (BertWs, BertRagWs) and their typed views (carve_bert, carve_bert_rag) are below.
+#include "tower.h"
 
 namespace gdr {
 
@@ -61,6 +66,19 @@ static BertWs bert_ws(const GdrBertWeights& w, int64_t M) {
   b.total = o;
   return b;
 }
+struct BertBuf {
+  float *x, *t, *qkv, *ctx, *ff;
+  char* scratch;  // split-K slabs / stream-K scratch (tower_streamk; StreamK::part is its first byte)
+};
+static BertBuf carve_bert(char* base, const BertWs& ws) {
+  return {reinterpret_cast<float*>(base + ws.x),   reinterpret_cast<float*>(base + ws.t),  reinterpret_cast<float*>(base + ws.qkv),
+          reinterpret_cast<float*>(base + ws.ctx), reinterpret_cast<float*>(base + ws.ff), base + ws.scratch};
+}
+static int check_bert_layer(const char* who, const GdrBertLayer& ly, int i) {
+  GDR_CHECK_ARG(ly.wqkv && ly.bqkv && ly.wo && ly.bo && ly.ln1_w && ly.ln1_b && ly.wi && ly.bi && ly.wo2 && ly.bo2 && ly.ln2_w && ly.ln2_b,
+                "%s: layer %d null weight", who, i);
+  return GDR_OK;
+}
 
 }  // namespace gdr
 
@@ -74,51 +92,28 @@ extern "C" int gdr_bert_encoder_forward(const GdrBertWeights* w, const int64_t* 
                                         float* out_pooled, void* workspace, size_t workspace_bytes, void* stream_) {
   using namespace gdr;
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  GDR_CHECK_ARG(w && ids && workspace && (out_hidden || out_pooled), "bert: null pointer");
-  GDR_CHECK_ARG(B > 0 && L > 0 && L <= 512 && L <= w->max_pos, "bert: B=%d L=%d (L must be <= min(512, max_pos = %d))", B, L, w->max_pos);
+  GDR_TRY(check_bert_call("bert", w && ids && workspace && (out_hidden || out_pooled), w, B, L));
   const int d = w->d_model, H = w->num_heads;
-  GDR_CHECK_ARG(d % 4 == 0 && H > 0 && d % H == 0 && (d / H) % 4 == 0 && w->d_ff % 4 == 0, "bert: unsupported dims");
-  GDR_CHECK_ARG(w->word_emb && w->pos_emb && w->type_emb && w->emb_ln_w && w->emb_ln_b && w->layers, "bert: null weight");
   const int64_t M = (int64_t)B * L;
   const BertWs ws = bert_ws(*w, M);
-  if (workspace_bytes < ws.total) {
-    set_error("bert: workspace %zu < required %zu", workspace_bytes, ws.total);
-    return GDR_ENOSPC;
-  }
-  GDR_CHECK_ARG(((uintptr_t)workspace & 255) == 0, "bert: workspace must be 256-byte aligned");
-  char* base = static_cast<char*>(workspace);
-  float* x = reinterpret_cast<float*>(base + ws.x);
-  float* t = reinterpret_cast<float*>(base + ws.t);
-  float* qkv = reinterpret_cast<float*>(base + ws.qkv);
-  float* ctx = reinterpret_cast<float*>(base + ws.ctx);
-  float* ff = reinterpret_cast<float*>(base + ws.ff);
-  float* scr = reinterpret_cast<float*>(base + ws.scratch);
+  GDR_TRY(check_workspace("bert", workspace, workspace_bytes, ws.total));
+  const BertBuf e = carve_bert(static_cast<char*>(workspace), ws);
+  float *x = e.x, *t = e.t, *qkv = e.qkv, *ctx = e.ctx, *ff = e.ff;
   int rc;
   StreamK sk{};  // the linears' stream-K tail (gemm_f32.hip): scratch inside the GEMM scratch region, flags zeroed per call
-  sk.part = scr, sk.flag = reinterpret_cast<int32_t*>(base + ws.scratch + STREAMK_PART_BYTES), sk.epoch = 0;
-  if (hipMemsetAsync(sk.flag, 0, 512 * sizeof(int32_t), stream) != hipSuccess) {
-    set_error("bert: memset of the stream-K flags failed");
-    return GDR_EHIP;
-  }
+  if ((rc = tower_streamk(e.scratch, &sk, "bert", stream))) return rc;
+  float* scr = sk.part;  // the split-K forms' slab space: the same region
   hipLaunchKernelGGL(bert_embed_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, stream, w->word_emb, w->pos_emb,
                      w->type_emb, ids, token_type_ids, M, L, d / 4, w->vocab_size, w->type_vocab, t);
   GDR_CHECK_LAUNCH("bert_embed_kernel");
   if ((rc = launch_layernorm(t, w->emb_ln_w, w->emb_ln_b, x, M, d, w->eps, nullptr, stream))) return rc;
 
-  AttnArgs at{};
-  at.q = qkv, at.k = qkv + d, at.v = qkv + 2 * d, at.out = ctx;
-  at.ldq = at.ldk = at.ldv = 3 * d, at.ldo = d;
-  at.q_bstride = at.k_bstride = at.o_bstride = L;
-  at.B = B, at.H = H, at.dk = d / H, at.Lq = L, at.Lk = L, at.q_pos0 = 0;
-  at.scale = 1.0f / sqrtf((float)(d / H));
-  at.rel_bias = nullptr, at.bidirectional = 1, at.num_buckets = 0;
-  at.key_mask = mask, at.mask_bstride = L, at.causal = 0, at.causal_neg_inf = 0, at.kv_rows = nullptr, at.kv_group = 1;
+  AttnArgs at = self_attn_args(B, H, d / H, L, 3 * d, mask);
+  attn_f32(at, qkv, ctx), attn_scale(at, 1.0f / sqrtf((float)(d / H)));
 
   for (int i = 0; i < w->num_layers; ++i) {
     const GdrBertLayer& ly = w->layers[i];
-    GDR_CHECK_ARG(ly.wqkv && ly.bqkv && ly.wo && ly.bo && ly.ln1_w && ly.ln1_b && ly.wi && ly.bi && ly.wo2 && ly.bo2 &&
-                      ly.ln2_w && ly.ln2_b,
-                  "bert: layer %d null weight", i);
+    if ((rc = check_bert_layer("bert", ly, i))) return rc;
     if ((rc = launch_linear_f32_ws(x, d, ly.wqkv, d, qkv, 3 * d, M, 3 * d, d, GDR_EPI_BIAS, ly.bqkv, nullptr, 0, scr, BERT_SCRATCH_BYTES,
                                    stream, &sk))) return rc;
     if ((rc = launch_attention(at, stream))) return rc;
@@ -183,17 +178,20 @@ __global__ __launch_bounds__(256) void bert_embed_packed_kernel(const float* __r
 // predicate (virtual K = 3 d); otherwise wi stores fp32 in `ff` and a split launch makes the planes
 static bool bert_plane_epilogue(const GdrBertWeights& w, int64_t M) { return linear_bf16_tile_form(M, w.d_ff, w.d_model, 0, 3, 2) >= 192; }
 
-struct BertRagWs {
-  size_t seq_len, seq_off, row_src, rows_total, ctx_cls, x_cls, t_cls, ff_cls, x16, pl_ff, total;
+struct BertRagWs {  // behind a BertWs: the pack plan, the CLS rows of a pooled-only call's last block, the bf16 / plane images
+  PackPlanWs plan;
+  size_t ctx_cls, x_cls, t_cls, ff_cls, x16, pl_ff, total;
+};
+struct BertRagBuf {
+  PackPlan plan;
+  float *ctx_cls, *x_cls, *t_cls, *ff_cls;
+  void *x16, *pl_ff;
 };
 static BertRagWs bert_rag_ws(const GdrBertWeights& w, int B, int L) {
   BertRagWs r{};
   const size_t d = w.d_model, M = (size_t)B * L;
-  size_t o = bert_ws(w, (int64_t)M).total;
-  r.seq_len = o, o += align_up((size_t)B * 4, 256);
-  r.seq_off = o, o += align_up((size_t)(B + 1) * 4, 256);
-  r.row_src = o, o += align_up(M * 4, 256);
-  r.rows_total = o, o += 256;
+  r.plan = pack_plan_ws(B, L, bert_ws(w, (int64_t)M).total);
+  size_t o = r.plan.end;
   r.ctx_cls = o, o += align_up((size_t)B * d * 4, 256);
   r.x_cls = o, o += align_up((size_t)B * d * 4, 256);
   r.t_cls = o, o += align_up((size_t)B * d * 4, 256);
@@ -205,172 +203,40 @@ static BertRagWs bert_rag_ws(const GdrBertWeights& w, int B, int L) {
   r.total = o;
   return r;
 }
+static BertRagBuf carve_bert_rag(char* base, const BertRagWs& r) {
+  return {carve_pack_plan(base, r.plan),
+          reinterpret_cast<float*>(base + r.ctx_cls),
+          reinterpret_cast<float*>(base + r.x_cls),
+          reinterpret_cast<float*>(base + r.t_cls),
+          reinterpret_cast<float*>(base + r.ff_cls),
+          base + r.x16,
+          base + r.pl_ff};
+}
 
-// prec: 0 fp32, 1 bf16 precision mode, 2 the fp16 x 2 split form of the fp32 linears (r06, exploratory: fp32-level error on the fp16 MFMA
-// path; weights as plane rows [N, 2 K] fp16; everything but the linears is the fp32 path's)
-static int bert_ragged_impl(const GdrBertWeights* w, const int64_t* ids, const int64_t* mask, const int64_t* token_type_ids, int B,
-                            int L, float* out_hidden, float* out_pooled, int64_t live_rows_hint, void* workspace,
-                            size_t workspace_bytes, int prec, hipStream_t stream) {
-  const bool bf16 = prec == 1, f16s = prec == 2;
-  if (B == 0) return GDR_OK;
-  GDR_CHECK_ARG(w && ids && mask && workspace && (out_hidden || out_pooled), "bert_ragged: null pointer");
-  GDR_CHECK_ARG(B > 0 && L > 0 && L <= 512 && L <= w->max_pos, "bert_ragged: B=%d L=%d (L must be <= min(512, max_pos = %d))", B, L, w->max_pos);
-  const int d = w->d_model, H = w->num_heads;
-  GDR_CHECK_ARG(d % 4 == 0 && H > 0 && d % H == 0 && (d / H) % 4 == 0 && w->d_ff % 4 == 0, "bert_ragged: unsupported dims");
-  GDR_CHECK_ARG(w->word_emb && w->pos_emb && w->type_emb && w->emb_ln_w && w->emb_ln_b && w->layers, "bert_ragged: null weight");
+// The three packed block sequences.  Each starts behind the embedding LayerNorm (x, and for the bf16 / fp16 x 2 forms its image x16,
+// are written) and ends with the packed rows of x back in the caller's layout.
+
+// fp32: the un-split linears over the live rows; the pooled-only tail on the B CLS rows
+static int bert_ragged_f32_blocks(const GdrBertWeights* w, const int64_t* mask, int B, int L, float* out_hidden, float* out_pooled,
+                                  int64_t live_rows_hint, const BertBuf& e, const BertRagBuf& r, StreamK* sk, hipStream_t stream) {
+  const int d = w->d_model, H = w->num_heads, dh = d / H, dff = w->d_ff;
   const int64_t M = (int64_t)B * L;
-  const int dh = d / H, dff = w->d_ff;
-  const BertWs ws = bert_ws(*w, M);
-  const BertRagWs rw = bert_rag_ws(*w, B, L);
-  if (workspace_bytes < rw.total) {
-    set_error("bert_ragged: workspace %zu < required %zu", workspace_bytes, rw.total);
-    return GDR_ENOSPC;
-  }
-  GDR_CHECK_ARG(((uintptr_t)workspace & 255) == 0, "bert_ragged: workspace must be 256-byte aligned");
-  char* base = static_cast<char*>(workspace);
+  float *x = e.x, *t = e.t, *qkv = e.qkv, *ctx = e.ctx, *ff = e.ff;
+  float *ctx_cls = r.ctx_cls, *x_cls = r.x_cls, *t_cls = r.t_cls, *ff_cls = r.ff_cls;
+  const int32_t* seq_off = r.plan.seq_off;
+  const int64_t* rows_dev = r.plan.rows_dev;
   int rc;
-  int32_t* seq_len = reinterpret_cast<int32_t*>(base + rw.seq_len);
-  int32_t* seq_off = reinterpret_cast<int32_t*>(base + rw.seq_off);
-  int32_t* row_src = reinterpret_cast<int32_t*>(base + rw.row_src);
-  int64_t* rows_dev = reinterpret_cast<int64_t*>(base + rw.rows_total);
-  if ((rc = launch_pack_plan(mask, B, L, seq_len, seq_off, row_src, rows_dev, stream))) return rc;
-  const int64_t tiles = ((M + 127) / 128) * ((d + 127) / 128);
-  const bool packs = dh == 64 && d % 32 == 0 && dff % 32 == 0;
-  if (bf16 || f16s) {
-    GDR_CHECK_ARG(packs && d % 128 == 0 && dff % 128 == 0,
-                  "bert_ragged(bf16 / split): needs head width 64 and d, d_ff multiples of 128 (d=%d H=%d d_ff=%d)", d, H, dff);
-  } else if (!packs || tiles < 192) {
-    // small problem / other head size: the padded forward, then the rows the packed form would not have computed are zeroed
-    float* full = out_hidden ? out_hidden : reinterpret_cast<float*>(base + ws.qkv);  // qkv is dead when the last LayerNorm runs
-    if ((rc = gdr_bert_encoder_forward(w, ids, mask, token_type_ids, B, L, full, out_pooled, workspace, ws.total, stream))) return rc;
-    return out_hidden ? launch_zero_dead_rows(out_hidden, seq_len, B, L, d, stream) : GDR_OK;
-  }
-  float* x = reinterpret_cast<float*>(base + ws.x);
-  float* t = reinterpret_cast<float*>(base + ws.t);
-  float* qkv = reinterpret_cast<float*>(base + ws.qkv);
-  float* ctx = reinterpret_cast<float*>(base + ws.ctx);
-  float* ff = reinterpret_cast<float*>(base + ws.ff);
-  float* scr = reinterpret_cast<float*>(base + ws.scratch);
-  float* ctx_cls = reinterpret_cast<float*>(base + rw.ctx_cls);
-  float* x_cls = reinterpret_cast<float*>(base + rw.x_cls);
-  float* t_cls = reinterpret_cast<float*>(base + rw.t_cls);
-  float* ff_cls = reinterpret_cast<float*>(base + rw.ff_cls);
-  void* x16 = base + rw.x16;
-  StreamK sk{};
-  sk.part = scr, sk.flag = reinterpret_cast<int32_t*>(base + ws.scratch + STREAMK_PART_BYTES), sk.epoch = 0;
-  if (hipMemsetAsync(sk.flag, 0, 512 * sizeof(int32_t), stream) != hipSuccess) {
-    set_error("bert_ragged: memset of the stream-K flags failed");
-    return GDR_EHIP;
-  }
-  hipLaunchKernelGGL(bert_embed_packed_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, stream, w->word_emb, w->pos_emb, w->type_emb,
-                     ids, token_type_ids, row_src, rows_dev, L, d / 4, w->vocab_size, w->type_vocab, t);
-  GDR_CHECK_LAUNCH("bert_embed_packed_kernel");
-  const bool plane_epi = bert_plane_epilogue(*w, M);
-  void* pl_ff = plane_epi ? static_cast<void*>(ff) : static_cast<void*>(base + rw.pl_ff);
-  const int ld_d = 2 * d, ld_ff = 2 * dff;  // fp16 x 2 plane rows
-  if ((rc = launch_layernorm_dev(t, w->emb_ln_w, w->emb_ln_b, x, rows_dev, M, d, w->eps, nullptr, stream, (bf16 || f16s) ? x16 : nullptr,
-                                 f16s ? ld_d : 0)))
-    return rc;
-
-  AttnArgs at{};
-  at.ldq = at.ldk = at.ldv = 3 * d, at.ldo = d;
-  at.q_bstride = at.k_bstride = at.o_bstride = L;
-  at.B = B, at.H = H, at.dk = dh, at.Lq = L, at.Lk = L, at.q_pos0 = 0;
-  at.rel_bias = nullptr, at.bidirectional = 1, at.num_buckets = 0;
-  at.key_mask = mask, at.mask_bstride = L, at.causal = 0, at.causal_neg_inf = 0, at.kv_rows = nullptr, at.kv_group = 1;
-  at.seq_off = seq_off, at.seq_len = seq_len;
-  if (bf16) {
-    const __bf16* q16 = reinterpret_cast<const __bf16*>(qkv);
-    at.q = reinterpret_cast<const float*>(q16), at.k = reinterpret_cast<const float*>(q16 + d), at.v = reinterpret_cast<const float*>(q16 + 2 * d);
-    at.qkv_bf16 = 1, at.out = nullptr, at.out_bf16 = ctx;  // the context as bf16 [rows, d] in the fp32 ctx buffer
-    at.scale = 1.0f;                                       // 1 / sqrt(dh) is folded into the q rows of wqkv / bqkv (gdr_hip.h)
-  } else {
-    at.q = qkv, at.k = qkv + d, at.v = qkv + 2 * d, at.out = ctx;
-    at.scale = 1.0f / sqrtf((float)dh);
-  }
+  AttnArgs at = self_attn_args(B, H, dh, L, 3 * d, mask);
+  attn_f32(at, qkv, ctx), attn_scale(at, 1.0f / sqrtf((float)dh)), attn_packed(at, r.plan);
   auto linear = [&](const float* A, int64_t lda, const float* W, float* C, int64_t ldc, int N, int K, int epi, const float* bias,
                     const float* residual) -> int {
-    return launch_linear_f32_dev(A, lda, W, K, C, ldc, M, rows_dev, N, K, epi, bias, residual, ldc, live_rows_hint, stream, &sk);
-  };
-  // bf16 linear: A bf16 [rows, K]; act 0 none / 2 gelu; out_bf16: the output is the next linear's bf16 operand
-  auto lin16 = [&](const void* A, const float* W, float* C, int64_t ldc, int64_t rows, const int64_t* md, int N, int K, int act,
-                   const float* bias, const float* residual, int out_bf16) -> int {
-    ProfScope prof(PROF_LINEAR, 2.0 * (double)(md && live_rows_hint >= 0 ? live_rows_hint : rows) * (double)N * (double)K, stream);
-    const int rc_ = launch_linear_bf16_glds(A, K, W, K, C, ldc, rows, N, K, bias != nullptr, residual != nullptr, act, bias, residual, ldc,
-                                            out_bf16, stream, md);
-    if (rc_ > 0) {
-      set_error("bert_ragged(bf16): shape not served by the LDS-DMA linear");
-      return GDR_EINVAL;
-    }
-    return rc_;
-  };
-  // fp16 x 2 split GEMM over plane rows P [rows, 2 K]; out_planes: the (activated) output leaves as plane rows [rows, 2 N]
-  auto gsplit = [&](const void* P, const float* W, void* C, int64_t ldc, int64_t rows, const int64_t* md, int N, int K, int act,
-                    const float* bias, const float* residual, int out_planes) -> int {
-    ProfScope prof(PROF_LINEAR, 2.0 * (double)(md && live_rows_hint >= 0 ? live_rows_hint : rows) * (double)N * (double)K, stream);
-    const int rc_ = launch_linear_bf16_glds(P, 2 * K, W, 2 * K, static_cast<float*>(C), ldc, rows, N, K, bias != nullptr, residual != nullptr, act,
-                                            bias, residual, ldc, out_planes ? 3 : 0, stream, md, 2);
-    if (rc_ > 0) {
-      set_error("bert_ragged(split): shape not served by the LDS-DMA linear");
-      return GDR_EINVAL;
-    }
-    return rc_;
+    return launch_linear_f32_dev(A, lda, W, K, C, ldc, M, rows_dev, N, K, epi, bias, residual, ldc, live_rows_hint, stream, sk);
   };
   const bool pooled_only = out_hidden == nullptr;
   for (int i = 0; i < w->num_layers; ++i) {
     const GdrBertLayer& ly = w->layers[i];
-    GDR_CHECK_ARG(ly.wqkv && ly.bqkv && ly.wo && ly.bo && ly.ln1_w && ly.ln1_b && ly.wi && ly.bi && ly.wo2 && ly.bo2 && ly.ln2_w &&
-                      ly.ln2_b,
-                  "bert_ragged: layer %d null weight", i);
+    if ((rc = check_bert_layer("bert_ragged", ly, i))) return rc;
     const bool last = i + 1 == w->num_layers;
-    if (f16s) {
-      // x (fp32) and its plane rows x16 come from the LayerNorm in front; attention is the fp32 path's
-      if ((rc = gsplit(x16, ly.wqkv, qkv, 3 * d, M, rows_dev, 3 * d, d, 0, ly.bqkv, nullptr, 0))) return rc;
-      if ((rc = launch_attention(at, stream))) return rc;
-      if (pooled_only && last) {
-        if ((rc = launch_gather_rows(ctx, seq_off, B, d, ctx_cls, stream))) return rc;
-        if ((rc = launch_gather_rows(x, seq_off, B, d, x_cls, stream))) return rc;
-        if ((rc = launch_split_f32_bf16x3(ctx_cls, d, x16, ld_d, B, d, nullptr, stream, 1))) return rc;
-        if ((rc = gsplit(x16, ly.wo, t_cls, d, B, nullptr, d, d, 0, ly.bo, x_cls, 0))) return rc;
-        if ((rc = launch_layernorm(t_cls, ly.ln1_w, ly.ln1_b, x_cls, B, d, w->eps, nullptr, stream, x16, ld_d))) return rc;
-        if ((rc = gsplit(x16, ly.wi, ff_cls, dff, B, nullptr, dff, d, 2, ly.bi, nullptr, 0))) return rc;
-        if ((rc = launch_split_f32_bf16x3(ff_cls, dff, pl_ff, ld_ff, B, dff, nullptr, stream, 1))) return rc;
-        if ((rc = gsplit(pl_ff, ly.wo2, t_cls, d, B, nullptr, d, dff, 0, ly.bo2, x_cls, 0))) return rc;
-        return launch_layernorm(t_cls, ly.ln2_w, ly.ln2_b, out_pooled, B, d, w->eps, nullptr, stream);
-      }
-      if ((rc = launch_split_f32_bf16x3(ctx, d, x16, ld_d, M, d, rows_dev, stream, 1))) return rc;  // x16 is free: x's planes fed qkv already
-      if ((rc = gsplit(x16, ly.wo, t, d, M, rows_dev, d, d, 0, ly.bo, x, 0))) return rc;
-      if ((rc = launch_layernorm_dev(t, ly.ln1_w, ly.ln1_b, x, rows_dev, M, d, w->eps, nullptr, stream, x16, ld_d))) return rc;
-      if (plane_epi) {
-        if ((rc = gsplit(x16, ly.wi, pl_ff, ld_ff, M, rows_dev, dff, d, 2, ly.bi, nullptr, 1))) return rc;  // GeLU, plane rows out
-      } else {
-        if ((rc = gsplit(x16, ly.wi, ff, dff, M, rows_dev, dff, d, 2, ly.bi, nullptr, 0))) return rc;
-        if ((rc = launch_split_f32_bf16x3(ff, dff, pl_ff, ld_ff, M, dff, rows_dev, stream, 1))) return rc;
-      }
-      if ((rc = gsplit(pl_ff, ly.wo2, t, d, M, rows_dev, d, dff, 0, ly.bo2, x, 0))) return rc;
-      if ((rc = launch_layernorm_dev(t, ly.ln2_w, ly.ln2_b, x, rows_dev, M, d, w->eps, nullptr, stream, last ? nullptr : x16, last ? 0 : ld_d)))
-        return rc;
-      continue;
-    }
-    if (bf16) {
-      if ((rc = lin16(x16, ly.wqkv, qkv, 3 * d, M, rows_dev, 3 * d, d, 0, ly.bqkv, nullptr, 1))) return rc;  // q, k, v as bf16
-      if ((rc = launch_attention(at, stream))) return rc;
-      if (pooled_only && last) {
-        if ((rc = launch_gather_rows(ctx, seq_off, B, d / 2, ctx_cls, stream))) return rc;  // bf16 rows are d / 2 floats wide
-        if ((rc = launch_gather_rows(x, seq_off, B, d, x_cls, stream))) return rc;
-        if ((rc = lin16(ctx_cls, ly.wo, t_cls, d, B, nullptr, d, d, 0, ly.bo, x_cls, 0))) return rc;
-        if ((rc = launch_layernorm(t_cls, ly.ln1_w, ly.ln1_b, x_cls, B, d, w->eps, nullptr, stream, ctx_cls))) return rc;  // + bf16 image
-        if ((rc = lin16(ctx_cls, ly.wi, ff_cls, dff, B, nullptr, dff, d, 2, ly.bi, nullptr, 1))) return rc;
-        if ((rc = lin16(ff_cls, ly.wo2, t_cls, d, B, nullptr, d, dff, 0, ly.bo2, x_cls, 0))) return rc;
-        return launch_layernorm(t_cls, ly.ln2_w, ly.ln2_b, out_pooled, B, d, w->eps, nullptr, stream);
-      }
-      if ((rc = lin16(ctx, ly.wo, t, d, M, rows_dev, d, d, 0, ly.bo, x, 0))) return rc;
-      if ((rc = launch_layernorm_dev(t, ly.ln1_w, ly.ln1_b, x, rows_dev, M, d, w->eps, nullptr, stream, x16))) return rc;
-      if ((rc = lin16(x16, ly.wi, ff, dff, M, rows_dev, dff, d, 2, ly.bi, nullptr, 1))) return rc;  // gelu, bf16 out (in the ff buffer)
-      if ((rc = lin16(ff, ly.wo2, t, d, M, rows_dev, d, dff, 0, ly.bo2, x, 0))) return rc;
-      if ((rc = launch_layernorm_dev(t, ly.ln2_w, ly.ln2_b, x, rows_dev, M, d, w->eps, nullptr, stream, last ? nullptr : x16))) return rc;
-      continue;
-    }
     if ((rc = linear(x, d, ly.wqkv, qkv, 3 * d, 3 * d, d, GDR_EPI_BIAS, ly.bqkv, nullptr))) return rc;
     if ((rc = launch_attention(at, stream))) return rc;
     if (pooled_only && last) {
@@ -390,16 +256,149 @@ static int bert_ragged_impl(const GdrBertWeights* w, const int64_t* ids, const i
     if ((rc = linear(ff, dff, ly.wo2, t, d, d, dff, GDR_EPI_BIAS_RESIDUAL, ly.bo2, x))) return rc;
     if ((rc = launch_layernorm_dev(t, ly.ln2_w, ly.ln2_b, x, rows_dev, M, d, w->eps, nullptr, stream))) return rc;
   }
-  // packed rows back into the [B, L, d] layout (PAD rows zero) and / or the CLS pool
-  if (out_pooled && (rc = launch_gather_rows(x, seq_off, B, d, out_pooled, stream))) return rc;
-  if (out_hidden) {
-    if (hipMemsetAsync(out_hidden, 0, (size_t)M * d * sizeof(float), stream) != hipSuccess) {
-      set_error("bert_ragged: memset failed");
-      return GDR_EHIP;
+  return unpack_rows(x, r.plan, B, M, d, out_pooled, out_hidden, "bert_ragged", stream);
+}
+
+// bf16 precision mode: bf16 linear operands, written by their producers (LayerNorm -> x16, attention -> ctx, the GeLU epilogue -> ff);
+// q, k, v leave the qkv linear as bf16, 1 / sqrt(dh) folded into the q rows of wqkv / bqkv (gdr_hip.h)
+static int bert_ragged_bf16_blocks(const GdrBertWeights* w, const int64_t* mask, int B, int L, float* out_hidden, float* out_pooled,
+                                   int64_t live_rows_hint, const BertBuf& e, const BertRagBuf& r, hipStream_t stream) {
+  const int d = w->d_model, H = w->num_heads, dh = d / H, dff = w->d_ff;
+  const int64_t M = (int64_t)B * L;
+  float *x = e.x, *t = e.t, *qkv = e.qkv, *ctx = e.ctx, *ff = e.ff;
+  float *ctx_cls = r.ctx_cls, *x_cls = r.x_cls, *t_cls = r.t_cls, *ff_cls = r.ff_cls;
+  void* x16 = r.x16;
+  const int32_t* seq_off = r.plan.seq_off;
+  const int64_t* rows_dev = r.plan.rows_dev;
+  int rc;
+  AttnArgs at = self_attn_args(B, H, dh, L, 3 * d, mask);
+  attn_qkv_bf16(at, qkv), attn_ctx_bf16(at, ctx), attn_packed(at, r.plan);  // the context as bf16 [rows, d] in the fp32 ctx buffer
+  // bf16 linear: A bf16 [rows, K]; act 0 none / 2 gelu; out_bf16: the output is the next linear's bf16 operand
+  const GldsLinear glds{"bert_ragged(bf16)", live_rows_hint, 0, stream};
+  auto lin16 = [&](const void* A, const float* W, float* C, int64_t ldc, int64_t rows, const int64_t* md, int N, int K, int act,
+                   const float* bias, const float* residual, int out_bf16) -> int {
+    return linear_glds(glds, A, W, C, ldc, rows, md, N, K, act, bias, residual, out_bf16);
+  };
+  const bool pooled_only = out_hidden == nullptr;
+  for (int i = 0; i < w->num_layers; ++i) {
+    const GdrBertLayer& ly = w->layers[i];
+    if ((rc = check_bert_layer("bert_ragged", ly, i))) return rc;
+    const bool last = i + 1 == w->num_layers;
+    if ((rc = lin16(x16, ly.wqkv, qkv, 3 * d, M, rows_dev, 3 * d, d, 0, ly.bqkv, nullptr, 1))) return rc;  // q, k, v as bf16
+    if ((rc = launch_attention(at, stream))) return rc;
+    if (pooled_only && last) {
+      if ((rc = launch_gather_rows(ctx, seq_off, B, d / 2, ctx_cls, stream))) return rc;  // bf16 rows are d / 2 floats wide
+      if ((rc = launch_gather_rows(x, seq_off, B, d, x_cls, stream))) return rc;
+      if ((rc = lin16(ctx_cls, ly.wo, t_cls, d, B, nullptr, d, d, 0, ly.bo, x_cls, 0))) return rc;
+      if ((rc = launch_layernorm(t_cls, ly.ln1_w, ly.ln1_b, x_cls, B, d, w->eps, nullptr, stream, ctx_cls))) return rc;  // + bf16 image
+      if ((rc = lin16(ctx_cls, ly.wi, ff_cls, dff, B, nullptr, dff, d, 2, ly.bi, nullptr, 1))) return rc;
+      if ((rc = lin16(ff_cls, ly.wo2, t_cls, d, B, nullptr, d, dff, 0, ly.bo2, x_cls, 0))) return rc;
+      return launch_layernorm(t_cls, ly.ln2_w, ly.ln2_b, out_pooled, B, d, w->eps, nullptr, stream);
     }
-    if ((rc = launch_scatter_rows(x, row_src, rows_dev, M, d, out_hidden, stream))) return rc;
+    if ((rc = lin16(ctx, ly.wo, t, d, M, rows_dev, d, d, 0, ly.bo, x, 0))) return rc;
+    if ((rc = launch_layernorm_dev(t, ly.ln1_w, ly.ln1_b, x, rows_dev, M, d, w->eps, nullptr, stream, x16))) return rc;
+    if ((rc = lin16(x16, ly.wi, ff, dff, M, rows_dev, dff, d, 2, ly.bi, nullptr, 1))) return rc;  // gelu, bf16 out (in the ff buffer)
+    if ((rc = lin16(ff, ly.wo2, t, d, M, rows_dev, d, dff, 0, ly.bo2, x, 0))) return rc;
+    if ((rc = launch_layernorm_dev(t, ly.ln2_w, ly.ln2_b, x, rows_dev, M, d, w->eps, nullptr, stream, last ? nullptr : x16))) return rc;
   }
-  return GDR_OK;
+  return unpack_rows(x, r.plan, B, M, d, out_pooled, out_hidden, "bert_ragged", stream);
+}
+
+// fp16 x 2 split form of the fp32 linears (r06, exploratory: fp32-level error on the fp16 MFMA path; weights as plane rows [N, 2 K]
+// fp16; everything but the linears is the fp32 path's): x (fp32) and its plane rows x16 come from the LayerNorm in front
+static int bert_ragged_f16x2_blocks(const GdrBertWeights* w, const int64_t* mask, int B, int L, float* out_hidden, float* out_pooled,
+                                    int64_t live_rows_hint, const BertBuf& e, const BertRagBuf& r, hipStream_t stream) {
+  const int d = w->d_model, H = w->num_heads, dh = d / H, dff = w->d_ff;
+  const int64_t M = (int64_t)B * L;
+  float *x = e.x, *t = e.t, *qkv = e.qkv, *ctx = e.ctx, *ff = e.ff;
+  float *ctx_cls = r.ctx_cls, *x_cls = r.x_cls, *t_cls = r.t_cls, *ff_cls = r.ff_cls;
+  void* x16 = r.x16;
+  const int32_t* seq_off = r.plan.seq_off;
+  const int64_t* rows_dev = r.plan.rows_dev;
+  int rc;
+  const bool plane_epi = bert_plane_epilogue(*w, M);
+  void* pl_ff = plane_epi ? static_cast<void*>(ff) : r.pl_ff;
+  const int ld_d = 2 * d, ld_ff = 2 * dff;  // fp16 x 2 plane rows
+  AttnArgs at = self_attn_args(B, H, dh, L, 3 * d, mask);
+  attn_f32(at, qkv, ctx), attn_scale(at, 1.0f / sqrtf((float)dh)), attn_packed(at, r.plan);
+  // fp16 x 2 split GEMM over plane rows P [rows, 2 K]; out_planes: the (activated) output leaves as plane rows [rows, 2 N]
+  const GldsLinear glds{"bert_ragged(split)", live_rows_hint, 2, stream};
+  auto gsplit = [&](const void* P, const float* W, void* C, int64_t ldc, int64_t rows, const int64_t* md, int N, int K, int act,
+                    const float* bias, const float* residual, int out_planes) -> int {
+    return linear_glds(glds, P, W, C, ldc, rows, md, N, K, act, bias, residual, out_planes ? 3 : 0);
+  };
+  const bool pooled_only = out_hidden == nullptr;
+  for (int i = 0; i < w->num_layers; ++i) {
+    const GdrBertLayer& ly = w->layers[i];
+    if ((rc = check_bert_layer("bert_ragged", ly, i))) return rc;
+    const bool last = i + 1 == w->num_layers;
+    if ((rc = gsplit(x16, ly.wqkv, qkv, 3 * d, M, rows_dev, 3 * d, d, 0, ly.bqkv, nullptr, 0))) return rc;
+    if ((rc = launch_attention(at, stream))) return rc;
+    if (pooled_only && last) {
+      if ((rc = launch_gather_rows(ctx, seq_off, B, d, ctx_cls, stream))) return rc;
+      if ((rc = launch_gather_rows(x, seq_off, B, d, x_cls, stream))) return rc;
+      if ((rc = launch_split_f32_bf16x3(ctx_cls, d, x16, ld_d, B, d, nullptr, stream, 1))) return rc;
+      if ((rc = gsplit(x16, ly.wo, t_cls, d, B, nullptr, d, d, 0, ly.bo, x_cls, 0))) return rc;
+      if ((rc = launch_layernorm(t_cls, ly.ln1_w, ly.ln1_b, x_cls, B, d, w->eps, nullptr, stream, x16, ld_d))) return rc;
+      if ((rc = gsplit(x16, ly.wi, ff_cls, dff, B, nullptr, dff, d, 2, ly.bi, nullptr, 0))) return rc;
+      if ((rc = launch_split_f32_bf16x3(ff_cls, dff, pl_ff, ld_ff, B, dff, nullptr, stream, 1))) return rc;
+      if ((rc = gsplit(pl_ff, ly.wo2, t_cls, d, B, nullptr, d, dff, 0, ly.bo2, x_cls, 0))) return rc;
+      return launch_layernorm(t_cls, ly.ln2_w, ly.ln2_b, out_pooled, B, d, w->eps, nullptr, stream);
+    }
+    if ((rc = launch_split_f32_bf16x3(ctx, d, x16, ld_d, M, d, rows_dev, stream, 1))) return rc;  // x16 is free: x's planes fed qkv already
+    if ((rc = gsplit(x16, ly.wo, t, d, M, rows_dev, d, d, 0, ly.bo, x, 0))) return rc;
+    if ((rc = launch_layernorm_dev(t, ly.ln1_w, ly.ln1_b, x, rows_dev, M, d, w->eps, nullptr, stream, x16, ld_d))) return rc;
+    if (plane_epi) {
+      if ((rc = gsplit(x16, ly.wi, pl_ff, ld_ff, M, rows_dev, dff, d, 2, ly.bi, nullptr, 1))) return rc;  // GeLU, plane rows out
+    } else {
+      if ((rc = gsplit(x16, ly.wi, ff, dff, M, rows_dev, dff, d, 2, ly.bi, nullptr, 0))) return rc;
+      if ((rc = launch_split_f32_bf16x3(ff, dff, pl_ff, ld_ff, M, dff, rows_dev, stream, 1))) return rc;
+    }
+    if ((rc = gsplit(pl_ff, ly.wo2, t, d, M, rows_dev, d, dff, 0, ly.bo2, x, 0))) return rc;
+    if ((rc = launch_layernorm_dev(t, ly.ln2_w, ly.ln2_b, x, rows_dev, M, d, w->eps, nullptr, stream, last ? nullptr : x16, last ? 0 : ld_d)))
+      return rc;
+  }
+  return unpack_rows(x, r.plan, B, M, d, out_pooled, out_hidden, "bert_ragged", stream);
+}
+
+// the packed entry points: checks, the pack plan, the padded fallback (fp32), then scratch, embedding and its LayerNorm in front of the
+// block sequence.  prec: 0 fp32, 1 bf16 precision mode, 2 the fp16 x 2 split form
+static int bert_ragged_impl(const GdrBertWeights* w, const int64_t* ids, const int64_t* mask, const int64_t* token_type_ids, int B,
+                            int L, float* out_hidden, float* out_pooled, int64_t live_rows_hint, void* workspace,
+                            size_t workspace_bytes, int prec, hipStream_t stream) {
+  const bool bf16 = prec == 1, f16s = prec == 2;
+  if (B == 0) return GDR_OK;
+  GDR_TRY(check_bert_call("bert_ragged", w && ids && mask && workspace && (out_hidden || out_pooled), w, B, L));
+  const int d = w->d_model, H = w->num_heads, dh = d / H, dff = w->d_ff;
+  const int64_t M = (int64_t)B * L;
+  const BertWs ws = bert_ws(*w, M);
+  const BertRagWs rw = bert_rag_ws(*w, B, L);
+  GDR_TRY(check_workspace("bert_ragged", workspace, workspace_bytes, rw.total));
+  char* base = static_cast<char*>(workspace);
+  const BertBuf e = carve_bert(base, ws);
+  const BertRagBuf r = carve_bert_rag(base, rw);
+  GDR_TRY(launch_pack_plan(mask, B, L, r.plan, stream));
+  const int64_t tiles = ((M + 127) / 128) * ((d + 127) / 128);
+  const bool packs = dh == 64 && d % 32 == 0 && dff % 32 == 0;
+  if (bf16 || f16s) {
+    GDR_CHECK_ARG(packs && d % 128 == 0 && dff % 128 == 0,
+                  "bert_ragged(bf16 / split): needs head width 64 and d, d_ff multiples of 128 (d=%d H=%d d_ff=%d)", d, H, dff);
+  } else if (!packs || tiles < 192) {
+    // small problem / other head size: the padded forward, then the rows the packed form would not have computed are zeroed
+    float* full = out_hidden ? out_hidden : e.qkv;  // qkv is dead when the last LayerNorm runs
+    GDR_TRY(gdr_bert_encoder_forward(w, ids, mask, token_type_ids, B, L, full, out_pooled, workspace, ws.total, stream));
+    return out_hidden ? launch_zero_dead_rows(out_hidden, r.plan.seq_len, B, L, d, stream) : GDR_OK;
+  }
+  StreamK sk{};
+  GDR_TRY(tower_streamk(e.scratch, &sk, "bert_ragged", stream));
+  hipLaunchKernelGGL(bert_embed_packed_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, stream, w->word_emb, w->pos_emb, w->type_emb,
+                     ids, token_type_ids, r.plan.row_src, r.plan.rows_dev, L, d / 4, w->vocab_size, w->type_vocab, e.t);
+  GDR_CHECK_LAUNCH("bert_embed_packed_kernel");
+  GDR_TRY(launch_layernorm_dev(e.t, w->emb_ln_w, w->emb_ln_b, e.x, r.plan.rows_dev, M, d, w->eps, nullptr, stream,
+                               (bf16 || f16s) ? r.x16 : nullptr, f16s ? 2 * d : 0));
+  if (f16s) return bert_ragged_f16x2_blocks(w, mask, B, L, out_hidden, out_pooled, live_rows_hint, e, r, stream);
+  if (bf16) return bert_ragged_bf16_blocks(w, mask, B, L, out_hidden, out_pooled, live_rows_hint, e, r, stream);
+  return bert_ragged_f32_blocks(w, mask, B, L, out_hidden, out_pooled, live_rows_hint, e, r, &sk, stream);
 }
 }  // namespace gdr
 

@@ -46,6 +46,11 @@ static inline bool env_flag(const char* name, bool dflt) {
   const char* e = getenv(name);
   return e ? atoi(e) != 0 : dflt;
 }
+// The same for a knob with more than two settings: unset = dflt, otherwise atoi(value); the call site clamps.
+static inline int env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
 
 // Most beams per query of the two-stage path: the beam decode (beam.hip: check_beam_dims) produces up to this many rows per
 // query and the stage behind it (rerank.hip: RR_MAX_BEAMS, k of the long-list select) takes as many.

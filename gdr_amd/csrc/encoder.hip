@@ -11,12 +11,17 @@
 //                 pad mask (1-m)*-1e9 + fp32 softmax + PV                           (:384-413, :290-314)
 // The position bias is never materialised as a [B,H,L,L] tensor: the kernel re-derives it from the
 // [buckets,H] table (layer 0's, shared by all layers as in :790-795).
-#include <stdlib.h>
-
+//
+// Layout of this file.  Five forwards, each with its block body written out: t5_encoder_impl (padded fp32, and the padded bf16 mode
+// with its fused form), ragged_f32_blocks / ragged_bf16_blocks (packed; ragged_impl in front of them does the checks, the two-chain
+// hand-off, the pack plan and the padded fallback) and ragged_split_impl (packed, split-form linears).  What stands around a body —
+// pack plan, stream-K scratch, attention arguments, the LDS-DMA linear's wrapper, the packed exit, the call checks — is tower.h's,
+// shared with bert.hip; the workspace layouts (EncWs, RagWs) and their typed views (carve_enc, carve_rag) are below.
+#include <algorithm>
 #include <mutex>
 #include <vector>
 
-#include "layers.h"
+#include "tower.h"
 
 namespace gdr {
 
@@ -25,21 +30,19 @@ constexpr size_t ENC_SPLITK_BYTES = (size_t)112 << 20;  // <= 384 tail tiles x 4
 static_assert(STREAMK_BYTES <= ENC_SPLITK_BYTES, "stream-K scratch must fit the split-K region");
 constexpr bool ENC_LAST_Q_CLS_DEFAULT = true;  // GDR_ENC_LAST_Q_CLS when unset (DESIGN 4 "Token table": the A/B that decided it)
 
-// the stream-K scratch inside the split-K region of an encoder workspace; flags zeroed once per call
-static int enc_streamk(char* splitk_region, StreamK* sk, hipStream_t stream) {
-  sk->part = reinterpret_cast<float*>(splitk_region);
-  sk->flag = reinterpret_cast<int32_t*>(splitk_region + STREAMK_PART_BYTES);
-  sk->epoch = 0;
-  if (hipMemsetAsync(sk->flag, 0, 512 * sizeof(int32_t), stream) != hipSuccess) {
-    set_error("t5_encoder: memset of the stream-K flags failed");
-    return GDR_EHIP;
-  }
-  return GDR_OK;
-}
-
 struct EncWs {
   size_t off_h, off_nx, off_qkv, off_ctx, off_ff, off_splitk, off_bf, total;
 };
+struct EncBuf {
+  float *h, *nx, *qkv, *ctx, *ff;
+  char* splitk;  // split-K slabs / stream-K scratch (tower_streamk; StreamK::part is its first byte)
+  void* abf;     // bf16 copy of a GEMM's A operand (the bf16 layouts only)
+};
+static EncBuf carve_enc(char* base, const EncWs& ws) {
+  return {reinterpret_cast<float*>(base + ws.off_h),   reinterpret_cast<float*>(base + ws.off_nx), reinterpret_cast<float*>(base + ws.off_qkv),
+          reinterpret_cast<float*>(base + ws.off_ctx), reinterpret_cast<float*>(base + ws.off_ff), base + ws.off_splitk,
+          base + ws.off_bf};
+}
 
 static EncWs enc_ws(const GdrT5Dims& dm, int64_t M, bool bf16 = false) {
   EncWs w{};
@@ -65,41 +68,34 @@ extern "C" size_t gdr_t5_encoder_workspace_bytes(const GdrT5Dims* dims, int B, i
 }
 
 namespace gdr {
+// bf16 precision mode, fused form: every contraction length a multiple of 64, so the LDS-DMA linear serves all four linears of a block
+static bool t5_fused16(const GdrT5EncoderWeights& w) {
+  const GdrT5Dims& dm = w.dims;
+  return dm.d_model % 64 == 0 && (dm.num_heads * dm.d_kv) % 64 == 0 && dm.d_ff % 64 == 0 && (((uintptr_t)w.layers[0].wqkv) & 15) == 0;
+}
+
 static int t5_encoder_impl(const GdrT5EncoderWeights* w, const int64_t* ids, const int64_t* mask, int B, int L,
                            float* out_hidden, float* out_pooled, void* workspace, size_t workspace_bytes, bool bf16,
                            hipStream_t stream) {
   if (B == 0) return GDR_OK;  // empty batch
-  GDR_CHECK_ARG(w && ids && out_hidden && workspace, "t5_encoder: null pointer");
+  GDR_TRY(check_t5_call("t5_encoder", w && ids && out_hidden && workspace, w, B, L, true));
   const GdrT5Dims& dm = w->dims;
-  GDR_CHECK_ARG(B > 0 && L > 0 && L <= T5_MAX_LEN, "t5_encoder: B=%d L=%d (L must be in [1,%d])", B, L, T5_MAX_LEN);
-  GDR_CHECK_ARG(dm.d_model % 4 == 0 && dm.d_kv % 4 == 0 && dm.d_ff % 4 == 0, "t5_encoder: dims must be multiples of 4");
-  GDR_CHECK_ARG(w->embed && w->rel_bias && w->final_ln && w->layers, "t5_encoder: null weight pointer");
   const int64_t M = (int64_t)B * L;
   const EncWs ws = enc_ws(dm, M, bf16);
   GDR_CHECK_ARG(!bf16 || (dm.d_model % 8 == 0 && dm.d_ff % 8 == 0 && (dm.num_heads * dm.d_kv) % 8 == 0),
                 "t5_encoder_bf16: dims must be multiples of 8");
-  if (workspace_bytes < ws.total) {
-    set_error("t5_encoder: workspace %zu < required %zu", workspace_bytes, ws.total);
-    return GDR_ENOSPC;
-  }
-  GDR_CHECK_ARG(((uintptr_t)workspace & 255) == 0, "t5_encoder: workspace must be 256-byte aligned");
-  char* base = static_cast<char*>(workspace);
-  float* h = reinterpret_cast<float*>(base + ws.off_h);
-  float* nx = reinterpret_cast<float*>(base + ws.off_nx);
-  float* qkv = reinterpret_cast<float*>(base + ws.off_qkv);
-  float* ctx = reinterpret_cast<float*>(base + ws.off_ctx);
-  float* ff = reinterpret_cast<float*>(base + ws.off_ff);
-  float* skw = reinterpret_cast<float*>(base + ws.off_splitk);
-  void* abf = base + ws.off_bf;
+  GDR_TRY(check_workspace("t5_encoder", workspace, workspace_bytes, ws.total));
+  const EncBuf e = carve_enc(static_cast<char*>(workspace), ws);
+  float *h = e.h, *nx = e.nx, *qkv = e.qkv, *ctx = e.ctx, *ff = e.ff;
+  void* abf = e.abf;
   StreamK sk{};
-  if (!bf16)
-    if (int rc_ = enc_streamk(base + ws.off_splitk, &sk, stream)) return rc_;
+  if (!bf16) GDR_TRY(tower_streamk(e.splitk, &sk, "t5_encoder", stream));
   // one linear: fp32 as is; in bf16 mode the activation operand is rounded to bf16 into `abf` first (the weights were
   // rounded once by the caller) and the GEMM runs on v_mfma_f32_32x32x16_bf16 with fp32 accumulate / epilogue / output
   auto linear = [&](const float* A, int64_t lda, const float* W, float* C, int64_t ldc, int N, int K, int epi,
                     const float* residual) -> int {
     if (!bf16)
-      return launch_linear_f32_ws(A, lda, W, K, C, ldc, M, N, K, epi, nullptr, residual, ldc, skw, ENC_SPLITK_BYTES, stream, &sk);
+      return launch_linear_f32_ws(A, lda, W, K, C, ldc, M, N, K, epi, nullptr, residual, ldc, sk.part, ENC_SPLITK_BYTES, stream, &sk);
     GDR_CHECK_ARG(lda == K, "t5_encoder_bf16: operand must be dense");
     int rc_ = launch_cast_f32_bf16(A, abf, M * (int64_t)K, stream);
     if (rc_) return rc_;
@@ -110,46 +106,25 @@ static int t5_encoder_impl(const GdrT5EncoderWeights* w, const int64_t* ids, con
   int rc = launch_embed(w->embed, ids, M, d, dm.vocab_size, h, stream);  // modeling_t5.py:725
   if (rc) return rc;
 
-  AttnArgs at{};
-  at.q = qkv, at.k = qkv + inner, at.v = qkv + 2 * inner, at.out = ctx;
-  at.ldq = at.ldk = at.ldv = 3 * inner, at.ldo = inner;
-  at.q_bstride = at.k_bstride = at.o_bstride = L;
-  at.B = B, at.H = H, at.dk = dk, at.Lq = L, at.Lk = L;
-  at.q_pos0 = 0, at.scale = 1.0f;
-  at.rel_bias = w->rel_bias, at.bidirectional = 1, at.num_buckets = dm.rel_buckets;
-  at.lut = make_bucket_lut(dm.rel_buckets / 2, dm.rel_max_distance);
-  at.key_mask = mask, at.mask_bstride = L, at.causal = 0, at.causal_neg_inf = 0;
-  at.kv_rows = nullptr, at.kv_group = 1;
+  // bf16 mode, fused form: the producers write the bf16 operand of the next linear directly — RMSNorm, the attention context
+  // and the ReLU epilogue of wi — instead of fp32 + a cast pass.  Rounding points are the same as in the cast form.
+  const bool fused16 = bf16 && t5_fused16(*w);
+  // d_kv = 64 (the MFMA attention form): q, k, v leave the linear as bf16 and are widened inside the attention kernel
+  const bool qkv16 = fused16 && dk == 64 && L <= 128;
+  AttnArgs at = self_attn_args(B, H, dk, L, 3 * inner, mask);
+  attn_f32(at, qkv, ctx), attn_t5_bias(at, w->rel_bias, dm);
+  if (qkv16) attn_qkv_bf16(at, qkv);
+  if (fused16) attn_ctx_bf16(at, abf);  // ctx as bf16 [M, inner] (nx is dead)
 
-  // bf16 mode, fused form (every contraction length a multiple of 64, so the LDS-DMA linear serves all four): the
-  // producers write the bf16 operand of the next linear directly — RMSNorm, the attention context and the ReLU
-  // epilogue of wi — instead of fp32 + a cast pass.  Rounding points are the same as in the cast form.
-  const bool fused16 = bf16 && d % 64 == 0 && inner % 64 == 0 && dm.d_ff % 64 == 0 && (((uintptr_t)w->layers[0].wqkv) & 15) == 0;
+  const GldsLinear glds{"t5_encoder_bf16", -1, 0, stream};
   auto lin16 = [&](const void* A, const float* W, float* C, int64_t ldc, int N, int K, int act, const float* residual,
-                   int out_bf16) -> int {
-    ProfScope prof(PROF_LINEAR, 2.0 * (double)M * (double)N * (double)K, stream);
-    const int rc_ = launch_linear_bf16_glds(A, K, W, K, C, ldc, M, N, K, 0, residual != nullptr, act, nullptr, residual, ldc,
-                                            out_bf16, stream);
-    if (rc_ > 0) {
-      set_error("t5_encoder_bf16: shape not served by the LDS-DMA linear");
-      return GDR_EINVAL;
-    }
-    return rc_;
-  };
+                   int out_bf16) -> int { return linear_glds(glds, A, W, C, ldc, M, nullptr, N, K, act, nullptr, residual, out_bf16); };
   for (int i = 0; i < dm.num_layers; ++i) {
     const GdrT5EncLayer& ly = w->layers[i];
     GDR_CHECK_ARG(ly.ln_attn && ly.wqkv && ly.wo && ly.ln_ff && ly.wi && ly.wo_ff, "t5_encoder: layer %d null weight", i);
     if (fused16) {
       if ((rc = launch_rmsnorm_bf16(h, ly.ln_attn, abf, M, d, dm.eps, stream))) return rc;
-      // d_kv = 64 (the MFMA attention form): q, k, v leave the linear as bf16 and are widened inside the attention kernel
-      const bool qkv16 = dk == 64 && L <= 128;
       if ((rc = lin16(abf, ly.wqkv, qkv, 3 * inner, 3 * inner, d, 0, nullptr, qkv16 ? 1 : 0))) return rc;
-      if (qkv16) {
-        const __bf16* q16 = reinterpret_cast<const __bf16*>(qkv);
-        at.q = reinterpret_cast<const float*>(q16), at.k = reinterpret_cast<const float*>(q16 + inner);
-        at.v = reinterpret_cast<const float*>(q16 + 2 * inner), at.qkv_bf16 = 1;
-      }
-      at.out_bf16 = abf;  // ctx as bf16 [M, inner] (nx is dead)
       if ((rc = launch_attention(at, stream))) return rc;
       if ((rc = lin16(abf, ly.wo, h, d, d, inner, 0, h, 0))) return rc;
       if ((rc = launch_rmsnorm_bf16(h, ly.ln_ff, abf, M, d, dm.eps, stream))) return rc;
@@ -188,23 +163,29 @@ extern "C" int gdr_t5_encoder_forward(const GdrT5EncoderWeights* w, const int64_
 // The row count is a device-side value (the mask lives on the device): grids are sized for B*L and kernels read the count,
 // so the call stays free of host synchronisation.
 namespace gdr {
-struct RagWs {
-  size_t seq_len, seq_off, row_src, rows_total, ctx_cls, h_cls, nx_cls, ff_cls, total;
+struct RagWs {  // behind an EncWs (bf16 layout): the pack plan, then the CLS rows of a pooled-only call's last block
+  PackPlanWs plan;
+  size_t ctx_cls, h_cls, nx_cls, ff_cls, total;
+};
+struct RagBuf {
+  PackPlan plan;
+  float *ctx_cls, *h_cls, *nx_cls, *ff_cls;  // [B, inner], [B, d], [B, d], [B, d_ff]; the bf16 mode keeps bf16 rows in all but h_cls
 };
 static RagWs rag_ws(const GdrT5Dims& dm, int B, int L, size_t base) {
   RagWs r{};
   const size_t inner = (size_t)dm.num_heads * dm.d_kv;
-  size_t o = base;
-  r.seq_len = o, o += align_up((size_t)B * 4, 256);
-  r.seq_off = o, o += align_up((size_t)(B + 1) * 4, 256);
-  r.row_src = o, o += align_up((size_t)B * L * 4, 256);
-  r.rows_total = o, o += 256;
+  r.plan = pack_plan_ws(B, L, base);
+  size_t o = r.plan.end;
   r.ctx_cls = o, o += align_up((size_t)B * inner * 4, 256);
   r.h_cls = o, o += align_up((size_t)B * dm.d_model * 4, 256);
   r.nx_cls = o, o += align_up((size_t)B * dm.d_model * 4, 256);
   r.ff_cls = o, o += align_up((size_t)B * dm.d_ff * 4, 256);
   r.total = o;
   return r;
+}
+static RagBuf carve_rag(char* base, const RagWs& r) {
+  return {carve_pack_plan(base, r.plan), reinterpret_cast<float*>(base + r.ctx_cls), reinterpret_cast<float*>(base + r.h_cls),
+          reinterpret_cast<float*>(base + r.nx_cls), reinterpret_cast<float*>(base + r.ff_cls)};
 }
 // The packed form needs the d_kv = 64 attention kernel.  ragged_packs: a 128x128 tile grid that fills the chip without
 // split-K (the narrowest linear has N = d_model) — the un-split forms, with the pooled-only tail on the CLS rows.
@@ -331,157 +312,81 @@ extern "C" size_t gdr_t5_encoder_ragged_workspace_bytes(const GdrT5Dims* dims, i
 }
 
 namespace gdr {
-static int ragged_impl(const GdrT5EncoderWeights* w, const int64_t* ids, const int64_t* mask, int B, int L, float* out_hidden,
-                       float* out_pooled, int64_t live_rows_hint, void* workspace, size_t workspace_bytes, bool bf16,
-                       hipStream_t stream, const EncChain* chain) {
-  if (B == 0) return GDR_OK;
-  GDR_CHECK_ARG(w && ids && mask && workspace && (out_hidden || out_pooled), "t5_encoder_ragged: null pointer");
+// ---- packed form of the bf16 precision mode: the producers write the bf16 operand of the next linear (RMSNorm, the attention
+//      context, the ReLU epilogue of wi); same rounding points as gdr_t5_encoder_forward_bf16, rows independent.  The CLS buffers
+//      of `r` hold bf16 rows here (all but h_cls).
+static int ragged_bf16_blocks(const GdrT5EncoderWeights* w, const int64_t* ids, const int64_t* mask, int B, int L, float* out_hidden,
+                              float* out_pooled, int64_t live_rows_hint, const EncBuf& e, const RagBuf& r, hipStream_t stream) {
   const GdrT5Dims& dm = w->dims;
-  GDR_CHECK_ARG(B > 0 && L > 0 && L <= T5_MAX_LEN, "t5_encoder_ragged: B=%d L=%d (L must be in [1,%d])", B, L, T5_MAX_LEN);
-  GDR_CHECK_ARG(dm.d_model % 4 == 0 && dm.d_kv % 4 == 0 && dm.d_ff % 4 == 0, "t5_encoder_ragged: dims must be multiples of 4");
-  GDR_CHECK_ARG(w->embed && w->rel_bias && w->final_ln && w->layers, "t5_encoder_ragged: null weight pointer");
   const int64_t M = (int64_t)B * L;
-  const EncWs ws = enc_ws(dm, M, true);
-  const RagWs rw = rag_ws(dm, B, L, ws.total);
-  const size_t required = chain ? rw.total : ragged_bytes(dm, B, L);  // a chain's slice; a call: the documented size
-  if (workspace_bytes < required) {
-    set_error("t5_encoder_ragged: workspace %zu < required %zu", workspace_bytes, required);
-    return GDR_ENOSPC;
-  }
-  GDR_CHECK_ARG(((uintptr_t)workspace & 255) == 0, "t5_encoder_ragged: workspace must be 256-byte aligned");
-  char* base = static_cast<char*>(workspace);
-  if (!chain && !bf16 && !out_hidden && enc_chains_eligible(dm, B, L)) {
-    static const int chains = [] {
-      const char* e = getenv("GDR_ENC_CHAINS");  // exact A/B knob: 1 = one chain, 2 = two half-batch chains in flight
-      return e ? atoi(e) : ENC_CHAINS_DEFAULT;
-    }();
-    static const int stagger = [] {
-      const char* e = getenv("GDR_ENC_CHAIN_STAGGER");  // lab knob: chain B starts behind this many of chain A's linears
-      const int v = e ? atoi(e) : ENC_CHAIN_STAGGER_DEFAULT;
-      return v < 0 ? 0 : v > 3 ? 3 : v;  // block 0 of a chain has three batch linears at least (o, wi, wo)
-    }();
-    if (chains == 2) {
-      if (EncSide* side = enc_side_acquire()) {
-        const int rc2 = ragged_two_chains(w, ids, mask, B, L, out_pooled, live_rows_hint, base, stagger, side, stream);
-        enc_side_release(side);
-        return rc2;
-      }
-    }
-  }
   const int d = dm.d_model, H = dm.num_heads, dk = dm.d_kv, inner = H * dk;
+  float *h = e.h, *nx = e.nx, *qkv = e.qkv, *ff = e.ff, *h_cls = r.h_cls;
+  void *abf = e.abf, *ctx_cls16 = r.ctx_cls, *nx_cls16 = r.nx_cls, *ff_cls16 = r.ff_cls;
+  const int32_t* seq_off = r.plan.seq_off;
+  const int64_t* rows_dev = r.plan.rows_dev;
   int rc;
-  int32_t* seq_len = reinterpret_cast<int32_t*>(base + rw.seq_len);
-  int32_t* seq_off = reinterpret_cast<int32_t*>(base + rw.seq_off);
-  int32_t* row_src = reinterpret_cast<int32_t*>(base + rw.row_src);
-  int64_t* rows_dev = reinterpret_cast<int64_t*>(base + rw.rows_total);
-  if ((rc = launch_pack_plan(mask, B, L, seq_len, seq_off, row_src, rows_dev, stream))) return rc;
-  // bf16 precision mode: the packed form exists for the fused producer chain only (every contraction a multiple of 64)
-  const bool fused16 = bf16 && d % 64 == 0 && inner % 64 == 0 && dm.d_ff % 64 == 0 && (((uintptr_t)w->layers[0].wqkv) & 15) == 0;
-  const bool big = ragged_packs(dm, B, L);
-  const bool small = !big && !bf16 && ragged_packs_small(dm, B, L);
-  if ((!big && !small) || (bf16 && !fused16)) {
-    // small problem / other head size: the padded forward, then the rows that the packed form would not have computed
-    // are zeroed so that the output contract does not depend on which form ran
-    float* full = out_hidden ? out_hidden : reinterpret_cast<float*>(base + ws.off_qkv);  // qkv is dead when the final norm runs
-    if ((rc = t5_encoder_impl(w, ids, mask, B, L, full, out_pooled, workspace, ws.total, bf16, stream))) return rc;
-    return out_hidden ? launch_zero_dead_rows(out_hidden, seq_len, B, L, d, stream) : GDR_OK;
+  const GldsLinear glds{"t5_encoder_ragged_bf16", live_rows_hint, 0, stream};
+  auto lin16 = [&](const void* A, const float* W, void* C, int64_t ldc, int64_t rows, const int64_t* md, int N, int K, int act,
+                   const float* residual, int out_bf16) -> int {
+    return linear_glds(glds, A, W, C, ldc, rows, md, N, K, act, nullptr, residual, out_bf16);
+  };
+  if ((rc = launch_embed_packed(w->embed, ids, r.plan.row_src, rows_dev, M, d, dm.vocab_size, h, stream))) return rc;
+  // the packed form always runs a d_kv = 64 MFMA attention: up to 128 tokens on bf16 q / k / v; above, the key-block form with
+  // position bias is fp32 (as the padded form above): the qkv linear stores fp32 and the context still leaves as bf16
+  const bool qkv16 = L <= 128;
+  AttnArgs at = self_attn_args(B, H, dk, L, 3 * inner, mask);
+  if (qkv16)
+    attn_qkv_bf16(at, qkv);
+  else
+    attn_f32(at, qkv, nullptr);
+  attn_ctx_bf16(at, abf), attn_t5_bias(at, w->rel_bias, dm), attn_packed(at, r.plan);
+  const bool pooled_only = out_hidden == nullptr;
+  for (int i = 0; i < dm.num_layers; ++i) {
+    const GdrT5EncLayer& ly = w->layers[i];
+    GDR_CHECK_ARG(ly.ln_attn && ly.wqkv && ly.wo && ly.ln_ff && ly.wi && ly.wo_ff, "t5_encoder_ragged: layer %d null weight", i);
+    if ((rc = launch_rmsnorm_bf16_dev(h, ly.ln_attn, abf, rows_dev, M, d, dm.eps, stream))) return rc;
+    if ((rc = lin16(abf, ly.wqkv, qkv, 3 * inner, M, rows_dev, 3 * inner, d, 0, nullptr, qkv16 ? 1 : 0))) return rc;  // q,k,v: bf16 up to 128 tokens, fp32 above
+    if ((rc = launch_attention(at, stream))) return rc;  // ctx -> abf as bf16 [rows, inner]
+    if (pooled_only && i == dm.num_layers - 1) {
+      // bf16 rows are inner/2 (d/2, d_ff/2) floats wide for the row mover
+      if ((rc = launch_gather_rows(static_cast<const float*>(abf), seq_off, B, inner / 2, static_cast<float*>(ctx_cls16), stream)))
+        return rc;
+      if ((rc = launch_gather_rows(h, seq_off, B, d, h_cls, stream))) return rc;
+      if ((rc = lin16(ctx_cls16, ly.wo, h_cls, d, B, nullptr, d, inner, 0, h_cls, 0))) return rc;
+      if ((rc = launch_rmsnorm_bf16(h_cls, ly.ln_ff, nx_cls16, B, d, dm.eps, stream))) return rc;
+      if ((rc = lin16(nx_cls16, ly.wi, ff_cls16, dm.d_ff, B, nullptr, dm.d_ff, d, 1, nullptr, 1))) return rc;
+      if ((rc = lin16(ff_cls16, ly.wo_ff, h_cls, d, B, nullptr, d, dm.d_ff, 0, h_cls, 0))) return rc;
+      return launch_rmsnorm(h_cls, w->final_ln, out_pooled, B, d, dm.eps, nullptr, 1, stream);
+    }
+    if ((rc = lin16(abf, ly.wo, h, d, M, rows_dev, d, inner, 0, h, 0))) return rc;
+    if ((rc = launch_rmsnorm_bf16_dev(h, ly.ln_ff, abf, rows_dev, M, d, dm.eps, stream))) return rc;
+    if ((rc = lin16(abf, ly.wi, ff, dm.d_ff, M, rows_dev, dm.d_ff, d, 1, nullptr, 1))) return rc;  // relu, bf16 out (in the ff buffer)
+    if ((rc = lin16(ff, ly.wo_ff, h, d, M, rows_dev, d, dm.d_ff, 0, h, 0))) return rc;
   }
-  if (bf16) {
-    // ---- packed form of the bf16 precision mode: the producers write the bf16 operand of the next linear (RMSNorm, the
-    //      attention context, the ReLU epilogue of wi); same rounding points as gdr_t5_encoder_forward_bf16, rows independent
-    float* h = reinterpret_cast<float*>(base + ws.off_h);
-    float* nx = reinterpret_cast<float*>(base + ws.off_nx);
-    float* qkv = reinterpret_cast<float*>(base + ws.off_qkv);
-    float* ff = reinterpret_cast<float*>(base + ws.off_ff);
-    void* abf = base + ws.off_bf;
-    float* h_cls = reinterpret_cast<float*>(base + rw.h_cls);
-    void* ctx_cls16 = base + rw.ctx_cls;
-    void* nx_cls16 = base + rw.nx_cls;
-    void* ff_cls16 = base + rw.ff_cls;
-    auto lin16 = [&](const void* A, const float* W, float* C, int64_t ldc, int64_t rows, const int64_t* md, int N, int K, int act,
-                     const float* residual, int out_bf16) -> int {
-      ProfScope prof(PROF_LINEAR, 2.0 * (double)(md && live_rows_hint >= 0 ? live_rows_hint : rows) * (double)N * (double)K, stream);
-      const int rc_ = launch_linear_bf16_glds(A, K, W, K, C, ldc, rows, N, K, 0, residual != nullptr, act, nullptr, residual, ldc,
-                                              out_bf16, stream, md);
-      if (rc_ > 0) {
-        set_error("t5_encoder_ragged_bf16: shape not served by the LDS-DMA linear");
-        return GDR_EINVAL;
-      }
-      return rc_;
-    };
-    if ((rc = launch_embed_packed(w->embed, ids, row_src, rows_dev, M, d, dm.vocab_size, h, stream))) return rc;
-    AttnArgs at{};
-    // the packed form always runs a d_kv = 64 MFMA attention: up to 128 tokens on bf16 q / k / v; above, the key-block form with
-    // position bias is fp32 (as the padded form above): the qkv linear stores fp32 and the context still leaves as bf16
-    const bool qkv16 = L <= 128;
-    if (qkv16) {
-      const __bf16* q16 = reinterpret_cast<const __bf16*>(qkv);
-      at.q = reinterpret_cast<const float*>(q16), at.k = reinterpret_cast<const float*>(q16 + inner);
-      at.v = reinterpret_cast<const float*>(q16 + 2 * inner), at.qkv_bf16 = 1;
-    } else {
-      at.q = qkv, at.k = qkv + inner, at.v = qkv + 2 * inner;
-    }
-    at.out = nullptr, at.out_bf16 = abf;
-    at.ldq = at.ldk = at.ldv = 3 * inner, at.ldo = inner;
-    at.q_bstride = at.k_bstride = at.o_bstride = L;
-    at.B = B, at.H = H, at.dk = dk, at.Lq = L, at.Lk = L;
-    at.q_pos0 = 0, at.scale = 1.0f;
-    at.rel_bias = w->rel_bias, at.bidirectional = 1, at.num_buckets = dm.rel_buckets;
-    at.lut = make_bucket_lut(dm.rel_buckets / 2, dm.rel_max_distance);
-    at.key_mask = mask, at.mask_bstride = L, at.causal = 0, at.causal_neg_inf = 0;
-    at.kv_rows = nullptr, at.kv_group = 1;
-    at.seq_off = seq_off, at.seq_len = seq_len;
-    const bool pooled_only = out_hidden == nullptr;
-    for (int i = 0; i < dm.num_layers; ++i) {
-      const GdrT5EncLayer& ly = w->layers[i];
-      GDR_CHECK_ARG(ly.ln_attn && ly.wqkv && ly.wo && ly.ln_ff && ly.wi && ly.wo_ff, "t5_encoder_ragged: layer %d null weight", i);
-      if ((rc = launch_rmsnorm_bf16_dev(h, ly.ln_attn, abf, rows_dev, M, d, dm.eps, stream))) return rc;
-      if ((rc = lin16(abf, ly.wqkv, qkv, 3 * inner, M, rows_dev, 3 * inner, d, 0, nullptr, qkv16 ? 1 : 0))) return rc;  // q,k,v: bf16 up to 128 tokens, fp32 above
-      if ((rc = launch_attention(at, stream))) return rc;  // ctx -> abf as bf16 [rows, inner]
-      if (pooled_only && i == dm.num_layers - 1) {
-        // bf16 rows are inner/2 (d/2, d_ff/2) floats wide for the row mover
-        if ((rc = launch_gather_rows(static_cast<const float*>(abf), seq_off, B, inner / 2, static_cast<float*>(ctx_cls16), stream)))
-          return rc;
-        if ((rc = launch_gather_rows(h, seq_off, B, d, h_cls, stream))) return rc;
-        if ((rc = lin16(ctx_cls16, ly.wo, h_cls, d, B, nullptr, d, inner, 0, h_cls, 0))) return rc;
-        if ((rc = launch_rmsnorm_bf16(h_cls, ly.ln_ff, nx_cls16, B, d, dm.eps, stream))) return rc;
-        if ((rc = lin16(nx_cls16, ly.wi, static_cast<float*>(ff_cls16), dm.d_ff, B, nullptr, dm.d_ff, d, 1, nullptr, 1))) return rc;
-        if ((rc = lin16(ff_cls16, ly.wo_ff, h_cls, d, B, nullptr, d, dm.d_ff, 0, h_cls, 0))) return rc;
-        return launch_rmsnorm(h_cls, w->final_ln, out_pooled, B, d, dm.eps, nullptr, 1, stream);
-      }
-      if ((rc = lin16(abf, ly.wo, h, d, M, rows_dev, d, inner, 0, h, 0))) return rc;
-      if ((rc = launch_rmsnorm_bf16_dev(h, ly.ln_ff, abf, rows_dev, M, d, dm.eps, stream))) return rc;
-      if ((rc = lin16(abf, ly.wi, ff, dm.d_ff, M, rows_dev, dm.d_ff, d, 1, nullptr, 1))) return rc;  // relu, bf16 out (in the ff buffer)
-      if ((rc = lin16(ff, ly.wo_ff, h, d, M, rows_dev, d, dm.d_ff, 0, h, 0))) return rc;
-    }
-    if ((rc = launch_rmsnorm_dev(h, w->final_ln, nx, rows_dev, M, d, dm.eps, stream))) return rc;
-    if (out_pooled && (rc = launch_gather_rows(nx, seq_off, B, d, out_pooled, stream))) return rc;
-    if (out_hidden) {
-      if (hipMemsetAsync(out_hidden, 0, (size_t)M * d * sizeof(float), stream) != hipSuccess) {
-        set_error("t5_encoder_ragged: memset failed");
-        return GDR_EHIP;
-      }
-      if ((rc = launch_scatter_rows(nx, row_src, rows_dev, M, d, out_hidden, stream))) return rc;
-    }
-    return GDR_OK;
-  }
-  float* h = reinterpret_cast<float*>(base + ws.off_h);
-  float* nx = reinterpret_cast<float*>(base + ws.off_nx);
-  float* qkv = reinterpret_cast<float*>(base + ws.off_qkv);
-  float* ctx = reinterpret_cast<float*>(base + ws.off_ctx);
-  float* ff = reinterpret_cast<float*>(base + ws.off_ff);
-  float* ctx_cls = reinterpret_cast<float*>(base + rw.ctx_cls);
-  float* h_cls = reinterpret_cast<float*>(base + rw.h_cls);
-  float* nx_cls = reinterpret_cast<float*>(base + rw.nx_cls);
-  float* ff_cls = reinterpret_cast<float*>(base + rw.ff_cls);
+  if ((rc = launch_rmsnorm_dev(h, w->final_ln, nx, rows_dev, M, d, dm.eps, stream))) return rc;
+  return unpack_rows(nx, r.plan, B, M, d, out_pooled, out_hidden, "t5_encoder_ragged", stream);
+}
+
+// ---- packed fp32 form.  big: the un-split forms (ragged_packs), with the token table, the last block's q on the CLS rows and the
+//      pooled-only tail; otherwise (ragged_packs_small) the forms the padded forward picks for B*L rows, over the live rows only.
+static int ragged_f32_blocks(const GdrT5EncoderWeights* w, const int64_t* ids, const int64_t* mask, int B, int L, float* out_hidden,
+                             float* out_pooled, int64_t live_rows_hint, const EncBuf& e, const RagBuf& r, bool big, const EncChain* chain,
+                             hipStream_t stream) {
+  const GdrT5Dims& dm = w->dims;
+  const int64_t M = (int64_t)B * L;
+  const int d = dm.d_model, H = dm.num_heads, dk = dm.d_kv, inner = H * dk;
+  float *h = e.h, *nx = e.nx, *qkv = e.qkv, *ctx = e.ctx, *ff = e.ff;
+  float *ctx_cls = r.ctx_cls, *h_cls = r.h_cls, *nx_cls = r.nx_cls, *ff_cls = r.ff_cls;
+  const int32_t *seq_off = r.plan.seq_off, *row_src = r.plan.row_src;
+  const int64_t* rows_dev = r.plan.rows_dev;
+  int rc;
   StreamK sk{};
-  if ((rc = enc_streamk(base + ws.off_splitk, &sk, stream))) return rc;
-  float* skw = reinterpret_cast<float*>(base + ws.off_splitk);
+  if ((rc = tower_streamk(e.splitk, &sk, "t5_encoder", stream))) return rc;
   int batch_linears = 0;  // two-chain form: chain A raises chain B's start event behind one of its first linears
   auto linear = [&](const float* A, int64_t lda, const float* W, float* C, int64_t ldc, int N, int K, int epi,
                     const float* residual) -> int {
-    if (small)  // the forms the padded forward picks for B*L rows (split-K / stream-K), over the live rows only
-      return launch_linear_f32_ws(A, lda, W, K, C, ldc, M, N, K, epi, nullptr, residual, ldc, skw, ENC_SPLITK_BYTES, stream, &sk,
+    if (!big)  // the forms the padded forward picks for B*L rows (split-K / stream-K), over the live rows only
+      return launch_linear_f32_ws(A, lda, W, K, C, ldc, M, N, K, epi, nullptr, residual, ldc, sk.part, ENC_SPLITK_BYTES, stream, &sk,
                                   rows_dev, live_rows_hint);
     GDR_TRY(launch_linear_f32_dev(A, lda, W, K, C, ldc, M, rows_dev, N, K, epi, nullptr, residual, ldc, live_rows_hint, stream, &sk,
                                   chain ? chain->grid_cap : 0));
@@ -504,23 +409,12 @@ static int ragged_impl(const GdrT5EncoderWeights* w, const int64_t* ids, const i
     rc = launch_embed_packed(w->embed, ids, row_src, rows_dev, M, d, dm.vocab_size, h, stream);
   if (rc) return rc;
 
-  AttnArgs at{};
-  at.q = qkv, at.k = qkv + inner, at.v = qkv + 2 * inner, at.out = ctx;
-  at.ldq = at.ldk = at.ldv = 3 * inner, at.ldo = inner;
-  at.q_bstride = at.k_bstride = at.o_bstride = L;
-  at.B = B, at.H = H, at.dk = dk, at.Lq = L, at.Lk = L;
-  at.q_pos0 = 0, at.scale = 1.0f;
-  at.rel_bias = w->rel_bias, at.bidirectional = 1, at.num_buckets = dm.rel_buckets;
-  at.lut = make_bucket_lut(dm.rel_buckets / 2, dm.rel_max_distance);
-  at.key_mask = mask, at.mask_bstride = L, at.causal = 0, at.causal_neg_inf = 0;
-  at.kv_rows = nullptr, at.kv_group = 1;
-  at.seq_off = seq_off, at.seq_len = seq_len;
+  AttnArgs at = self_attn_args(B, H, dk, L, 3 * inner, mask);
+  attn_f32(at, qkv, ctx), attn_t5_bias(at, w->rel_bias, dm), attn_packed(at, r.plan);
 
   const bool pooled_only = out_hidden == nullptr && big;
-  static const bool last_q_cls_on = [] {
-    const char* e = getenv("GDR_ENC_LAST_Q_CLS");  // exact A/B knob: 0 = the last block's q for every live row (one qkv launch)
-    return e ? atoi(e) != 0 : ENC_LAST_Q_CLS_DEFAULT;
-  }();
+  // exact A/B knob: 0 = the last block's q for every live row (one qkv launch)
+  static const bool last_q_cls_on = env_flag("GDR_ENC_LAST_Q_CLS", ENC_LAST_Q_CLS_DEFAULT);
   for (int i = 0; i < dm.num_layers; ++i) {
     const GdrT5EncLayer& ly = w->layers[i];
     GDR_CHECK_ARG(ly.ln_attn && ly.wqkv && ly.wo && ly.ln_ff && ly.wi && ly.wo_ff, "t5_encoder_ragged: layer %d null weight", i);
@@ -563,15 +457,49 @@ static int ragged_impl(const GdrT5EncoderWeights* w, const int64_t* ids, const i
   }
   // final_layer_norm over the live rows, then back into the [B,L,d] layout (PAD rows zero) and / or the CLS pool
   if ((rc = launch_rmsnorm_dev(h, w->final_ln, nx, rows_dev, M, d, dm.eps, stream))) return rc;
-  if (out_pooled && (rc = launch_gather_rows(nx, seq_off, B, d, out_pooled, stream))) return rc;
-  if (out_hidden) {
-    if (hipMemsetAsync(out_hidden, 0, (size_t)M * d * sizeof(float), stream) != hipSuccess) {
-      set_error("t5_encoder_ragged: memset failed");
-      return GDR_EHIP;
+  return unpack_rows(nx, r.plan, B, M, d, out_pooled, out_hidden, "t5_encoder_ragged", stream);
+}
+
+// the packed entry points: checks, the two-chain hand-off, the pack plan, then the block sequence of the form that serves the call
+static int ragged_impl(const GdrT5EncoderWeights* w, const int64_t* ids, const int64_t* mask, int B, int L, float* out_hidden,
+                       float* out_pooled, int64_t live_rows_hint, void* workspace, size_t workspace_bytes, bool bf16,
+                       hipStream_t stream, const EncChain* chain) {
+  if (B == 0) return GDR_OK;
+  GDR_TRY(check_t5_call("t5_encoder_ragged", w && ids && mask && workspace && (out_hidden || out_pooled), w, B, L, true));
+  const GdrT5Dims& dm = w->dims;
+  const EncWs ws = enc_ws(dm, (int64_t)B * L, true);
+  const RagWs rw = rag_ws(dm, B, L, ws.total);
+  // a chain's slice; a call: the documented size
+  GDR_TRY(check_workspace("t5_encoder_ragged", workspace, workspace_bytes, chain ? rw.total : ragged_bytes(dm, B, L)));
+  char* base = static_cast<char*>(workspace);
+  if (!chain && !bf16 && !out_hidden && enc_chains_eligible(dm, B, L)) {
+    // exact A/B knob: 1 = one chain, 2 = two half-batch chains in flight
+    static const int chains = env_int("GDR_ENC_CHAINS", ENC_CHAINS_DEFAULT);
+    // lab knob: chain B starts behind this many of chain A's linears; block 0 of a chain has three batch linears at least (o, wi, wo)
+    static const int stagger = std::max(0, std::min(3, env_int("GDR_ENC_CHAIN_STAGGER", ENC_CHAIN_STAGGER_DEFAULT)));
+    if (chains == 2) {
+      if (EncSide* side = enc_side_acquire()) {
+        const int rc2 = ragged_two_chains(w, ids, mask, B, L, out_pooled, live_rows_hint, base, stagger, side, stream);
+        enc_side_release(side);
+        return rc2;
+      }
     }
-    if ((rc = launch_scatter_rows(nx, row_src, rows_dev, M, d, out_hidden, stream))) return rc;
   }
-  return GDR_OK;
+  const EncBuf e = carve_enc(base, ws);
+  const RagBuf r = carve_rag(base, rw);
+  GDR_TRY(launch_pack_plan(mask, B, L, r.plan, stream));
+  const bool big = ragged_packs(dm, B, L);
+  const bool small = !big && !bf16 && ragged_packs_small(dm, B, L);
+  // bf16 precision mode: the packed form exists for the fused producer chain only
+  if ((!big && !small) || (bf16 && !t5_fused16(*w))) {
+    // small problem / other head size: the padded forward, then the rows that the packed form would not have computed
+    // are zeroed so that the output contract does not depend on which form ran
+    float* full = out_hidden ? out_hidden : e.qkv;  // qkv is dead when the final norm runs
+    GDR_TRY(t5_encoder_impl(w, ids, mask, B, L, full, out_pooled, workspace, ws.total, bf16, stream));
+    return out_hidden ? launch_zero_dead_rows(out_hidden, r.plan.seq_len, B, L, dm.d_model, stream) : GDR_OK;
+  }
+  if (bf16) return ragged_bf16_blocks(w, ids, mask, B, L, out_hidden, out_pooled, live_rows_hint, e, r, stream);
+  return ragged_f32_blocks(w, ids, mask, B, L, out_hidden, out_pooled, live_rows_hint, e, r, big, chain, stream);
 }
 }  // namespace gdr
 
@@ -600,10 +528,8 @@ static int ragged_split_impl(const GdrT5EncoderWeights* w, const int64_t* ids, c
   if (B == 0) return GDR_OK;
   GDR_CHECK_ARG(terms == 6 || terms == 3 || terms == 2, "t5_encoder_split: terms must be 6 or 3 (bf16 planes) or 2 (fp16 x 2)");
   const int f16 = terms == 2 ? 1 : 0;
-  GDR_CHECK_ARG(w && ids && mask && workspace && (out_hidden || out_pooled), "t5_encoder_split: null pointer");
+  GDR_TRY(check_t5_call("t5_encoder_split", w && ids && mask && workspace && (out_hidden || out_pooled), w, B, L, false));
   const GdrT5Dims& dm = w->dims;
-  GDR_CHECK_ARG(B > 0 && L > 0 && L <= T5_MAX_LEN, "t5_encoder_split: B=%d L=%d (L must be in [1,%d])", B, L, T5_MAX_LEN);
-  GDR_CHECK_ARG(w->embed && w->rel_bias && w->final_ln && w->layers, "t5_encoder_split: null weight pointer");
   const int d = dm.d_model, H = dm.num_heads, dk = dm.d_kv, inner = H * dk, dff = dm.d_ff;
   GDR_CHECK_ARG(dk == 64 && d % 64 == 0 && inner % 64 == 0 && dff % 64 == 0,
                 "t5_encoder_split: needs d_kv = 64 and d_model, inner, d_ff multiples of 64 (the packed attention and the LDS-DMA linear)");
@@ -611,45 +537,25 @@ static int ragged_split_impl(const GdrT5EncoderWeights* w, const int64_t* ids, c
   const EncWs ws = enc_ws(dm, M, true);
   const RagWs rw = rag_ws(dm, B, L, ws.total);
   const size_t planes_off = rw.total, total = planes_off + split_ws_bytes(dm, M);
-  if (workspace_bytes < total) {
-    set_error("t5_encoder_split: workspace %zu < required %zu", workspace_bytes, total);
-    return GDR_ENOSPC;
-  }
-  GDR_CHECK_ARG(((uintptr_t)workspace & 255) == 0, "t5_encoder_split: workspace must be 256-byte aligned");
+  GDR_TRY(check_workspace("t5_encoder_split", workspace, workspace_bytes, total));
   char* base = static_cast<char*>(workspace);
+  const EncBuf e = carve_enc(base, ws);
+  const RagBuf r = carve_rag(base, rw);
   int rc;
-  int32_t* seq_len = reinterpret_cast<int32_t*>(base + rw.seq_len);
-  int32_t* seq_off = reinterpret_cast<int32_t*>(base + rw.seq_off);
-  int32_t* row_src = reinterpret_cast<int32_t*>(base + rw.row_src);
-  int64_t* rows_dev = reinterpret_cast<int64_t*>(base + rw.rows_total);
-  if ((rc = launch_pack_plan(mask, B, L, seq_len, seq_off, row_src, rows_dev, stream))) return rc;
-  float* h = reinterpret_cast<float*>(base + ws.off_h);
-  float* nx = reinterpret_cast<float*>(base + ws.off_nx);
-  float* qkv = reinterpret_cast<float*>(base + ws.off_qkv);
-  float* ctx = reinterpret_cast<float*>(base + ws.off_ctx);
-  float* ff = reinterpret_cast<float*>(base + ws.off_ff);
-  float* ctx_cls = reinterpret_cast<float*>(base + rw.ctx_cls);
-  float* h_cls = reinterpret_cast<float*>(base + rw.h_cls);
-  float* nx_cls = reinterpret_cast<float*>(base + rw.nx_cls);
-  float* ff_cls = reinterpret_cast<float*>(base + rw.ff_cls);
+  if ((rc = launch_pack_plan(mask, B, L, r.plan, stream))) return rc;
+  float *h = e.h, *nx = e.nx, *qkv = e.qkv, *ctx = e.ctx, *ff = e.ff;
+  float *ctx_cls = r.ctx_cls, *h_cls = r.h_cls, *nx_cls = r.nx_cls, *ff_cls = r.ff_cls;
+  const int32_t* seq_off = r.plan.seq_off;
+  const int64_t* rows_dev = r.plan.rows_dev;
   void* planes = base + planes_off;                                  // d_model / inner wide operands
   void* planes_ff = base + planes_off + split_ws_a_bytes(dm, M);     // the d_ff wide ReLU output of wi
-  static const bool fuse_on = [] {
-    const char* e = getenv("GDR_SPLIT_FUSE");  // A/B knob: 0 = every operand split by a launch of its own (split_f32_bf16x3_kernel)
-    return e ? atoi(e) != 0 : true;
-  }();
+  // A/B knob: 0 = every operand split by a launch of its own (split_f32_bf16x3_kernel)
+  static const bool fuse_on = env_flag("GDR_SPLIT_FUSE", true);
   // the split GEMM over plane rows P [rows, split_row_elems(K)]; out_planes: the output leaves as plane rows (row stride ldc elements)
+  const GldsLinear glds{"t5_encoder_split", live_rows_hint, terms, stream};
   auto gemm = [&](const void* P, const float* W, void* C, int64_t ldc, int64_t rows, const int64_t* md, int N, int K, int act,
                   const float* residual, int out_planes) -> int {
-    const int ld = split_row_elems(K, f16);
-    ProfScope prof(PROF_LINEAR, 2.0 * (double)(md && live_rows_hint >= 0 ? live_rows_hint : rows) * (double)N * (double)K, stream);
-    const int rc_ = launch_linear_bf16_glds(P, ld, W, ld, static_cast<float*>(C), ldc, rows, N, K, 0, residual != nullptr, act, nullptr, residual,
-                                            ldc, out_planes ? (f16 ? 3 : 2) : 0, stream, md, terms);
-    if (rc_ > 0) {
-      set_error("t5_encoder_split: shape not served by the LDS-DMA linear");
-      return GDR_EINVAL;
-    }
-    return rc_;
+    return linear_glds(glds, P, W, C, ldc, rows, md, N, K, act, nullptr, residual, out_planes ? (f16 ? 3 : 2) : 0);
   };
   // one linear over `rows` fp32 rows (md: their device-side count, or null): split the operand into planes, then the split GEMM
   auto linear = [&](const float* A, const float* W, float* C, int64_t ldc, int64_t rows, const int64_t* md, int N, int K, int act,
@@ -664,18 +570,9 @@ static int ragged_split_impl(const GdrT5EncoderWeights* w, const int64_t* ids, c
   const bool fuse = fuse_on && M >= 8192;
   const bool fuse_wi = fuse && linear_bf16_tile_form(M, dff, d, 0, f16 ? 3 : 2, terms) >= 192;
   const int ld_d = split_row_elems(d, f16), ld_ff = split_row_elems(dff, f16);
-  if ((rc = launch_embed_packed(w->embed, ids, row_src, rows_dev, M, d, dm.vocab_size, h, stream))) return rc;
-  AttnArgs at{};
-  at.q = qkv, at.k = qkv + inner, at.v = qkv + 2 * inner, at.out = ctx;
-  at.ldq = at.ldk = at.ldv = 3 * inner, at.ldo = inner;
-  at.q_bstride = at.k_bstride = at.o_bstride = L;
-  at.B = B, at.H = H, at.dk = dk, at.Lq = L, at.Lk = L;
-  at.q_pos0 = 0, at.scale = 1.0f;
-  at.rel_bias = w->rel_bias, at.bidirectional = 1, at.num_buckets = dm.rel_buckets;
-  at.lut = make_bucket_lut(dm.rel_buckets / 2, dm.rel_max_distance);
-  at.key_mask = mask, at.mask_bstride = L, at.causal = 0, at.causal_neg_inf = 0;
-  at.kv_rows = nullptr, at.kv_group = 1;
-  at.seq_off = seq_off, at.seq_len = seq_len;
+  if ((rc = launch_embed_packed(w->embed, ids, r.plan.row_src, rows_dev, M, d, dm.vocab_size, h, stream))) return rc;
+  AttnArgs at = self_attn_args(B, H, dk, L, 3 * inner, mask);
+  attn_f32(at, qkv, ctx), attn_t5_bias(at, w->rel_bias, dm), attn_packed(at, r.plan);
   const bool pooled_only = out_hidden == nullptr;
   for (int i = 0; i < dm.num_layers; ++i) {
     const GdrT5EncLayer& ly = w->layers[i];
@@ -713,15 +610,7 @@ static int ragged_split_impl(const GdrT5EncoderWeights* w, const int64_t* ids, c
     }
   }
   if ((rc = launch_rmsnorm_dev(h, w->final_ln, nx, rows_dev, M, d, dm.eps, stream))) return rc;
-  if (out_pooled && (rc = launch_gather_rows(nx, seq_off, B, d, out_pooled, stream))) return rc;
-  if (out_hidden) {
-    if (hipMemsetAsync(out_hidden, 0, (size_t)M * d * sizeof(float), stream) != hipSuccess) {
-      set_error("t5_encoder_split: memset failed");
-      return GDR_EHIP;
-    }
-    if ((rc = launch_scatter_rows(nx, row_src, rows_dev, M, d, out_hidden, stream))) return rc;
-  }
-  return GDR_OK;
+  return unpack_rows(nx, r.plan, B, M, d, out_pooled, out_hidden, "t5_encoder_split", stream);
 }
 }  // namespace gdr
 
