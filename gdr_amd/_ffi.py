@@ -203,6 +203,14 @@ COMPACT_SIGNATURES = {
     "gdr_rowmask_compact": (_i, [_vp, _i64, _i, _i64, _vp, _i64, _vp, _i64, _vp]),
 }
 
+# name -> (restype, argtypes); every symbol declared in include/gdr_hip_kmeans_seed.h (which gdr_hip.h includes): one greedy
+# k-means++ seeding step over every node of a tree level.  A table of its own, as the header is.
+KMEANS_SEED_SIGNATURES = {
+    "gdr_kmeans_seed_tile": (_i, []),
+    "gdr_kmeans_seed_workspace_bytes": (_sz, [_i, _i, _i]),
+    "gdr_kmeans_seed_dist": (_i, [_vp, _i64, _i, _vp, _i64, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+}
+
 _lib = None
 
 
@@ -222,7 +230,8 @@ def lib():
             # GDR_FFI_NO_TORCH: it never touches a GPU.)
             import torch  # noqa: F401
         l = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(PREFILTER_MASK_SIGNATURES.items()) + list(COMPACT_SIGNATURES.items()):
+        for name, (res, args) in (list(SIGNATURES.items()) + list(PREFILTER_MASK_SIGNATURES.items()) + list(COMPACT_SIGNATURES.items())
+                                  + list(KMEANS_SEED_SIGNATURES.items())):
             fn = getattr(l, name)            # AttributeError if the .so lacks a declared symbol
             fn.restype, fn.argtypes = res, args
         got = l.gdr_abi_version()

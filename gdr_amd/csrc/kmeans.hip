@@ -14,6 +14,9 @@
 //     place their rows at scan value + rank inside the tile.  Nothing depends on arrival order; a child's rows stay ascending.
 //   gdr_kmeans_centroids: the update step over the child CSR the partition writes — member means as a fixed-shape two-stage sum
 //     (below); gdr_cluster_centroids' one sequential chain per cluster made every root round wait ~2 ms for 30 chains.
+//   gdr_kmeans_seed_dist: one greedy k-means++ seeding step over the same (node, tile) work list: fp32 squared
+//     distances of every row to its node's T candidates over one pinned summation tree without fma, per-tile integer potentials
+//     and maxima.  The draws, the prefix sums and the argmin between the steps are torch (gdr_amd/kmeans.py).
 #include "common.h"
 
 namespace gdr {
@@ -367,6 +370,122 @@ __global__ __launch_bounds__(256) void cent_final_kernel(int d4, int S, const in
   }
 }
 
+// ---- k-means++ seeding: one greedy step over every node of a level (include/gdr_hip_kmeans_seed.h) -------------------------------
+// d2(x, c) = sum_j (x_j - c_j)^2 with every operation rounded on its own (no fma) and ONE summation tree per (row, centre): lane j of
+// the 16 lanes of a row takes the 16-byte pieces j, j + 16, ... in order (inside a piece x, y, z, w; a chain from 0), then the xor
+// butterfly 8, 4, 2, 1.  A work item is KS_TILE = 128 row positions: 16 rows per pass, 8 passes kept in registers so that a lane
+// fetches its pieces of the T candidate rows once per 8 rows.  The potentials are integers (order-free): floor(v * 2^(22 - e)).
+constexpr int KS_TILE = 128;
+constexpr int KS_MAX_T = 6;  // 2 + floor(ln 64)
+
+__device__ __forceinline__ void sq_acc(float& acc, const float4 x, const float4 c) {
+#pragma clang fp contract(off)
+  float t = x.x - c.x;
+  acc = acc + t * t;
+  t = x.y - c.y;
+  acc = acc + t * t;
+  t = x.z - c.z;
+  acc = acc + t * t;
+  t = x.w - c.w;
+  acc = acc + t * t;
+}
+
+__device__ __forceinline__ float add_rn(float a, float b) {
+#pragma clang fp contract(off)
+  return a + b;
+}
+
+template <int T>
+__global__ __launch_bounds__(256) void seed_dist_kernel(const float* __restrict__ D, int64_t N, int d4, const int32_t* __restrict__ rows,
+                                                        int64_t n_rows, const int32_t* __restrict__ node_off, int S,
+                                                        const int32_t* __restrict__ work, const int32_t* __restrict__ cand,
+                                                        const float* __restrict__ d2, const int32_t* __restrict__ e_node,
+                                                        float* __restrict__ out_d2, long long* __restrict__ out_pot,
+                                                        float* __restrict__ out_max, int32_t* __restrict__ status) {
+  __shared__ long long s_pot[4][T];
+  __shared__ float s_max[4][T];
+  int node, lo, hi, p0;
+  if (!load_item(work, blockIdx.x, node_off, S, n_rows, node, lo, hi, p0)) {  // block-uniform
+    if (threadIdx.x == 0) atomicOr(status, 2);
+    return;
+  }
+  const int tid = threadIdx.x, g = tid >> 4, j = tid & 15;
+  const int end = min(hi, p0 + KS_TILE);
+  const float4* D4 = reinterpret_cast<const float4*>(D);
+  const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+  int64_t xb[8], cb[T];
+  bool has[T];
+#pragma unroll
+  for (int u = 0; u < 8; ++u) {
+    const int p = p0 + 16 * u + g;
+    const int32_t id = p < end ? rows[p] : -1;
+    xb[u] = (id >= 0 && id < N) ? (int64_t)id * d4 : -1;  // an id outside the corpus reads as a zero row
+  }
+#pragma unroll
+  for (int t = 0; t < T; ++t) {
+    const int32_t id = cand[(int64_t)node * T + t];
+    has[t] = id >= 0;  // a negative candidate: the column is the current d2
+    cb[t] = (id >= 0 && id < N) ? (int64_t)id * d4 : -1;
+  }
+  float acc[8][T];
+#pragma unroll
+  for (int u = 0; u < 8; ++u)
+#pragma unroll
+    for (int t = 0; t < T; ++t) acc[u][t] = 0.f;
+  for (int c = j; c < d4; c += 16) {
+    float4 cv[T], x[8];
+#pragma unroll
+    for (int t = 0; t < T; ++t) cv[t] = cb[t] >= 0 ? D4[cb[t] + c] : zero4;
+#pragma unroll
+    for (int u = 0; u < 8; ++u) x[u] = xb[u] >= 0 ? D4[xb[u] + c] : zero4;
+#pragma unroll
+    for (int u = 0; u < 8; ++u)
+#pragma unroll
+      for (int t = 0; t < T; ++t) sq_acc(acc[u][t], x[u], cv[t]);
+  }
+#pragma unroll
+  for (int m = 8; m >= 1; m >>= 1)
+#pragma unroll
+    for (int u = 0; u < 8; ++u)
+#pragma unroll
+      for (int t = 0; t < T; ++t) acc[u][t] = add_rn(acc[u][t], __shfl_xor(acc[u][t], m));
+
+  // lane j < T of a row's 16 lanes owns column j: it stores the column and sums its weights over the lane's 8 rows
+  const int e = max(-1000, min(1000, e_node[node]));
+  const double scale = __longlong_as_double((long long)(1045 - e) << 52);  // 2^(22 - e)
+  long long pot = 0;
+  float mx = 0.f;
+#pragma unroll
+  for (int u = 0; u < 8; ++u) {
+    const int p = p0 + 16 * u + g;
+    if (p < end) {
+      const float cur = d2[p];
+#pragma unroll
+      for (int t = 0; t < T; ++t) {
+        if (j == t) {
+          const float v = has[t] ? fminf(cur, acc[u][t]) : cur;
+          out_d2[(int64_t)p * T + t] = v;
+          pot += (long long)fmin((double)v * scale, 4194303.0);  // v >= 0: the conversion truncates = floor; v >= 2^e saturates
+          mx = fmaxf(mx, v);
+        }
+      }
+    }
+  }
+  pot += __shfl_xor(pot, 16);
+  pot += __shfl_xor(pot, 32);
+  mx = fmaxf(mx, __shfl_xor(mx, 16));
+  mx = fmaxf(mx, __shfl_xor(mx, 32));
+  if ((tid & 63) < T) {
+    s_pot[tid >> 6][tid & 63] = pot;
+    s_max[tid >> 6][tid & 63] = mx;
+  }
+  __syncthreads();
+  if (tid < T) {
+    out_pot[(int64_t)blockIdx.x * T + tid] = s_pot[0][tid] + s_pot[1][tid] + s_pot[2][tid] + s_pot[3][tid];
+    out_max[(int64_t)blockIdx.x * T + tid] = fmaxf(fmaxf(s_max[0][tid], s_max[1][tid]), fmaxf(s_max[2][tid], s_max[3][tid]));
+  }
+}
+
 }  // namespace
 }  // namespace gdr
 
@@ -496,5 +615,48 @@ extern "C" int gdr_kmeans_centroids(const float* D, int64_t N, int d, const int3
   hipLaunchKernelGGL(cent_final_kernel, dim3((unsigned)(((int64_t)n_children * S + 3) / 4)), dim3(256), 0, stream, d4, S,
                      child_offsets, (int)n_rows, n_children, partial, out_centroids, out_counts);
   GDR_CHECK_LAUNCH("kmeans cent_final_kernel");
+  return GDR_OK;
+}
+
+extern "C" int gdr_kmeans_seed_tile(void) { return gdr::KS_TILE; }
+
+// the step keeps no scratch: every partial it forms is one of its outputs
+extern "C" size_t gdr_kmeans_seed_workspace_bytes(int n_nodes, int n_work, int n_trials) { return 0; }
+
+extern "C" int gdr_kmeans_seed_dist(const float* D, int64_t N, int d, const int32_t* rows, int64_t n_rows, const int32_t* node_offsets,
+                                    int n_nodes, const int32_t* work, int n_work, const int32_t* cand, int n_trials, const float* d2,
+                                    const int32_t* e, float* out_cand_d2, int64_t* out_pot, float* out_max, int32_t* out_status,
+                                    void* workspace, size_t workspace_bytes, void* stream_) {
+  using namespace gdr;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  GDR_CHECK_ARG(D && rows && node_offsets && work && cand && d2 && e && out_cand_d2 && out_pot && out_max && out_status,
+                "kmeans_seed_dist: null pointer");
+  GDR_CHECK_ARG(N > 0 && N < ((int64_t)1 << 31), "kmeans_seed_dist: N=%lld does not fit int32 doc ids", (long long)N);
+  GDR_CHECK_ARG(n_rows > 0 && n_rows < ((int64_t)1 << 31) && n_nodes > 0 && n_work > 0,
+                "kmeans_seed_dist: bad size n_rows=%lld n_nodes=%d n_work=%d", (long long)n_rows, n_nodes, n_work);
+  GDR_CHECK_ARG(d > 0 && d % 4 == 0 && d <= KM_MAX_D, "kmeans_seed_dist: d=%d (needs d %% 4 == 0, 4 <= d <= %d)", d, KM_MAX_D);
+  GDR_CHECK_ARG(n_trials >= 1 && n_trials <= KS_MAX_T, "kmeans_seed_dist: n_trials=%d (needs 1 <= n_trials <= %d)", n_trials, KS_MAX_T);
+  GDR_CHECK_ARG(((uintptr_t)D & 15) == 0, "kmeans_seed_dist: D must be 16-byte aligned");
+  (void)workspace;
+  (void)workspace_bytes;
+  if (hipMemsetAsync(out_status, 0, sizeof(int32_t), stream) != hipSuccess) {
+    set_error("kmeans_seed_dist: hipMemsetAsync failed");
+    return GDR_EHIP;
+  }
+  const int d4 = d / 4;
+  long long* pot = reinterpret_cast<long long*>(out_pot);
+#define GDR_SEED_LAUNCH(T)                                                                                                          \
+  hipLaunchKernelGGL(seed_dist_kernel<T>, dim3((unsigned)n_work), dim3(256), 0, stream, D, N, d4, rows, n_rows, node_offsets, n_nodes, \
+                     work, cand, d2, e, out_cand_d2, pot, out_max, out_status)
+  switch (n_trials) {
+    case 1: GDR_SEED_LAUNCH(1); break;
+    case 2: GDR_SEED_LAUNCH(2); break;
+    case 3: GDR_SEED_LAUNCH(3); break;
+    case 4: GDR_SEED_LAUNCH(4); break;
+    case 5: GDR_SEED_LAUNCH(5); break;
+    default: GDR_SEED_LAUNCH(6); break;
+  }
+#undef GDR_SEED_LAUNCH
+  GDR_CHECK_LAUNCH("kmeans seed_dist_kernel");
   return GDR_OK;
 }

@@ -3,8 +3,12 @@ Data_process/NQ_dataset/kmeans/kmeans.py (recursive sklearn k-means, `--k 30 --c
 
 The tree is built level by level: every open node of a level runs Lloyd's algorithm in the same launches
 (gdr_kmeans_assign -> gdr_kmeans_partition -> gdr_kmeans_centroids per round).  The level loop, the restarts and the seeding
-live here in torch; there is no per-node Python loop.  tests/kmeans_ref.py restates the semantics in numpy.
+live here in torch; there is no per-node Python loop.  tests/kmeans_ref.py restates the semantics in numpy.  A split is seeded
+from hashed member rows (init="hash", the default) or by the greedy k-means++ rule (init="k-means++": one gdr_kmeans_seed_dist
+launch per step for the whole level; tests/kmeans_pp_ref.py restates it bit for bit).
 """
+import math
+
 import numpy as np
 import torch
 
@@ -32,18 +36,25 @@ def _lsr(z, s):
     return (z >> s) & ((1 << (64 - s)) - 1)      # torch's >> on int64 is arithmetic
 
 
-def mix_keys(seed, restart, level, doc_ids):
-    """63-bit keys (int64 >= 0) of doc_ids (int64 tensor): splitmix64(prefix(seed, restart, level) ^ doc_id) >> 1 — integer
-    operations only (int64 multiplication wraps), so the device agrees with tests/kmeans_ref.mix bit for bit."""
-    h = _splitmix64_int(int(seed) & _M64)
-    h = _splitmix64_int(h ^ (int(restart) & _M64))
-    h = _splitmix64_int(h ^ (int(level) & _M64))
-    z = doc_ids ^ _s64(h)
+def _splitmix64_t(z):
+    """splitmix64 of an int64 tensor (bit patterns; int64 multiplication wraps)."""
     z = z + _s64(0x9E3779B97F4A7C15)
     z = (z ^ _lsr(z, 30)) * _s64(0xBF58476D1CE4E5B9)
     z = (z ^ _lsr(z, 27)) * _s64(0x94D049BB133111EB)
-    z = z ^ _lsr(z, 31)
-    return _lsr(z, 1)
+    return z ^ _lsr(z, 31)
+
+
+def _prefix(seed, restart, level):
+    """The part of a key that does not depend on the document (tests/kmeans_ref.mix_prefix), as an int64 bit pattern."""
+    h = _splitmix64_int(int(seed) & _M64)
+    h = _splitmix64_int(h ^ (int(restart) & _M64))
+    return _s64(_splitmix64_int(h ^ (int(level) & _M64)))
+
+
+def mix_keys(seed, restart, level, doc_ids):
+    """63-bit keys (int64 >= 0) of doc_ids (int64 tensor): splitmix64(prefix(seed, restart, level) ^ doc_id) >> 1 — integer
+    operations only (int64 multiplication wraps), so the device agrees with tests/kmeans_ref.mix bit for bit."""
+    return _lsr(_splitmix64_t(doc_ids ^ _prefix(seed, restart, level)), 1)
 
 
 class DocIds:
@@ -99,12 +110,110 @@ def _lloyd(D, rows, node_off, cent, k, max_iter, work_a, work_p, ws, ws_c):
     return labels, score, rounds, status, cent
 
 
+INITS = ("hash", "k-means++")
+_W_MAX = float((1 << 22) - 1)
+
+
+def n_trials(k):
+    """Candidates per greedy k-means++ step: sklearn's 2 + int(log(k)) (2 .. 6 for k = 2 .. 64)."""
+    return 2 + int(math.floor(math.log(k)))
+
+
+def _weights(d2, e, node_of):
+    """floor(min(d2 * 2^(22 - e), 2^22 - 1)) as int64: the exact power of two is built from its float64 bit pattern."""
+    scale = ((1045 - e.to(torch.int64)) << 52).view(torch.float64)
+    return torch.floor(torch.clamp(d2.double() * scale[node_of], max=_W_MAX)).to(torch.int64)
+
+
+def _seed_plusplus(D, rows, node_off, off64, sizes, node_of, hashed, k, seed, restart, level, work, status):
+    """Greedy k-means++ seeds of every node of the level (tests/kmeans_pp_ref.seed_node) -> doc ids int64[S, k].
+    hashed int64[S, k] are the hashed rule's ids: the first centre, every centre of a node of <= k members, and the centres a node
+    of zero potential still lacks.  One gdr_kmeans_seed_dist launch per step for the whole level; the integer prefix sums, the
+    draws and the argmin are torch; no read-back."""
+    dev = D.device
+    n, S, T = rows.numel(), sizes.numel(), n_trials(k)
+    lo, hi = off64[:-1], off64[1:]
+    a = _splitmix64_t(rows[lo].to(torch.int64) ^ _prefix(seed, restart, level))   # per node: its smallest doc id under the prefix
+    tile_node = work[:, 0].to(torch.int64)
+    tile_off = torch.cat([lo.new_zeros(1), torch.cumsum(torch.bincount(tile_node, minlength=S), 0)])
+    trials = torch.arange(T, device=dev)
+    # the draws depend on (seed, restart, level, node, step, trial) alone: all k - 1 steps at once, as float64 u * 2^-53 (exact)
+    steps = torch.arange(1, k, device=dev)
+    u = _lsr(_splitmix64_t(a[None, :, None] ^ ((steps << 8)[:, None, None] | trials[None, None, :])), 11).double() * 2.0 ** -53
+
+    def node_max(v):                                                             # per-tile maxima -> per node (a max is order-free)
+        return torch.zeros((S,), dtype=torch.float32, device=dev).scatter_reduce_(0, tile_node, v, "amax")
+
+    picks, zero = [], []
+    cand = torch.full((S, T), -1, dtype=torch.int32, device=dev)
+    cand[:, 0] = hashed[:, 0].to(torch.int32)
+    d2 = torch.full((n,), float("inf"), dtype=torch.float32, device=dev)
+    e = torch.zeros((S,), dtype=torch.int32, device=dev)
+    cd, _pot, mx, st = ops.kmeans_seed_dist(D, rows, node_off, cand, d2, e, work=work)
+    status |= st
+    d2, dmax = cd[:, 0].contiguous(), node_max(mx[:, 0])
+    for step in range(1, k):
+        e = torch.frexp(dmax).exponent.to(torch.int32)
+        w = _weights(d2, e, node_of)
+        cs = torch.cumsum(w, 0)                                                  # int64: exact in any order
+        base = cs[lo] - w[lo]
+        pot = cs[hi - 1] - base
+        thr = torch.floor(u[step - 1] * pot.double()[:, None]).to(torch.int64)
+        thr = torch.minimum(thr, pot[:, None] - 1).clamp_(min=0)
+        pos = torch.searchsorted(cs, (base[:, None] + thr).reshape(-1), right=True).view(S, T)
+        pos = torch.minimum(torch.maximum(pos, lo[:, None]), hi[:, None] - 1)    # a node of zero potential draws nothing
+        cand = rows[pos]
+        cd, tpot, mx, st = ops.kmeans_seed_dist(D, rows, node_off, cand, d2, e, work=work)
+        status |= st
+        cp = torch.cat([tpot.new_zeros((1, T)), torch.cumsum(tpot, 0)])
+        pots = cp[tile_off[1:]] - cp[tile_off[:-1]]                              # [S, T], < 2^53
+        best = (pots * 8 + trials[None, :]).min(1).values & 7                    # the smallest potential, ties to the lower trial
+        picks.append(cand.gather(1, best[:, None])[:, 0])
+        zero.append(pot == 0)
+        d2 = cd.gather(1, best[node_of][:, None])[:, 0].contiguous()
+        dmax = node_max(mx.gather(1, best[tile_node][:, None])[:, 0])
+    greedy = torch.stack(picks, 1).to(torch.int64)
+    keep = (sizes <= k)[:, None] | torch.stack(zero, 1)                          # a small node; a node whose potential was 0
+    return torch.cat([hashed[:, :1], torch.where(keep, hashed[:, 1:], greedy)], 1)
+
+
+def seed_level(D, rows, node_off, k, seed=7, restart=0, level=0, init="hash", work=None):
+    """Doc ids int64[S, k] of the initial centres of every node of a level (rows int32[n], ascending inside a node; node_off
+    int32[S+1]) and the kernels' status word int32[1].  "hash": the k smallest (key, doc id) of the node, a node of m < k members
+    repeats them (centre j = member j mod m).  "k-means++": the greedy rule from there (_seed_plusplus); work is the level's work
+    list over gdr_kmeans_seed_tile() rows (built here when absent)."""
+    if init not in INITS:
+        raise GdrError(f"seed_level: init={init!r} (one of {', '.join(INITS)})")
+    dev = rows.device
+    n, S = rows.numel(), node_off.numel() - 1
+    off64 = node_off.to(torch.int64)
+    sizes = off64[1:] - off64[:-1]
+    node_of = torch.repeat_interleave(torch.arange(S, device=dev), sizes, output_size=n)
+    rows64 = rows.to(torch.int64)
+    # rows are ascending inside a node, so two stable sorts order them by (node, key, doc id)
+    keys = mix_keys(seed, restart, level, rows64)
+    o1 = torch.sort(keys, stable=True).indices
+    o2 = torch.sort(node_of[o1], stable=True).indices
+    order = o1[o2]                                                    # positions, grouped by node, by (key, id) inside it
+    j = torch.arange(k, device=dev)[None, :] % sizes[:, None]
+    ids = rows64[order[off64[:-1, None] + j]]
+    status = torch.zeros((1,), dtype=torch.int32, device=dev)
+    if init == "k-means++":
+        if work is None:
+            work = ops.kmeans_worklist(node_off, lib().gdr_kmeans_seed_tile())
+        ids = _seed_plusplus(D, rows, node_off, off64, sizes, node_of, ids, k, seed, restart, level, work, status)
+    return ids, status
+
+
 def build_docids(D, k=30, c=30, seed=7, max_iter=300, n_init=DEFAULT_N_INIT, max_depth=8, init_centroids=None, kary=None,
-                 output_vocab_size=None):
+                 output_vocab_size=None, init="hash"):
     """Hierarchical k-means ids of the corpus D fp32[N, d] (device) -> DocIds.  k children per split (2..64), leaves of <= c
     docs, n_init restarts per split (the smaller inertia wins), ids of at most max_depth digits (GdrError beyond).
     init_centroids fp32[k, d] replaces the seeding of the root (one restart there).  With kary the ids must be printable in
-    that scheme: max(k, c) <= output_vocab_size."""
+    that scheme: max(k, c) <= output_vocab_size.  init: "hash" seeds a split from its k members with the smallest hashed keys;
+    "k-means++" runs the greedy k-means++ rule on the device — Lloyd, the restarts and the id rules are the same."""
+    if init not in INITS:
+        raise GdrError(f"build_docids: init={init!r} (one of {', '.join(INITS)})")
     if not isinstance(D, torch.Tensor) or not D.is_cuda:
         raise GdrError("build_docids: D must be a CUDA (ROCm) tensor; there is no CPU path")
     if D.dtype != torch.float32:
@@ -131,6 +240,7 @@ def build_docids(D, k=30, c=30, seed=7, max_iter=300, n_init=DEFAULT_N_INIT, max
     dev = D.device
     ws, ws_c = ops.Workspace(dev), ops.Workspace(dev)
     ta, tp = lib().gdr_kmeans_assign_tile(), lib().gdr_kmeans_partition_tile()
+    ts = lib().gdr_kmeans_seed_tile()
     xn2 = torch.empty((N,), dtype=torch.float64, device=dev)
     for lo in range(0, N, 1 << 16):
         x = D[lo:lo + (1 << 16)].double()
@@ -150,6 +260,7 @@ def build_docids(D, k=30, c=30, seed=7, max_iter=300, n_init=DEFAULT_N_INIT, max
         sizes = off64[1:] - off64[:-1]
         node_of = torch.repeat_interleave(torch.arange(S, device=dev), sizes, output_size=n)
         work_a, work_p = ops.kmeans_worklist(node_off, ta), ops.kmeans_worklist(node_off, tp)
+        work_s = work_a if ts == ta else ops.kmeans_worklist(node_off, ts)
         rows64 = rows.to(torch.int64)
         xn2_rows = xn2[rows64]
         best_labels = best_inertia = None
@@ -160,13 +271,9 @@ def build_docids(D, k=30, c=30, seed=7, max_iter=300, n_init=DEFAULT_N_INIT, max
             if level == 0 and init_centroids is not None:
                 cent = init_centroids.contiguous().clone()
             else:
-                # the k smallest (key, doc id) of every node: rows are ascending inside a node, so two stable sorts do it
-                keys = mix_keys(seed, r, level, rows64)
-                o1 = torch.sort(keys, stable=True).indices
-                o2 = torch.sort(node_of[o1], stable=True).indices
-                order = o1[o2]                                        # positions, grouped by node, by (key, id) inside it
-                j = torch.arange(k, device=dev)[None, :] % sizes[:, None]
-                cent = D[rows64[order[(off64[:-1, None] + j).reshape(-1)]]].contiguous()
+                ids, st = seed_level(D, rows, node_off, k, seed, r, level, init, work_s)
+                status |= st
+                cent = D[ids.reshape(-1)].contiguous()
             labels, score, rounds, st, cent = _lloyd(D, rows, node_off, cent, k, max_iter, work_a, work_p, ws, ws_c)
             status |= st
             rounds_max = max(rounds_max, rounds)
@@ -211,7 +318,7 @@ def build_docids(D, k=30, c=30, seed=7, max_iter=300, n_init=DEFAULT_N_INIT, max
         level_inertia = float(best_inertia.sum().item())
         total_inertia += level_inertia
         open_child = ~leaf
-        levels.append({"level": level, "nodes": S, "rows": n, "restarts": restarts, "rounds": rounds_max,
+        levels.append({"level": level, "nodes": S, "rows": n, "restarts": restarts, "rounds": rounds_max, "init": init,
                        "inertia": level_inertia, "leaves": int((leaf & (csize > 0)).sum().item())})
         rows = crow[~pos_leaf].contiguous()
         osz = csize[open_child]

@@ -1309,6 +1309,52 @@ def kmeans_centroids(D, child_offsets, rows, workspace=None):
     return cent, counts
 
 
+KMEANS_SEED_MAX_T = 6
+
+
+def kmeans_seed_dist(D, rows, node_offsets, cand, d2, e, work=None, workspace=None):
+    """gdr_kmeans_seed_dist: one greedy k-means++ step over the nodes of a level (include/gdr_hip_kmeans_seed.h).  cand int32[S, T]
+    candidate doc ids (negative: none), d2 fp32[n] distance to the nearest chosen centre (+inf before the first), e int32[S] the
+    nodes' exponents; work = kmeans_worklist(node_offsets, gdr_kmeans_seed_tile()) (built here when absent) -> (cand_d2 fp32[n, T] =
+    min(d2, distance to the candidate), pot int64[n_work, T] and max fp32[n_work, T] per tile, status int32[1]).  No read-back."""
+    _need_cuda(D, rows, node_offsets, cand, d2, e, work)
+    if D.dtype != torch.float32:
+        raise _ffi.GdrError(f"kmeans_seed_dist: the corpus must be float32, got {D.dtype} (a bf16 corpus is not supported)")
+    if D.dim() != 2 or D.shape[1] % 4 or not 4 <= D.shape[1] <= KMEANS_MAX_D:
+        raise _ffi.GdrError(f"kmeans_seed_dist: d={D.shape[-1]} (needs d % 4 == 0, 4 <= d <= {KMEANS_MAX_D})")
+    if D.shape[0] >= 1 << 31:
+        raise _ffi.GdrError(f"kmeans_seed_dist: N={D.shape[0]} does not fit int32 doc ids")
+    for t in (rows, node_offsets, cand, e):
+        if t.dtype != torch.int32:
+            raise _ffi.GdrError(f"kmeans_seed_dist: expected int32, got {t.dtype}")
+    if rows.numel() == 0 or node_offsets.numel() < 2:
+        raise _ffi.GdrError("kmeans_seed_dist: empty level")
+    D = _f32c(D)
+    n, S = rows.numel(), node_offsets.numel() - 1
+    if cand.dim() != 2 or cand.shape[0] != S or not 1 <= cand.shape[1] <= KMEANS_SEED_MAX_T:
+        raise _ffi.GdrError(f"kmeans_seed_dist: cand {tuple(cand.shape)}, expected ({S}, 1..{KMEANS_SEED_MAX_T})")
+    if d2.dtype != torch.float32 or d2.numel() != n or e.numel() != S:
+        raise _ffi.GdrError("kmeans_seed_dist: d2 must be float32[n] and e int32[n_nodes]")
+    T = cand.shape[1]
+    if work is None:
+        work = kmeans_worklist(node_offsets, lib().gdr_kmeans_seed_tile())
+    if work.dtype != torch.int32 or work.dim() != 2 or work.shape[1] != 2 or work.shape[0] == 0:
+        raise _ffi.GdrError("kmeans_seed_dist: work must be int32[n_work, 2]")
+    dev = D.device
+    W = work.shape[0]
+    cand_d2 = torch.empty((n, T), dtype=torch.float32, device=dev)
+    pot = torch.empty((W, T), dtype=torch.int64, device=dev)
+    mx = torch.empty((W, T), dtype=torch.float32, device=dev)
+    status = torch.empty((1,), dtype=torch.int32, device=dev)
+    need = lib().gdr_kmeans_seed_workspace_bytes(S, W, T)
+    ws = (workspace or Workspace(dev)).get(need) if need else None
+    check(lib().gdr_kmeans_seed_dist(ptr(D), D.shape[0], D.shape[1], ptr(rows.contiguous()), n, ptr(node_offsets.contiguous()), S,
+                                     ptr(work.contiguous()), W, ptr(cand.contiguous()), T, ptr(d2.contiguous()), ptr(e.contiguous()),
+                                     ptr(cand_d2), ptr(pot), ptr(mx), ptr(status), ptr(ws), ws.numel() if ws is not None else 0,
+                                     stream_ptr()), "gdr_kmeans_seed_dist")
+    return cand_d2, pot, mx, status
+
+
 def relative_bucket_table(bidirectional, num_buckets, max_distance, qlen, klen):
     """Host table int32[qlen,klen] from the same routine the attention kernels use (no GPU needed)."""
     buf = (C.c_int32 * (qlen * klen))()

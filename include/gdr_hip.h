@@ -863,5 +863,7 @@ int gdr_beam_search_table(const float* table, int B, int out_vocab, int num_beam
 #include "gdr_hip_prefilter_mask.h"
 /* Compacting a live corpus (the plan, the row mover, the id and row-bitmap remaps): declared in a header of their own. */
 #include "gdr_hip_compact.h"
+/* k-means++ seeding of the hierarchical docid build (one greedy step over every node of a level): declared in a header of its own. */
+#include "gdr_hip_kmeans_seed.h"
 
 #endif /* GDR_HIP_H */

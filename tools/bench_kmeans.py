@@ -3,11 +3,12 @@
 k = c = 30 — the shape of the reference's `kmeans.py --k 30 --c 30` run behind the bert_k30_c30 ids.
 
 Reports the three kernels of one root-level Lloyd round (assign / partition / centroids: ms between device events around many
-rounds, against bytes / 5.5 TB/s), the same for the second level (k nodes), the whole build (s, per-level rounds and time) and,
-if sklearn is importable here, the reference's recipe (MiniBatchKMeans / KMeans, n_init = 100) on a sub-sample, extrapolated and
-labelled so.  Prints one JSON line last.
+rounds, against bytes / 5.5 TB/s), the same for the second level (k nodes), one k-means++ seeding step of the root, the whole build
+for every --init in turn in one process (s, per-level rounds, the tree's inertia, and the seeding's share of the build from event
+pairs around every seeding of a level) and, if sklearn is importable here, the reference's recipe (MiniBatchKMeans / KMeans,
+n_init = 100) on a sub-sample, extrapolated and labelled so.  Prints one JSON line last.
 
-    python tools/bench_kmeans.py [--rows 334314] [--n_init 4] [--reps 20] [--cpu_rows 20000]
+    python tools/bench_kmeans.py [--rows 334314] [--n_init 4] [--init hash k-means++] [--reps 20] [--cpu_rows 20000]
 """
 import argparse
 import json
@@ -61,6 +62,42 @@ def round_kernels(D, rows, off, cent, k, reps):
             "largest_child": int(sizes.max().item())}, (crow, coff)
 
 
+def seed_step(D, rows, off, k, reps):
+    """ms of one gdr_kmeans_seed_dist step over the level (T candidates per node) and its byte floor (the rows once)."""
+    n, S, T = rows.numel(), off.numel() - 1, kmeans.n_trials(k)
+    work = ops.kmeans_worklist(off, lib().gdr_kmeans_seed_tile())
+    cand = rows[(off[:-1, None].long() + torch.arange(T, device=D.device)[None, :] % (off[1:] - off[:-1])[:, None].long())]
+    d2 = torch.full((n,), float("inf"), device=D.device)
+    e = torch.zeros((S,), dtype=torch.int32, device=D.device)
+    t = timed_dev(lambda: ops.kmeans_seed_dist(D, rows, off, cand, d2, e, work=work), reps)
+    return {"nodes": S, "rows": n, "trials": T, "seed_dist_ms": round(t, 4),
+            "seed_dist_floor_ms": round((n * D.shape[1] * 4 + n * 4 * (1 + T)) / HBM * 1e3, 4)}
+
+
+class SeedingClock:
+    """Event pairs around every kmeans.seed_level call of a build: the device time the seeding of the levels takes."""
+
+    def __enter__(self):
+        self.pairs, self.orig = [], kmeans.seed_level
+
+        def timed(*a, **kw):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            out = self.orig(*a, **kw)
+            e1.record()
+            self.pairs.append((e0, e1))
+            return out
+        kmeans.seed_level = timed
+        return self
+
+    def __exit__(self, *exc):
+        kmeans.seed_level = self.orig
+
+    def ms(self):
+        torch.cuda.synchronize()
+        return sum(a.elapsed_time(b) for a, b in self.pairs)
+
+
 def cpu_reference(X, k, c, threads):
     """The reference's recipe through sklearn on X: seconds for the root split and for the whole recursion."""
     from sklearn.cluster import KMeans, MiniBatchKMeans
@@ -95,6 +132,7 @@ def main():
     ap.add_argument("--k", type=int, default=30)
     ap.add_argument("--c", type=int, default=30)
     ap.add_argument("--n_init", type=int, default=kmeans.DEFAULT_N_INIT)
+    ap.add_argument("--init", nargs="+", default=list(kmeans.INITS), choices=kmeans.INITS, help="the seedings to build with, in turn")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--cpu_rows", type=int, default=20000, help="sub-sample for the sklearn line (0: skip)")
     ap.add_argument("--max_depth", type=int, default=12)
@@ -121,14 +159,22 @@ def main():
     cent2 = D[crow.long()[(off2[:-1, None].long() + torch.arange(k, device=dev)[None, :] % (off2[1:] - off2[:-1])[:, None].long()).reshape(-1)]]
     res["level1_round"], _ = round_kernels(D, crow, off2, cent2.contiguous(), k, a.reps)
     res["level1_round"]["nodes"] = S2
+    res["root_seed_step"] = seed_step(D, rows, off, k, a.reps)
+    res["level1_seed_step"] = seed_step(D, crow, off2, k, a.reps)
     for n_init in sorted({1, a.n_init}):
-        kmeans.build_docids(D[:20000].contiguous(), k=k, c=a.c, n_init=1, max_depth=a.max_depth)     # warm-up
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        out = kmeans.build_docids(D, k=k, c=a.c, seed=7, n_init=n_init, max_depth=a.max_depth)
-        torch.cuda.synchronize()
-        res[f"build_n_init_{n_init}"] = {"seconds": round(time.perf_counter() - t0, 3), "clusters": len(out.cluster_index.names),
-                                         "depth": int(out.lengths.max()), "inertia": out.inertia, "levels": out.levels}
+        for init in a.init:
+            kmeans.build_docids(D[:20000].contiguous(), k=k, c=a.c, n_init=1, max_depth=a.max_depth, init=init)     # warm-up
+            torch.cuda.synchronize()
+            with SeedingClock() as clock:
+                t0 = time.perf_counter()
+                out = kmeans.build_docids(D, k=k, c=a.c, seed=7, n_init=n_init, max_depth=a.max_depth, init=init)
+                torch.cuda.synchronize()
+                sec = time.perf_counter() - t0
+                seed_ms = clock.ms()
+            key = f"build_n_init_{n_init}" + ("" if init == "hash" else "_kmeans_pp")
+            res[key] = {"init": init, "seconds": round(sec, 3), "seeding_ms": round(seed_ms, 2), "seeding_share": round(seed_ms / 1e3 / sec, 4),
+                        "clusters": len(out.cluster_index.names), "depth": int(out.lengths.max()), "inertia": out.inertia,
+                        "levels": out.levels}
     if a.cpu_rows:
         try:
             import sklearn  # noqa: F401
