@@ -1,5 +1,5 @@
 // Full self-attention for 128 < L <= 512 at d_kv = 64 (the doc tower at the reference's passage length, Data_process/NQ_dataset/bert/
-// bert_NQ.sh:5 MAX_LEN=512).  The one-pass kernels of layers.hip keep the whole K and V of a (sequence, head) in LDS and give one wave
+// bert_NQ.sh:5 MAX_LEN=512).  The one-pass kernels of attention.hip keep the whole K and V of a (sequence, head) in LDS and give one wave
 // to each 16-query tile: 2 * L * 68 * 4 B is 278 KB at L = 512.  Here a workgroup owns a block of ATTN_LONG_QB = 128 query rows of one
 // (sequence, head) — 8 waves x 16 queries — and walks K / V from key 0 in blocks of ATTN_LONG_KB = 64 keys that are staged through a
 // double-buffered LDS image, with an online softmax: per query row a running maximum m and a running sum l; when a block raises the
@@ -21,24 +21,12 @@
 // Staging: the next block's global loads are issued into registers before the current block's MFMAs and written to the other LDS
 // buffer after them (one workgroup barrier per block); K / V rows past the sequence's end are read from its last row (finite values,
 // probability 0).
-#include "layers.h"
+#include "attention.h"
 
 namespace gdr {
 
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-
 constexpr int ATTN_LONG_QB = 128;  // query rows per workgroup (8 waves x 16); ops.ATTN_LONG_QUERY_BLOCK states it for the tests
 constexpr int ATTN_LONG_KB = 64;   // keys per staged block; ops.ATTN_LONG_KEY_BLOCK
-
-__device__ __forceinline__ uint2 long_pack_bf16x4(float a, float b, float c, float d) {
-  union {
-    __bf16 h[4];
-    uint2 u;
-  } o;
-  o.h[0] = (__bf16)a, o.h[1] = (__bf16)b, o.h[2] = (__bf16)c, o.h[3] = (__bf16)d;  // v_cvt_pk_bf16_f32: RNE
-  return o.u;
-}
 
 // ---------------------------------------------------------------------------------------------------------------- fp32 q / k / v
 // LDS: 2 buffers x (K[64][68] + V[64][68] + mask[64]) floats = 70 144 B (two workgroups per CU).  Row stride 68 floats: the
@@ -59,20 +47,6 @@ __device__ __forceinline__ uint2 long_pack_bf16x4(float a, float b, float c, flo
 // key 0 of every visited block is real, so the running maximum stays finite); LONG_PLAIN keeps the -1e9 it shipped with.
 enum { LONG_PLAIN = 0, LONG_T5_SELF = 1, LONG_T5_CROSS = 2 };
 constexpr int ATTN_LONG_MAXL = 512;  // RelT spans the offsets of this many positions; launch_attention bounds Lk by it
-
-// T5's bucket of (query position - key position) = n, modeling_t5.py:242-288 through the 128-entry table
-__device__ __forceinline__ int long_rel_bucket(const AttnArgs& a, int n) {
-  int bucket = 0;
-  if (a.bidirectional) {
-    if (n < 0) {
-      bucket = a.num_buckets >> 1;
-      n = -n;
-    }
-  } else if (n < 0) {
-    n = 0;
-  }
-  return bucket + a.lut.v[n < 127 ? n : 127];
-}
 
 template <int FORM>
 __global__ __launch_bounds__(512) void attention_long_f32_kernel(const AttnArgs a) {
@@ -130,7 +104,7 @@ __global__ __launch_bounds__(512) void attention_long_f32_kernel(const AttnArgs 
     mk_raw = 1;
     if (tid < KB && a.key_mask && kb * KB + tid < L) mk_raw = a.key_mask[(int64_t)kvb * a.mask_bstride + kb * KB + tid];
     if (CROSS && a.rel_bias && tid < KB && kb * KB + tid < L)
-      kbias = a.rel_bias[long_rel_bucket(a, a.q_pos0 - (kb * KB + tid)) * a.H + h];
+      kbias = a.rel_bias[rel_bucket(a, a.q_pos0 - (kb * KB + tid)) * a.H + h];
   };
   auto store_block = [&](int kb, float* buf) {
     *reinterpret_cast<float4*>(buf + sr * DS + 4 * sc) = kst0;
@@ -148,7 +122,7 @@ __global__ __launch_bounds__(512) void attention_long_f32_kernel(const AttnArgs 
   if (FORM == LONG_T5_SELF) {
     float* RelT = smem + 2 * BUF;  // RelT[(q - k) + 511]
     for (int c = tid; c < 2 * ATTN_LONG_MAXL - 1; c += 512)
-      RelT[c] = a.rel_bias[long_rel_bucket(a, c - (ATTN_LONG_MAXL - 1)) * a.H + h];
+      RelT[c] = a.rel_bias[rel_bucket(a, c - (ATTN_LONG_MAXL - 1)) * a.H + h];
   }
 #pragma unroll
   for (int jj = 0; jj < DK / 16; ++jj) qv[jj].x *= a.scale, qv[jj].y *= a.scale, qv[jj].z *= a.scale, qv[jj].w *= a.scale;
@@ -171,20 +145,7 @@ __global__ __launch_bounds__(512) void attention_long_f32_kernel(const AttnArgs 
       const float* Vs = cur + KB * DS;
       const float* Mk = cur + 2 * KB * DS;
       f32x4_t st[KB / 16];
-#pragma unroll
-      for (int t = 0; t < KB / 16; ++t) st[t] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-      // S^T tiles: A = K rows (keys), B = Q rows; d permuted inside chunks of 16 identically on both operands
-#pragma unroll
-      for (int jj = 0; jj < DK / 16; ++jj) {
-#pragma unroll
-        for (int t = 0; t < KB / 16; ++t) {
-          const float4 kv = *reinterpret_cast<const float4*>(Ks + (16 * t + c16) * DS + 4 * q4 + 16 * jj);
-          st[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(kv.x, qv[jj].x, st[t], 0, 0, 0);
-          st[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(kv.y, qv[jj].y, st[t], 0, 0, 0);
-          st[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(kv.z, qv[jj].z, st[t], 0, 0, 0);
-          st[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(kv.w, qv[jj].w, st[t], 0, 0, 0);
-        }
-      }
+      score_tiles_f32<KB / 16>(st, Ks, qv, KB, KB / 16, c16, q4);  // every row of the staged block is a finite K row
       // additive mask, block maximum: this lane holds keys 16t + 4q4 + r of its query
       float bm = -INFINITY;
 #pragma unroll
@@ -197,8 +158,7 @@ __global__ __launch_bounds__(512) void attention_long_f32_kernel(const AttnArgs 
         st[t][0] += mk.x, st[t][1] += mk.y, st[t][2] += mk.z, st[t][3] += mk.w;
         bm = fmaxf(bm, fmaxf(fmaxf(st[t][0], st[t][1]), fmaxf(st[t][2], st[t][3])));
       }
-      bm = fmaxf(bm, __shfl_xor(bm, 16));
-      bm = fmaxf(bm, __shfl_xor(bm, 32));
+      bm = quad_max(bm);
       const float m_new = fmaxf(m, bm);          // finite: a masked key adds -1e9, and the -inf tail cells of the T5 forms follow real key 0 of the block
       const float alpha = __expf(m - m_new);     // first block: exp(-inf) = 0 over l = 0, o = 0
       m = m_new;
@@ -231,20 +191,13 @@ __global__ __launch_bounds__(512) void attention_long_f32_kernel(const AttnArgs 
     __syncthreads();
   }
   if (!active) return;
-  l += __shfl_xor(l, 16);
-  l += __shfl_xor(l, 32);
-  const float inv = 1.0f / l;
+  const float inv = 1.0f / quad_sum(l);
   const int i = q0 + 16 * w + c16;
   if (i < Lq) {
 #pragma unroll
-    for (int dt = 0; dt < DK / 16; ++dt) {
-      const int64_t off = (orow0 + i) * a.ldo + h * DK + 16 * dt + 4 * q4;
-      const float4 ov = make_float4(o[dt][0] * inv, o[dt][1] * inv, o[dt][2] * inv, o[dt][3] * inv);
-      if (a.out_bf16)
-        *reinterpret_cast<uint2*>(static_cast<__bf16*>(a.out_bf16) + off) = long_pack_bf16x4(ov.x, ov.y, ov.z, ov.w);
-      else
-        *reinterpret_cast<float4*>(a.out + off) = ov;
-    }
+    for (int dt = 0; dt < DK / 16; ++dt)
+      store_ctx4(a, (orow0 + i) * a.ldo + h * DK + 16 * dt + 4 * q4,
+                 make_float4(o[dt][0] * inv, o[dt][1] * inv, o[dt][2] * inv, o[dt][3] * inv));
   }
 }
 
@@ -254,8 +207,6 @@ __global__ __launch_bounds__(512) void attention_long_f32_kernel(const AttnArgs 
 // (p = hi + mid + lo, truncations of the successive remainders), fp32 accumulate, bf16 output rows.  Because the split is exact, the
 // running maximum of the online softmax adds no rounding point of its own.
 // LDS: 2 buffers x (K[64][144 B] + V^T[64 d][152 B] + mask[64] floats) = 38 400 B.
-__device__ __forceinline__ uint32_t long_bf16_trunc_bits(float x) { return __float_as_uint(x) & 0xffff0000u; }
-
 __global__ __launch_bounds__(512) void attention_long_bf16_kernel(const AttnArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_b[];
   constexpr int DK = 64, KS = 144, VS = 152, KB = ATTN_LONG_KB, QB = ATTN_LONG_QB, BUF = KB * KS + DK * VS + KB * 4;
@@ -340,8 +291,7 @@ __global__ __launch_bounds__(512) void attention_long_bf16_kernel(const AttnArgs
         st[t][0] += mk.x, st[t][1] += mk.y, st[t][2] += mk.z, st[t][3] += mk.w;
         bm = fmaxf(bm, fmaxf(fmaxf(st[t][0], st[t][1]), fmaxf(st[t][2], st[t][3])));
       }
-      bm = fmaxf(bm, __shfl_xor(bm, 16));
-      bm = fmaxf(bm, __shfl_xor(bm, 32));
+      bm = quad_max(bm);
       const float m_new = fmaxf(m, bm);
       const float alpha = __expf(m - m_new);
       m = m_new;
@@ -361,19 +311,10 @@ __global__ __launch_bounds__(512) void attention_long_bf16_kernel(const AttnArgs
       uint4 ph[2], pm[2], pl[2];
 #pragma unroll
       for (int u = 0; u < 2; ++u) {
-        uint32_t hi[8], mid[8], lo[8];
+        float p[8];
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const float p = st[2 * u + (e >> 2)][e & 3];
-          const uint32_t h1 = long_bf16_trunc_bits(p);
-          const float r1 = p - __uint_as_float(h1);
-          const uint32_t h2 = long_bf16_trunc_bits(r1);
-          const float r2 = r1 - __uint_as_float(h2);
-          hi[e] = h1 >> 16, mid[e] = h2 >> 16, lo[e] = long_bf16_trunc_bits(r2) >> 16;
-        }
-        ph[u] = make_uint4(hi[0] | (hi[1] << 16), hi[2] | (hi[3] << 16), hi[4] | (hi[5] << 16), hi[6] | (hi[7] << 16));
-        pm[u] = make_uint4(mid[0] | (mid[1] << 16), mid[2] | (mid[3] << 16), mid[4] | (mid[5] << 16), mid[6] | (mid[7] << 16));
-        pl[u] = make_uint4(lo[0] | (lo[1] << 16), lo[2] | (lo[3] << 16), lo[4] | (lo[5] << 16), lo[6] | (lo[7] << 16));
+        for (int e = 0; e < 8; ++e) p[e] = st[2 * u + (e >> 2)][e & 3];
+        split_bf16x3(p, ph[u], pm[u], pl[u]);
       }
 #pragma unroll
       for (int dt = 0; dt < DK / 16; ++dt) {
@@ -394,20 +335,13 @@ __global__ __launch_bounds__(512) void attention_long_bf16_kernel(const AttnArgs
     __syncthreads();
   }
   if (!active) return;
-  l += __shfl_xor(l, 16);
-  l += __shfl_xor(l, 32);
-  const float inv = 1.0f / l;
+  const float inv = 1.0f / quad_sum(l);
   const int i = q0 + 16 * w + c16;
   if (i < L) {
 #pragma unroll
-    for (int dt = 0; dt < DK / 16; ++dt) {
-      const int64_t off = (orow0 + i) * a.ldo + h * DK + 16 * dt + 4 * q4;
-      const float4 ov = make_float4(o[dt][0] * inv, o[dt][1] * inv, o[dt][2] * inv, o[dt][3] * inv);
-      if (a.out_bf16)
-        *reinterpret_cast<uint2*>(static_cast<__bf16*>(a.out_bf16) + off) = long_pack_bf16x4(ov.x, ov.y, ov.z, ov.w);
-      else
-        *reinterpret_cast<float4*>(a.out + off) = ov;
-    }
+    for (int dt = 0; dt < DK / 16; ++dt)
+      store_ctx4(a, (orow0 + i) * a.ldo + h * DK + 16 * dt + 4 * q4,
+                 make_float4(o[dt][0] * inv, o[dt][1] * inv, o[dt][2] * inv, o[dt][3] * inv));
   }
 }
 

@@ -192,6 +192,18 @@ size_t sim_rows_workspace_bytes(int B, int64_t cap, int k);
 int launch_sim_rows(const void* Q, int B, const void* D, int64_t N, int d, int k, int32_t idx_offset, float* out_val, int32_t* out_idx,
                     int32_t* status, const uint32_t* bitmaps, int64_t qstride, int64_t cap, void* ws, bool bf16, hipStream_t stream);
 
+// MFMA operand / accumulator vectors, and four floats rounded to bf16 (the operand of a bf16-mode linear)
+typedef float f32x4_t __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
+__device__ __forceinline__ uint2 pack_bf16x4(float a, float b, float c, float d) {
+  union {
+    __bf16 h[4];
+    uint2 u;
+  } o;
+  o.h[0] = (__bf16)a, o.h[1] = (__bf16)b, o.h[2] = (__bf16)c, o.h[3] = (__bf16)d;  // v_cvt_pk_bf16_f32: RNE
+  return o.u;
+}
+
 // Sums / maxima over the 64 lanes as the xor butterfly 32, 16, 8, 4, 2, 1 (every lane ends with the total).  The four steps
 // inside a row of 16 lanes are DPP row rotations: after the xor-16 step the values have period 16, so "rotate by 8" pairs lane i
 // with lane i ^ 8 exactly; the values then have period 8 inside the row, so "rotate by 4" meets the partner "xor 4" would

@@ -25,6 +25,7 @@
 #include <mutex>
 #include <vector>
 
+#include "attention.h"
 #include "beam.h"
 #include "layers.h"
 

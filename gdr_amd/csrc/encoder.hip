@@ -6,7 +6,7 @@
 //   qkv / o / wi / wo   gemm_f32.hip on v_mfma_f32_32x32x2_f32 (persistent form at encoder batch sizes); q,k,v fused into
 //                 one [3*inner,d] GEMM,
 //                 residual add and ReLU fused into the GEMM epilogues        (:360-364,:413,:182-185,:199)
-//   attn          layers.hip  attention_mfma16_kernel (d_kv = 64: S^T = K·Q^T and O^T = V^T·P^T on v_mfma_f32_16x16x4_f32, one
+//   attn          attention.hip  attention_mfma16_kernel (d_kv = 64: S^T = K·Q^T and O^T = V^T·P^T on v_mfma_f32_16x16x4_f32, one
 //                 wave per 16-query tile; above 128 tokens attention_long.hip's key-block form) or attention_kernel (any d_kv): QKᵀ (no 1/sqrt(d)) + bucketed relative bias +
 //                 pad mask (1-m)*-1e9 + fp32 softmax + PV                           (:384-413, :290-314)
 // The position bias is never materialised as a [B,H,L,L] tensor: the kernel re-derives it from the

@@ -35,7 +35,6 @@ namespace gdr {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 
 constexpr int BM = 128, BN = 128, BK = 32;
 constexpr int LDS_STRIDE = BK + 4;  // floats; 144 B rows, 16-B aligned

@@ -3,6 +3,7 @@
 // self-attention arguments, the wrapper of the LDS-DMA linear, the way out of a packed forward, the checks of a call — is here, once.
 // Plain structs and functions: nothing here launches a kernel that the forward calling it did not launch at the same point before.
 #pragma once
+#include "attention.h"
 #include "layers.h"
 
 namespace gdr {

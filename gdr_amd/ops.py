@@ -1505,7 +1505,7 @@ class T5EncoderHandle:
 
 
 BERT_MAX_LEN = 512             # the doc tower's entry points take L <= min(BERT_MAX_LEN, max_pos) (csrc/bert.hip)
-T5_MAX_LEN = 512               # input tokens per sequence in every T5 encoder form and in generate() (csrc/layers.h T5_MAX_LEN)
+T5_MAX_LEN = 512               # input tokens per sequence in every T5 encoder form and in generate() (csrc/attention.h T5_MAX_LEN)
 ATTN_LONG_QUERY_BLOCK = 128    # above 128 tokens (csrc/attention_long.hip): query rows per workgroup ...
 ATTN_LONG_KEY_BLOCK = 64       # ... and keys per staged K / V block; stated here for the tests that walk the block edges
 

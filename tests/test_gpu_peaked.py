@@ -7,7 +7,7 @@ fp32 paths: bound = max(1e-4, 4 g), absolute + relative, g = the recorded distan
 inputs (peaked.py, re-asserted by test_peaked_host.py); ids by hypothesis_lists_match with that bound as its absolute tie tolerance (the
 host test holds the share of beam rows inside such a tie group under 5 %).  bf16 mode: against the oracle's
 bf16 emulation with float64 sums, 4 x the recorded max and mean distance between that emulation with fp32 and with float64 sums.
-Each case names the kernel its shape reaches through launch_attention (csrc/layers.hip) and prints its measured maximum error."""
+Each case names the kernel its shape reaches through launch_attention (csrc/attention.hip) and prints its measured maximum error."""
 import numpy as np
 import pytest
 import torch

@@ -9,7 +9,7 @@ stale maximum overflows.  No sequence here has an all-zero mask (fp32 quantises 
 stay with the fp32-oracle tests of test_gpu_t5_long.py).
 
 Under 128 keys — the instantiations of the one-pass kernels that no case of test_gpu_peaked.py reaches; each sizes its own LDS image.
-Each test names the kernel form its shape reaches through launch_attention (csrc/layers.hip) and prints its measured maximum error."""
+Each test names the kernel form its shape reaches through launch_attention (csrc/attention.hip) and prints its measured maximum error."""
 import numpy as np
 import pytest
 import torch
