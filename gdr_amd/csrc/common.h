@@ -237,6 +237,17 @@ __device__ __forceinline__ float wave_max(float v) {
   v = fmaxf(v, __shfl_xor(v, 16));
   return row16_max(v);
 }
+// the integer forms (the plan kernels' counts): the plain butterfly — the DPP rows above are a float trick
+__device__ __forceinline__ int wave_sum(int v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+  return v;
+}
+__device__ __forceinline__ int wave_max(int v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v = max(v, __shfl_xor(v, off));
+  return v;
+}
 // x / b for many x and one b > 0 (a norm's denominator): r = RN(1 / b) once — the hardware reciprocal and one Newton step —,
 // then per element q = x * r, the exact residual e = x - b * q (one fma) and q + e * r: the correctly rounded quotient
 // (Markstein: a faithful q corrected with the correctly rounded reciprocal), i.e. the bits of the IEEE division the reference's

@@ -15,7 +15,7 @@
 //           in flight per lane, narrow rows are packed side by side in one wave.
 //   IDS     out[i] = new_id[ids[i]]; negative ids kept; dead / out-of-range -> -1 and one atomicOr into the status word.
 //   MASK    a wave per 64 output rows and bitmap: lane l tests bit old_id[j] of the input, one ballot is two output words.
-#include "common.h"
+#include "scan.h"
 
 namespace gdr {
 
@@ -27,23 +27,6 @@ constexpr int64_t COMPACT_GRID = 2048;                 // workgroups of the memo
 
 static inline int64_t plan_tiles(int64_t N) { return ((N + 31) / 32 + PLAN_TILE_WORDS - 1) / PLAN_TILE_WORDS; }
 
-// word w of a bitmap over N rows; bits past N in the last word are ignored
-__device__ __forceinline__ uint32_t plan_word(const uint32_t* __restrict__ bm, int64_t w, int64_t N) {
-  uint32_t bits = bm[w];
-  const int64_t rem = N - w * 32;
-  if (rem < 32) bits &= (1u << rem) - 1u;
-  return bits;
-}
-
-__device__ __forceinline__ int wave_scan_incl(int v, int lane) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int t = __shfl_up(v, o);
-    if (lane >= o) v += t;
-  }
-  return v;
-}
-
 // ---- plan 1: tile_cnt[t] = live rows of tile t.  256 threads = 4 tiles per workgroup. ---------------------------------------------
 __global__ __launch_bounds__(256) void compact_count_kernel(const uint32_t* __restrict__ bm, int64_t N, int64_t n_tiles,
                                                             int32_t* __restrict__ tile_cnt) {
@@ -54,10 +37,9 @@ __global__ __launch_bounds__(256) void compact_count_kernel(const uint32_t* __re
 #pragma unroll
     for (int i = 0; i < PLAN_TILE_WORDS / 64; ++i) {
       const int64_t w = t * PLAN_TILE_WORDS + i * 64 + lane;
-      if (w < n_words) c += __popc(plan_word(bm, w, N));
+      if (w < n_words) c += __popc(bitmap_word(bm, w, N));
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off);
+    c = wave_sum(c);
     if (lane == 0) tile_cnt[t] = c;
   }
 }
@@ -67,23 +49,14 @@ __global__ __launch_bounds__(PLAN_SCAN_STEP) void compact_scan_kernel(int32_t* _
                                                                       int32_t* __restrict__ status) {
   __shared__ int wsum[PLAN_SCAN_STEP / 64];
   __shared__ int carry;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (tid == 0) carry = 0;
-  __syncthreads();
+  BlockScan<PLAN_SCAN_STEP> scan(wsum, &carry);
   for (int64_t t0 = 0; t0 < n_tiles; t0 += PLAN_SCAN_STEP) {  // workgroup-uniform
-    const int64_t t = t0 + tid;
-    const int c = t < n_tiles ? tile[t] : 0;  // every total <= N < 2^31
-    const int inc = wave_scan_incl(c, lane);
-    if (lane == 63) wsum[wave] = inc;
-    __syncthreads();
-    int before = carry;
-    for (int w = 0; w < wave; ++w) before += wsum[w];
-    if (t < n_tiles) tile[t] = before + inc - c;
-    __syncthreads();
-    if (tid == PLAN_SCAN_STEP - 1) carry = before + inc;
-    __syncthreads();
+    const int64_t t = t0 + threadIdx.x;
+    const int before = scan.round(t < n_tiles ? tile[t] : 0);  // every total <= N < 2^31
+    if (t < n_tiles) tile[t] = before;
   }
-  if (tid == 0) status[0] = (int64_t)carry != n_live ? 1 : 0;
+  const int total = scan.total();
+  if (threadIdx.x == 0) status[0] = (int64_t)total != n_live ? 1 : 0;
 }
 
 // ---- plan 3: new_id / old_id.  Grid as compact_count_kernel. --------------------------------------------------------------------------
@@ -98,7 +71,7 @@ __global__ __launch_bounds__(256) void compact_place_kernel(const uint32_t* __re
     for (int i = 0; i < PLAN_TILE_WORDS / 64; ++i) {
       const int64_t w0 = t * PLAN_TILE_WORDS + i * 64;
       if (w0 >= n_words) break;
-      const uint32_t bits = w0 + lane < n_words ? plan_word(bm, w0 + lane, N) : 0u;
+      const uint32_t bits = w0 + lane < n_words ? bitmap_word(bm, w0 + lane, N) : 0u;
       const int pc = __popc(bits);
       const int inc = wave_scan_incl(pc, lane);
       const int wbase = base + inc - pc;  // live rows in front of this lane's word

@@ -28,6 +28,7 @@
 #include "attention.h"
 #include "beam.h"
 #include "layers.h"
+#include "scan.h"
 
 namespace gdr {
 
@@ -185,7 +186,7 @@ __global__ __launch_bounds__(1024) void prefix_plan_kernel(BeamBufs bb, int rows
   // round 3 the workgroup walked the rows 1 024 at a time with three barriers per chunk: 470 us at 20 480 rows, at the head of
   // the adaptor chain of every step.)
   __shared__ int wsum[16];
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int tid = threadIdx.x;
   const int per = (rows + 1023) >> 10;
   const int r0 = tid * per, r1 = min(rows, r0 + per);
   int cnt = 0;
@@ -193,20 +194,8 @@ __global__ __launch_bounds__(1024) void prefix_plan_kernel(BeamBufs bb, int rows
     const int nd = bb.node[cur][r];
     cnt += (nd >= 0 && nd < n_table) ? 0 : 1;
   }
-  int inc = cnt;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int t = __shfl_up(inc, o);
-    if (lane >= o) inc += t;
-  }
-  if (lane == 63) wsum[wave] = inc;
-  __syncthreads();
-  int before = 0, total = 0;
-  for (int w = 0; w < 16; ++w) {
-    if (w < wave) before += wsum[w];
-    total += wsum[w];
-  }
-  int pos = before + inc - cnt;
+  int total;
+  int pos = block_scan_once<1024>(cnt, wsum, &total);
   for (int r = r0; r < r1; ++r) {
     const int nd = bb.node[cur][r];
     const bool miss = !(nd >= 0 && nd < n_table);

@@ -17,7 +17,7 @@
 //   gdr_kmeans_seed_dist: one greedy k-means++ seeding step over the same (node, tile) work list: fp32 squared
 //     distances of every row to its node's T candidates over one pinned summation tree without fma, per-tile integer potentials
 //     and maxima.  The draws, the prefix sums and the argmin between the steps are torch (gdr_amd/kmeans.py).
-#include "common.h"
+#include "scan.h"
 
 namespace gdr {
 namespace {
@@ -220,20 +220,12 @@ __global__ __launch_bounds__(256) void part_hist_kernel(const int32_t* __restric
 
 // one block: exclusive scan of m int32 counts in place (m = n_work * k < 2^31, total <= n_rows < 2^31)
 __global__ __launch_bounds__(1024) void part_scan_kernel(int32_t* __restrict__ a, int64_t m) {
-  __shared__ int32_t part[1024];
+  __shared__ int32_t wsum[16];
   const int t = threadIdx.x;
   const int64_t per = (m + 1023) / 1024, i0 = t * per, i1 = min(m, i0 + per);
   int32_t sum = 0;
   for (int64_t i = i0; i < i1; ++i) sum += a[i];
-  part[t] = sum;
-  __syncthreads();
-  for (int o = 1; o < 1024; o <<= 1) {
-    const int32_t v = t >= o ? part[t - o] : 0;
-    __syncthreads();
-    part[t] += v;
-    __syncthreads();
-  }
-  int32_t run = t ? part[t - 1] : 0;
+  int32_t run = block_scan_once<1024>(sum, wsum);
   for (int64_t i = i0; i < i1; ++i) {
     const int32_t c = a[i];
     a[i] = run;
@@ -277,19 +269,25 @@ __global__ void part_tail_kernel(const int32_t* __restrict__ node_off, int S, in
 // of every child that starts in it — of which only the last can be longer than a chunk.  So partial[2 slot + (chunk 0 ? 1 : 0)]
 // holds each long child's chunk sums without any index structure.
 constexpr int KC_CHUNK = 256;
-
+// rows[a] .. rows[b - 1] of D4 at this lane's column, added in that order from 0; 8 rows in flight, every load of a batch issued before the
+// first add, the next batch's ids loaded beside the current rows — centroid_kernel's loop (cluster_insert.hip), written out there
 __device__ __forceinline__ float4 seq_sum(const float4* __restrict__ D4, int64_t N, int d4, int col, bool on,
                                           const int32_t* __restrict__ rows, int a, int b) {
   float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+  int32_t mid[8];
+#pragma unroll
+  for (int u = 0; u < 8; ++u) mid[u] = a + u < b ? rows[a + u] : -1;
   for (int j = a; j < b; j += 8) {
     float4 x[8];
     bool ok[8];
 #pragma unroll
-    for (int u = 0; u < 8; ++u) {  // every load of the batch is issued before the first add
-      const int32_t m = j + u < b ? rows[j + u] : -1;
+    for (int u = 0; u < 8; ++u) {
+      const int32_t m = mid[u];
       ok[u] = m >= 0 && m < N;
       x[u] = (ok[u] && on) ? D4[(int64_t)m * d4 + col] : make_float4(0.f, 0.f, 0.f, 0.f);
     }
+#pragma unroll
+    for (int u = 0; u < 8; ++u) mid[u] = b - j > 8 + u ? rows[j + 8 + u] : -1;  // no j + 8 + u past INT_MAX
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
       if (ok[u]) {

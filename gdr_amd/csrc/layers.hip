@@ -7,6 +7,7 @@
 #include <stdlib.h>
 
 #include "layers.h"
+#include "scan.h"
 
 namespace gdr {
 
@@ -47,7 +48,7 @@ __global__ __launch_bounds__(256) void pack_len_kernel(const int64_t* __restrict
     last = on ? j : last;
   }
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
+  for (int o = 32; o > 0; o >>= 1) {  // sum and max in one butterfly (the parent's code: every kernel of the C2 step but pack_scan is)
     cnt += __shfl_xor(cnt, o);
     last = max(last, __shfl_xor(last, o));
   }
@@ -58,30 +59,16 @@ __global__ __launch_bounds__(1024) void pack_scan_kernel(int B, const int32_t* _
                                                          int32_t* __restrict__ seq_off, int64_t* __restrict__ rows_total) {
   __shared__ int wsum[16];
   __shared__ int carry;
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  if (tid == 0) carry = 0;
-  __syncthreads();
-  for (int base = 0; base < B; base += 1024) {
-    const int b = base + tid;
-    const int v = b < B ? seq_len[b] : 0;
-    int inc = v;  // inclusive scan inside the wave
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int t = __shfl_up(inc, o);
-      if (lane >= o) inc += t;
-    }
-    if (lane == 63) wsum[wave] = inc;
-    __syncthreads();
-    int before = carry;
-    for (int w = 0; w < wave; ++w) before += wsum[w];
-    if (b < B) seq_off[b] = before + inc - v;
-    __syncthreads();
-    if (tid == 1023) carry = before + inc;
-    __syncthreads();
+  BlockScan<1024> scan(wsum, &carry);
+  for (int base = 0; base < B; base += 1024) {  // workgroup-uniform
+    const int b = base + threadIdx.x;
+    const int before = scan.round(b < B ? seq_len[b] : 0);
+    if (b < B) seq_off[b] = before;
   }
-  if (tid == 0) {
-    seq_off[B] = carry;
-    *rows_total = carry;
+  const int total = scan.total();
+  if (threadIdx.x == 0) {
+    seq_off[B] = total;
+    *rows_total = total;
   }
 }
 

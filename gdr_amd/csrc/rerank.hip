@@ -23,6 +23,7 @@
 // lower position" (gdr_topk_merge_packed) of the per-shard lists reproduces the unsharded list bit for bit.
 #include <math.h>
 
+#include "scan.h"
 #include "select.h"
 
 namespace gdr {
@@ -383,9 +384,9 @@ __global__ __launch_bounds__(256) void cluster_candidates_kernel(GdrClusterIndex
   __shared__ int wsum[4];
   __shared__ int carry;
   const int b = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  if (tid == 0) carry = 0, off_s[0] = 0;
-  __syncthreads();
-  for (int j0 = 0; j0 < R; j0 += 256) {
+  BlockScan<256> scan(wsum, &carry);
+  if (tid == 0) off_s[0] = 0;
+  for (int j0 = 0; j0 < R; j0 += 256) {  // workgroup-uniform
     const int j = j0 + tid;
     int cl = -1, cnt = 0;
     if (j < R) {
@@ -419,21 +420,10 @@ __global__ __launch_bounds__(256) void cluster_candidates_kernel(GdrClusterIndex
       cl_s[j] = cl;
       cluster_of[(int64_t)b * R + j] = cl;
     }
-    int inc = cnt;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int t = __shfl_up(inc, o);
-      if (lane >= o) inc += t;
-    }
-    if (lane == 63) wsum[wave] = inc;
-    __syncthreads();
-    int before = carry;
-    for (int w = 0; w < wave; ++w) before += wsum[w];
-    if (j < R) off_s[j + 1] = before + inc;
-    __syncthreads();
-    if (tid == 255) carry = before + inc;
-    __syncthreads();
+    const int before = scan.round(cnt);
+    if (j < R) off_s[j + 1] = before + cnt;
   }
+  __syncthreads();  // off_s and cl_s are whole
   for (int j = tid; j <= R; j += 256) cand_offsets[(int64_t)b * (R + 1) + j] = off_s[j];
   for (int j = wave; j < R; j += 4) {  // a wave per segment
     const int cl = cl_s[j];

@@ -18,6 +18,7 @@
 //               The keys are a strict total order, so both give the same list bit for bit.
 //
 // The whole sequence is stream-ordered with no host synchronisation: every grid is sized from (B, cap) alone.
+#include "scan.h"
 #include "select.h"
 
 namespace gdr {
@@ -54,20 +55,6 @@ static RowsPlan rows_plan(int B, int64_t cap, int k, size_t base) {
 
 size_t sim_rows_workspace_bytes(int B, int64_t cap, int k) { return rows_plan(B, cap, k, 0).total; }
 
-__device__ __forceinline__ int wave_sum_int(int v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-
-// word w of a bitmap over N rows; bits past N in the last word are ignored
-__device__ __forceinline__ uint32_t rows_word(const uint32_t* __restrict__ bm, int64_t w, int64_t N) {
-  uint32_t bits = bm[w];
-  const int64_t rem = N - w * 32;
-  if (rem < 32) bits &= (1u << rem) - 1u;
-  return bits;
-}
-
 // words [w0, w1) of segment s
 __device__ __forceinline__ void rows_segment(int s, int64_t N, int64_t& w0, int64_t& w1) {
   const int64_t n_words = (N + 31) / 32, per = (n_words + ROWS_SEGS - 1) / ROWS_SEGS;
@@ -84,8 +71,8 @@ __global__ __launch_bounds__(256) void rows_count_kernel(const uint32_t* __restr
   for (int64_t q = blockIdx.y; q < B; q += gridDim.y) {
     const uint32_t* bm = bitmaps + q * qstride;
     int c = 0;  // <= N < 2^31
-    for (int64_t w = w0 + lane; w < w1; w += 64) c += __popc(rows_word(bm, w, N));
-    c = wave_sum_int(c);
+    for (int64_t w = w0 + lane; w < w1; w += 64) c += __popc(bitmap_word(bm, w, N));
+    c = wave_sum(c);
     if (lane == 0) segcnt[q * ROWS_SEGS + s] = c;
   }
 }
@@ -93,12 +80,13 @@ __global__ __launch_bounds__(256) void rows_count_kernel(const uint32_t* __restr
 // ---- 2: counts, status and the flat unit list.  One workgroup. ---------------------------------------------------------------------
 __global__ __launch_bounds__(1024) void rows_units_kernel(const int32_t* __restrict__ segcnt, int B, int cap, int32_t* __restrict__ cnt,
                                                           int32_t* __restrict__ status, int32_t* __restrict__ unit_off) {
+  // scan.h's BlockScan<1024> written out around its wave scan: through the struct 10.18 - 10.27 us per launch against the parent's 10.15 - 10.20
   __shared__ int wsum[16];
   __shared__ int carry;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   if (tid == 0) carry = 0;
   __syncthreads();
-  for (int q0 = 0; q0 < B; q0 += 1024) {
+  for (int q0 = 0; q0 < B; q0 += 1024) {  // workgroup-uniform
     const int q = q0 + tid;
     int units = 0;
     if (q < B) {
@@ -114,12 +102,7 @@ __global__ __launch_bounds__(1024) void rows_units_kernel(const int32_t* __restr
       if (status) status[q] = total > cap ? 1 : 0;  // the list is the top-k of the first cap allowed rows
       units = (n + ROWS_UNIT - 1) / ROWS_UNIT;
     }
-    int inc = units;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int t = __shfl_up(inc, o);
-      if (lane >= o) inc += t;
-    }
+    const int inc = wave_scan_incl(units, lane);
     if (lane == 63) wsum[wave] = inc;
     __syncthreads();
     int before = carry;
@@ -139,19 +122,14 @@ __global__ __launch_bounds__(256) void rows_place_kernel(const uint32_t* __restr
   int64_t w0, w1;
   rows_segment(s, N, w0, w1);
   for (int64_t q = blockIdx.y; q < B; q += gridDim.y) {
-    int64_t base = wave_sum_int(lane < s ? segcnt[q * ROWS_SEGS + lane] : 0);  // allowed rows in front of this segment
+    int64_t base = wave_sum(lane < s ? segcnt[q * ROWS_SEGS + lane] : 0);  // allowed rows in front of this segment
     const uint32_t* bm = bitmaps + q * qstride;
     int32_t* out = ids + q * cap;
     for (int64_t t0 = w0; t0 < w1 && base < cap; t0 += 64) {  // wave-uniform bounds
       const int64_t w = t0 + lane;
-      uint32_t bits = w < w1 ? rows_word(bm, w, N) : 0u;
+      uint32_t bits = w < w1 ? bitmap_word(bm, w, N) : 0u;
       const int pc = __popc(bits);
-      int inc = pc;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(inc, o);
-        if (lane >= o) inc += t;
-      }
+      const int inc = wave_scan_incl(pc, lane);
       const int total = __shfl(inc, 63);
       int64_t pos = base + inc - pc;
       while (bits != 0u && pos < cap) {

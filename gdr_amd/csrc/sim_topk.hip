@@ -28,6 +28,7 @@
 #include <mutex>
 #include <tuple>
 
+#include "scan.h"
 #include "select.h"
 
 namespace gdr {
@@ -767,15 +768,9 @@ __global__ __launch_bounds__(256) void sim_live_thr_fixup_kernel(const uint32_t*
   int c = 0;
   for (int64_t e = threadIdx.x; e < n_sample_tiles * (TILE / 32); e += 256) {
     const int64_t w = (e / (TILE / 32)) * stride * (TILE / 32) + e % (TILE / 32);
-    if (w < n_words) {
-      uint32_t bits = live[w];
-      const int64_t rem = N - w * 32;
-      if (rem < 32) bits &= (1u << rem) - 1u;  // bits past N in the last word are ignored
-      c += __popc(bits);
-    }
+    if (w < n_words) c += __popc(bitmap_word(live, w, N));
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off);
+  c = wave_sum(c);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = c;
   __syncthreads();
   if (red[0] + red[1] + red[2] + red[3] >= k) return;

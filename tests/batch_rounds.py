@@ -1,9 +1,11 @@
 """Cases, CPU-side builders and references of the batches that need more than one round of a one-workgroup "plan" kernel:
 pack_scan_kernel (csrc/layers.hip: seq_off[] and the live-row count of every packed forward), rows_units_kernel (csrc/sim_rows.hip:
 counts, status and the unit list of the gather top-k) and prefix_plan_kernel (csrc/decode.hip: the hit / miss compaction of the beam
-rows).  All three walk their batch ROUND = 1024 entries at a time; the first two hand an LDS carry from round to round, the third
-gives every thread ceil(rows / 1024) consecutive rows.  tests/test_batch_rounds_host.py checks on the CPU that every case reaches
-what it names; tests/test_gpu_batch_rounds.py runs the cases on the GPU.  No test lives here.
+rows).  Their prefix sums are csrc/scan.h's block scan, ROUND = 1024 threads wide: the first two in its round form (one round per 1024
+entries, a carry between the rounds; rows_units_kernel is that loop written out), the third in its single-shot form (every thread sums
+ceil(rows / 1024) consecutive rows first) — as are insert_scan_kernel's (csrc/cluster_insert.hip, section 4) and part_scan_kernel's
+(csrc/kmeans.hip, section 5).  tests/test_batch_rounds_host.py checks on the CPU that every case reaches what it names;
+tests/test_gpu_batch_rounds.py (and, for section 5, tests/test_gpu_kmeans.py) runs the cases on the GPU.  No test lives here.
 
 Every bound below either names the existing test it was taken from (`source`) or carries the figure it was measured from and the
 margin (`measured`, `margin`) — never a kernel's output.
@@ -450,6 +452,32 @@ def insert_case():
     targets = rng.integers(0, INSERT_C, INSERT_NEW).astype(np.int32)
     targets[:8] = [1023, 1024, 1024, 2047, 2048, 2048, 0, 1022]
     return offsets, members, new_ids, targets
+
+
+REMOVE_EMPTIED = (1022, 1024, 2046, 2048)  # clusters that lose every member: on either side of the thread boundaries of per = 3
+
+
+@functools.lru_cache(maxsize=None)
+def remove_case():
+    """(offsets, members, ids int32 strictly ascending) over insert_case's CSR — the removal mode of insert_scan_kernel (a negative
+    histogram) at the same C = 2049: every member of the REMOVE_EMPTIED clusters, 400 members drawn at random, and one id that is a
+    member of no cluster."""
+    offsets, members, _, _ = insert_case()
+    rng = np.random.default_rng(78)
+    gone = [members[offsets[c]:offsets[c + 1]] for c in REMOVE_EMPTIED]
+    ids = np.unique(np.concatenate(gone + [rng.choice(members, 400, replace=False), [members.size + 7]])).astype(np.int32)
+    return offsets, members, ids
+
+
+# ==================================================================================================== 5. k-means partition
+KP_TILE = 256                              # csrc/kmeans.hip KP_TILE: rows of one partition work item
+# (k, node sizes): part_scan_kernel scans m = k * (tiles of 256 rows over the nodes) counts, per = ceil(m / 1024) consecutive ones per
+# thread: m = 1024 (one entry per thread), 1025 (per = 2, threads 0 .. 512 own entries), 1023 (the last thread owns none)
+PARTITION_CASES = ((64, (4096,)), (41, (6400,)), (33, (256,) * 31))
+
+
+def partition_scan_entries(k, sizes):
+    return k * sum(-(-s // KP_TILE) for s in sizes)
 
 
 if __name__ == "__main__":

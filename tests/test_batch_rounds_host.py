@@ -197,3 +197,26 @@ def test_insert_case_spans_three_clusters_per_thread():
     assert targets.min() >= 0 and targets.max() < C and {1023, 1024, 2047, 2048} <= set(targets.tolist())
     o, m = expand_ref.merge(offsets, members, new_ids, targets)
     assert o[-1] == members.size + BR.INSERT_NEW == m.size
+
+
+def test_remove_case_empties_clusters_and_names_an_absent_id():
+    import lifecycle_ref
+    offsets, members, ids = BR.remove_case()
+    C = BR.INSERT_C
+    assert offsets.size == C + 1 and -(-C // BR.ROUND) == 3
+    assert (np.diff(ids) > 0).all() and ids[-1] == members.size + 7 and not np.isin(ids[-1], members)
+    sizes = np.diff(offsets)
+    assert all(sizes[c] > 0 for c in BR.REMOVE_EMPTIED)
+    o, m, gone = lifecycle_ref.remove(offsets, members, ids)
+    left = np.diff(o)
+    assert all(left[c] == 0 for c in BR.REMOVE_EMPTIED) and gone == ids.size - 1 >= 400
+    assert o[-1] == m.size == members.size - gone and 0 < left.max() <= sizes.max()
+    assert (left < sizes).sum() > 300 and (left == sizes).sum() > 300      # clusters that lose members beside clusters that keep all
+
+
+# ------------------------------------------------------------------------------------------------------------ k-means partition
+def test_partition_cases_sit_on_either_side_of_one_entry_per_thread():
+    m = [BR.partition_scan_entries(k, sizes) for k, sizes in BR.PARTITION_CASES]
+    assert m == [1024, 1025, 1023] and [-(-x // BR.ROUND) for x in m] == [1, 2, 1]
+    assert [(k, len(sizes), sum(sizes)) for k, sizes in BR.PARTITION_CASES] == [(64, 1, 4096), (41, 1, 6400), (33, 31, 7936)]
+    assert all(k <= 64 for k, _ in BR.PARTITION_CASES)                     # csrc/kmeans.hip KM_MAX_K

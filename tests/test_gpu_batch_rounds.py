@@ -1,7 +1,9 @@
 """Batches past one round of the one-workgroup plan kernels (cases, builders and references: tests/batch_rounds.py; their premises on the
-CPU: tests/test_batch_rounds_host.py).  Which case enters which round count:
+CPU: tests/test_batch_rounds_host.py).  The scans are csrc/scan.h's: the round form (BlockScan<1024>::round per 1024 entries, a carry
+between the rounds; rows_units_kernel is that loop written out) and the single-shot form (block_scan_once over the 1024 thread sums of
+ceil(n / 1024) consecutive entries each).  Which case enters which round count:
 
-pack_scan_kernel (csrc/layers.hip; `for (base = 0; base < B; base += 1024)` with an LDS carry) — every packed forward of both towers:
+pack_scan_kernel (csrc/layers.hip; round form) — every packed forward of both towers:
   B = 1023, L = 24    one partial round (threads 1023 idle)
   B = 1024, L = 24    exactly one round
   B = 1025, L = 24    two rounds, the second with one sequence; pooled-only fp32 T5 stays one chain (the halves do not pack)
@@ -10,18 +12,24 @@ pack_scan_kernel (csrc/layers.hip; `for (base = 0; base < B; base += 1024)` with
   forms: T5 fp32 / bf16 and the doc tower's fp32 bit for bit against the padded form of the same handle (which has no plan);
   T5 split 6 / 3 / 2 terms and the doc tower's bf16 / split against the float64 CPU oracle on the sequences on either side of
   every round boundary, the split forms also against the fp32 packed form on every sequence.
-rows_units_kernel (csrc/sim_rows.hip; the same loop and carry) — ops.sim_topk(gather=4096), fp32 and bf16 corpus:
+rows_units_kernel (csrc/sim_rows.hip; round form) — ops.sim_topk(gather=4096), fp32 and bf16 corpus:
   B = 1024            exactly one round
   B = 1025            two rounds, the second with one query
   B = 2050            three rounds, the third with two queries
   every query against the same call on slices of <= 512 queries (one round each), the sampled ones against float64 scores.
-prefix_plan_kernel (csrc/decode.hip; per = ceil(rows / 1024) consecutive rows per thread) — generate() with a prefix table:
+prefix_plan_kernel (csrc/decode.hip; single-shot form, per = ceil(rows / 1024) consecutive rows per thread) — generate() with a prefix table:
   B = 171, R = 6      1026 rows: per = 2, threads 0 .. 512 own rows
   B = 350, R = 6      2100 rows: per = 3, threads 0 .. 699 own rows
   both with holes in the trie's second level (keep_every 3 and 7): hit and miss rows inside one thread's rows at step 2.
-insert_scan_kernel (csrc/cluster_insert.hip; per = ceil(C / 1024) clusters per thread) — test_gpu_expand.py reaches C = 2000 through
-  add_documents, but only compares one call with three; no test compares a merge at C > 1024 with tests/expand_ref.py.  One case:
-  C = 2049        per = 3, threads 0 .. 682 own clusters, against expand_ref.merge exactly.
+insert_scan_kernel (csrc/cluster_insert.hip; single-shot form over int64 sums, per = ceil(C / 1024) clusters per thread, a block maximum
+  beside it) — test_gpu_expand.py reaches C = 2000 through add_documents, but only compares one call with three; test_gpu_lifecycle.py
+  removes from 9 clusters.  Two cases at C = 2049 (per = 3, threads 0 .. 682 own clusters):
+  insert          against expand_ref.merge exactly.
+  removal         a negative histogram, clusters emptied on either side of the thread boundaries, an id in no cluster: against
+                  lifecycle_ref.remove exactly, out_max = the largest surviving cluster.
+part_scan_kernel (csrc/kmeans.hip; single-shot form) at 1024 / 1025 / 1023 scan entries: tests/test_gpu_kmeans.py
+  test_partition_is_a_stable_counting_sort (batch_rounds.PARTITION_CASES).  cluster_candidates_kernel (csrc/rerank.hip; round form at
+  256 threads) at R = 256 / 257: tests/test_gpu_rerank.py test_cluster_candidates_on_either_side_of_one_scan_round.
 """
 import gc
 
@@ -297,3 +305,19 @@ def test_cluster_insert_at_2049_clusters(dev):
         assert np.array_equal(o.cpu().numpy(), want_o), "offsets differ from tests/expand_ref.py"
         assert np.array_equal(m.cpu().numpy(), want_m), "members differ from tests/expand_ref.py"
         assert mx == int(np.diff(want_o).max())
+
+
+def test_cluster_remove_at_2049_clusters(dev):
+    """insert_scan_kernel over a NEGATIVE histogram (the removal mode) at per = 3: clusters emptied on either side of the thread
+    boundaries, an id that is in no cluster; against tests/lifecycle_ref.py exactly, the largest SURVIVING cluster included."""
+    import lifecycle_ref
+    from gdr_amd import ops
+    offsets, members, ids = BR.remove_case()
+    want_o, want_m, want_n = lifecycle_ref.remove(offsets, members, ids)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)   # noqa: E731
+    for _ in range(2):
+        o, m, mx, gone = ops.cluster_remove(up(offsets), up(members), up(ids))
+        _no_fault()
+        assert np.array_equal(o.cpu().numpy(), want_o), "offsets differ from tests/lifecycle_ref.py"
+        assert np.array_equal(m.cpu().numpy(), want_m), "members differ from tests/lifecycle_ref.py"
+        assert mx == int(np.diff(want_o).max()) and gone == want_n == ids.size - 1

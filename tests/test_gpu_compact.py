@@ -21,7 +21,8 @@ pytestmark = pytest.mark.gpu
 
 TOL = 1e-4                         # oracle/parity_rules.py, as tests/test_gpu_live_search.py uses it
 # csrc/compact.hip: a wave sweeps a chunk of 64 bitmap words (PLAN_CHUNK_ROWS), a tile is PLAN_TILE_WORDS = 128 words (a wave per
-# tile), a workgroup holds 4 waves (PLAN_BLOCK_ROWS), and the one-workgroup scan takes PLAN_SCAN_STEP = 1024 tiles per step
+# tile), a workgroup holds 4 waves (PLAN_BLOCK_ROWS), and the one-workgroup scan (csrc/scan.h BlockScan) takes PLAN_SCAN_STEP = 1024
+# tiles per round
 PLAN_CHUNK_ROWS = 64 * 32
 PLAN_TILE_ROWS = 128 * 32
 PLAN_BLOCK_ROWS = 4 * PLAN_TILE_ROWS

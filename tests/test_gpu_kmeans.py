@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+import batch_rounds as BR
 import expand_ref
 import kmeans_ref as kr
 from conftest import REPO, golden
@@ -135,7 +136,8 @@ def test_a_node_alone_and_inside_a_level_gets_the_same_bits(dev):
 
 def test_partition_is_a_stable_counting_sort(dev):
     rng = np.random.default_rng(2)
-    for k, sizes in ((30, [70000, 1, 255, 256, 257, 31, 5000]), (64, [3, 1000]), (2, [513])):
+    # batch_rounds.PARTITION_CASES: part_scan_kernel at 1024, 1025 and 1023 scan entries (one per thread, two, and an idle last thread)
+    for k, sizes in ((30, [70000, 1, 255, 256, 257, 31, 5000]), (64, [3, 1000]), (2, [513])) + BR.PARTITION_CASES:
         n = sum(sizes)
         off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
         rows = np.concatenate([np.sort(rng.choice(10 ** 6, s, replace=False)) for s in sizes]).astype(np.int32)

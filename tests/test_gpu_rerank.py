@@ -79,6 +79,33 @@ def test_cluster_candidates_device_equals_host_lookup(dev):
     assert cl.tolist() == want_cl and cl[13] == 5 and cl[20] == 6 and cl[7] == -1 and (cl[R * 4:R * 5] == -1).all()
 
 
+@pytest.mark.parametrize("R", [256, 257])
+def test_cluster_candidates_on_either_side_of_one_scan_round(dev, R):
+    """cluster_candidates_kernel scans the cluster sizes of a query's R beam rows 256 at a time (csrc/scan.h BlockScan<256>): R = 256 is
+    exactly one round, R = 257 a second round of one row.  Two queries over a small index, against the host lookup; the last row of
+    each query names a cluster, so the carry into the second round shows in the last offset."""
+    from gdr_amd import codec, ops
+    V, ml, B = 30, 10, 2
+    index, names, depth = _index(600, 3, V)
+    rng = np.random.Generator(np.random.PCG64(R))
+    picks = [int(rng.integers(0, len(names))) for _ in range(B * R)]
+    picks[5], picks[254], picks[R + 40] = "unknown", "empty", "unknown"
+    rows = _rows_for(names, picks, V, ml, rng)
+    dec = codec.dec_2d(codec.decode_token(rows, kary=V, output_vocab_size=V), R)
+    offs_h, ids_h, max_h = index.candidates(dec)
+    offs_h, ids_h = offs_h.numpy(), ids_h.numpy()
+    cl, offs, ids, stride = ops.DeviceClusterIndex(index, dev, V).candidates(torch.from_numpy(rows).to(dev), B, R)
+    assert stride == R * 3 and max_h <= stride
+    offs, ids, cl = offs.cpu().numpy(), ids.cpu().numpy(), cl.cpu().numpy()
+    assert cl.tolist() == [index.lookup.get(s, -1) for row in dec for s in row] and (cl >= 0).sum() == B * R - 3
+    for b in range(B):
+        base = offs_h[b * R]
+        assert np.array_equal(offs[b], offs_h[b * R:(b + 1) * R + 1] - base), b
+        n = offs[b, R]
+        assert n == 3 * (cl[b * R:(b + 1) * R] >= 0).sum() and offs[b, R] > offs[b, R - 1]
+        assert np.array_equal(ids[b, :n], ids_h[base:base + n]), b
+
+
 @pytest.mark.parametrize("B,R,csz,k", [(64, 10, 12, 10), (2, 100, 12, 100), (1, 100, 12, 100), (3, 100, 30, 100)])
 def test_rerank_at_c3_and_infer_sh_widths_vs_oracle(dev, B, R, csz, k):
     """The rerank at C3's shape (64 x 10 beams x 12-doc clusters) and at infer.sh's (100 beams: ~1 200 candidates, k = 100,

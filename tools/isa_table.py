@@ -56,7 +56,7 @@ def kernels(paths):
 def demangle(names):
     try:
         res = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True, check=True).stdout.split("\n")
-        return dict(zip(names, res))
+        return dict(zip(names, (r.replace("(anonymous namespace)::", "") for r in res)))
     except (OSError, subprocess.CalledProcessError):
         return {n: n for n in names}
 

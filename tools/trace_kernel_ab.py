@@ -47,7 +47,7 @@ def main():
         mp, mh = [r[n][1] / r[n][0] / 1e3 for r in P], [r[n][1] / r[n][0] / 1e3 for r in H]
         lo, hi = min(mp), max(mp)
         verdict = ", ".join("SLOWER" if x > hi else ("faster" if x < lo else "inside") for x in mh) if len(P) > 1 else "%.3f" % (mh[0] / mp[0])
-        print("%-44s %7d  %-28s %-28s %s%s" % (re.sub(r"^void gdr::|^gdr::|\(.*", "", n)[:44], calls[0], " ".join("%.2f" % x for x in mp),
+        print("%-44s %7d  %-28s %-28s %s%s" % (re.sub(r"^void gdr::|^gdr::|\(.*", "", n.replace("(anonymous namespace)::", ""))[:44], calls[0], " ".join("%.2f" % x for x in mp),
                                                 " ".join("%.2f" % x for x in mh), verdict, "" if len(set(calls)) == 1 else "  !! calls differ"))
     print("verdict: %s" % ("names and call counts equal" if not bad else "DIFFERENT names or call counts"))
     return bad
